@@ -10,6 +10,11 @@ LIPs, nquad 75, lmmax=[20,20], lpad 10 -> Nrad 70, Nang 61, Nbf 4230; XC grid ld
 --symmetry 1 (three m-blocks of 1470/1380/1380).  One "step" = one SCF iteration's hot path:
 J(P) + XC(P) -> F = sym(H0+J+XC) -> eig_gsym_sub(F) -> P = C_occ C_occ^T, inputs resident in HBM.
 Density: the core-Hamiltonian guess orbitals (deterministic, synthetic - no files).
+
+A plain run sets up, warms up, times the steps and prints the headline (`value` = `ms_per_step`).  `--full` adds what
+takes work of its own: HIP-event times per stage during the timed steps (`stages_ms`, `roofline`, `stage_rooflines`),
+a self-check step from the guess density (`check`) and the CPU baseline (`cpu_baseline`).  `--dump-outputs DIR` writes
+what the last timed step computed (see dump_outputs).
 """
 import argparse
 import json
@@ -295,17 +300,48 @@ def cpu_baseline(w, bval, lval, mval, ldft, mdft, P, F, Sinvh, blocks):
                        % (tJ, len(pts), NQ, w["nelem"], nth, tXC_sample, NQ / float(len(pts)), sizes, cores, tE, ksample))
 
 
+def dump_outputs(step, outdir, nsample=1 << 20, seed=20261016):
+    """What the timed path hands its caller after its last step, as float64 .npy files in outdir: the eigenvalues E
+    (eigenvalues.npy), the XC quadrature's Exc, Nel, Ekin (xc_scalars.npy), and the Fock matrix F and the total density
+    P at the same `nsample` entries inside the symmetry blocks (fock_sample.npy, density_sample.npy; outside the blocks
+    both are zero by construction, and at Nbf = 4230 the whole matrices are 143 MB each).  The entries are drawn without
+    replacement by a generator with a fixed seed and kept in ascending order of (block, row, column), all of them when
+    the blocks hold fewer.  The orbitals C are left out: the sign of each column is arbitrary, P = 2 C_occ C_occ^T carries
+    what the occupied ones determine."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    N = step.N
+    ptr, idx = step.blk_ptr, step.blk_idx
+    sizes = np.diff(ptr)
+    ends = np.cumsum(sizes * sizes)
+    total = int(ends[-1])
+    k = np.sort(np.random.default_rng(seed).choice(total, size=min(nsample, total), replace=False))
+    b = np.searchsorted(ends, k, side="right")
+    r = k - (ends[b] - sizes[b] * sizes[b])
+    i = idx[ptr[b] + r // sizes[b]]
+    j = idx[ptr[b] + r % sizes[b]]
+    flat = torch.from_numpy(i + j * N).to(step.dev)  # column-major N x N
+    out = {"eigenvalues": step.E, "xc_scalars": step.scal, "fock_sample": step.F[flat], "density_sample": step.P[flat]}
+    for name, t in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="n2_pbe_nbf4230")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-stage times and rooflines of the timed steps, the self-check step and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--symmetry", type=int, default=1, help="0: one unsymmetrised eigenproblem; 1 (reference default): m blocks")
     ap.add_argument("--density", default="core", choices=["core", "seeded"],
                     help="start density: occupied orbitals of the core Hamiltonian, or BASELINE.md's seeded mt19937_64 orbitals")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import helfem_amd as hf
@@ -354,8 +390,9 @@ def main():
         one_step()
     torch.cuda.synchronize()
     step.set_density(P0, C_guess)
-    ctx.profile(True)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile(True)
+        ctx.profile_reset()
     parallel.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -366,21 +403,24 @@ def main():
     dt = time.perf_counter() - t0
     dt = parallel.max_over_ranks(dt, device=step.dev if (world > 1 or parallel.forced()) else "cpu")
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step, args.dump_outputs)
 
-    fams = {}
-    for name in ("coulomb", "xc", "scatter", "eig_reduce", "eig_tridiag", "eig_tridiag_solve", "eig_backtransform",
-                 "gemm", "eig_products", "density", "k_trdp", "exchange", "exl_element_gemm", "exl_element_gemm_gflop"):
-        ms, n = ctx.profile_get(name)
-        fams[name] = dict(ms_per_step=ms / args.steps, calls=n)
-    ctx.profile(False)
-    # self-check of the timed path, independent of the number of ranks: ONE step from the fixed guess density
-    # (the undamped iteration itself is chaotic from a core guess, its later iterates are not comparable)
-    step.set_density(P0, C_guess)
-    one_step()
-    torch.cuda.synchronize()
-    check = {"sum_lowest_eigenvalues_after_one_step": float(step.E[:w["nocc"]].sum().item()),
-             "sum_all_eigenvalues_after_one_step": float(step.E.sum().item()),
-             "xc_energy_after_one_step": float(step.scal[0].item())}
+    fams, check = {}, None
+    if args.full:
+        for name in ("coulomb", "xc", "scatter", "eig_reduce", "eig_tridiag", "eig_tridiag_solve", "eig_backtransform",
+                     "gemm", "eig_products", "density", "k_trdp", "exchange", "exl_element_gemm", "exl_element_gemm_gflop"):
+            ms, n = ctx.profile_get(name)
+            fams[name] = dict(ms_per_step=ms / args.steps, calls=n)
+        ctx.profile(False)
+        # self-check of the timed path, independent of the number of ranks: ONE step from the fixed guess density
+        # (the undamped iteration itself is chaotic from a core guess, its later iterates are not comparable)
+        step.set_density(P0, C_guess)
+        one_step()
+        torch.cuda.synchronize()
+        check = {"sum_lowest_eigenvalues_after_one_step": float(step.E[:w["nocc"]].sum().item()),
+                 "sum_all_eigenvalues_after_one_step": float(step.E.sum().item()),
+                 "xc_energy_after_one_step": float(step.scal[0].item())}
 
     # dominant kernel, measured live: all its launches of one eigensolve replayed back to back between two HIP
     # events on the launch stream (3 repetitions, the last is kept)
@@ -388,7 +428,7 @@ def main():
     ctx_gemv = (0.0, 0)
     trd_kernel = TRD_KERNEL
     trdp_shapes = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         if fams["k_trdp"]["calls"] > 0:
             # persistent tridiagonalisation: ONE cooperative launch per eigensolve, timed by HIP events around each of
             # the launches of the timed region itself on the launch stream (nothing to replay: the kernel consumes its input)
@@ -406,49 +446,6 @@ def main():
 
     if rank == 0:
         sizes = [len(b) for b in blocks]
-        my_sizes = [n for ib, n in enumerate(sizes) if ib % world == 0]
-        # Dominant kernel: k_trdb_gemv, the trailing-matrix sweep y = A22 v of the Householder tridiagonalisation
-        # (one launch per column, all symmetry blocks batched).  Algorithmic bytes: every Householder
-        # column streams one triangle of the trailing matrix once, 4 (n-k)^2 B; summed over the columns of a
-        # block that is (4/3) n^3 B.  Duration: HIP events around every launch on the launch stream.
-        gemv_ms, gemv_launches = ctx_gemv
-        launches_per_step = float(gemv_launches) / (args.steps if trd_kernel == "k_trdp" else 1.0)
-        alg_bytes_step = sum(sum(4.0 * float(n - k - 1) ** 2 for k in range(n - 2)) for n in my_sizes)
-        alg_bytes = alg_bytes_step / launches_per_step if launches_per_step else 0.0
-        avg_ms = gemv_ms / gemv_launches if gemv_launches else 0.0
-        trd_ms = fams["eig_tridiag"]["ms_per_step"]
-        achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        # HBM-side bytes per launch of the same kernel from the committed PMC passes of this command
-        # (tools/gpu_round.sh: separate FETCH_SIZE / WRITE_SIZE runs, FETCH_SIZE doubled as the gfx950 guide
-        # prescribes; tools/pmc_traffic.py).  The counters cannot be collected from inside this process.
-        traffic = None
-        traffic_file = None
-        try:
-            if world == 1:
-                import glob
-                pat = "r[0-9][0-9]_pmc_traffic.json" if args.workload == "n2_pbe_nbf4230" else "r[0-9][0-9]_exchange_pmc_traffic_%s.json" % args.workload
-                traffic_file = sorted(glob.glob(os.path.join(ROOT, "profiles", pat)))[-1]
-                with open(traffic_file) as fh:
-                    tj = json.load(fh)
-                meta = tj.pop("_meta", {})
-                if meta.get("kernel_sources_sha256", kernel_sources_sha()) == kernel_sources_sha():  # stale figures are dropped
-                    if trdp_shapes:
-                        # all launches of one eigensolve (one per phase, each its own template instance
-                        # "void hfg::k_trdp<R, U, false>"), averaged per launch like `achieved`
-                        tot, cnt = 0.0, 0.0
-                        for nm, rec_s in trdp_shapes.items():
-                            key = "void hfg::" + nm[:-1] + ", false>"
-                            if key in tj and tj[key].get("traffic_bytes_per_launch") is not None:
-                                tot += tj[key]["traffic_bytes_per_launch"] * rec_s["launches_per_step"]
-                                cnt += rec_s["launches_per_step"]
-                        if cnt == sum(r["launches_per_step"] for r in trdp_shapes.values()) and cnt > 0:
-                            traffic = tot / cnt
-                    else:
-                        for kname, rec in tj.items():  # "hfg::k_trdf<1024>" or "hfg::k_trdb_gemv"
-                            if ("hfg::" + trd_kernel) in kname:
-                                traffic = rec.get("traffic_bytes_per_launch")
-        except Exception:
-            traffic = None
         out = {
             "metric": "scf_iteration_wall_time_fock_plus_geneig_nbf4230" if args.workload == "n2_pbe_nbf4230"
             else "scf_iteration_wall_time_" + args.workload,
@@ -471,66 +468,112 @@ def main():
                        "timed_path": "device-resident step (hfg_*_dev entry points on HBM buffers: the loop body of hfg_scf_run, "
                                      "which the diatomic/atomic executables and helfem::gpu::run_scf call); the host-pointer "
                                      "entry points (hfg_coulomb, hfg_eig_gsym_sub, ...) add ~12 ms of PCIe per call"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                         "frac": achieved / 8000.0, "traffic": traffic,
-                         "traffic_source": ("profiles/%s (committed rocprofv3 --pmc passes of this command, not "
-                                            "measured in this run)" % os.path.basename(traffic_file)) if traffic is not None else None,
-                         "kernel": "hfg::" + trd_kernel, "algorithmic_bytes_per_launch": alg_bytes,
-                         "avg_launch_us": avg_ms * 1e3, "launches_per_step": launches_per_step,
-                         "launches_by_tile_shape": trdp_shapes,
-                         "note": ("persistent cooperative launches, one per phase of an eigensolve (a phase ends when the "
-                                  "trailing matrices fit the next narrower register tile), the trailing matrices resident in "
-                                  "the register file: the algorithmic bytes (one triangle of the trailing matrix per Householder "
-                                  "column, SURVEY 8d) never cross HBM; achieved = algorithmic bytes of an eigensolve / time of its "
-                                  "launches; bound by one exchange between workgroups per column (DESIGN.md 3.4)")
-                         if trd_kernel == "k_trdp" else
-                         "latency-bound: one dependent launch per Householder column (see DESIGN.md 3.4)"},
-            "stages_ms": {k: round(v["ms_per_step"], 4) for k, v in fams.items()},
-            # the other stages against their own bounds (stage time of this run, algorithmic work)
-            "stage_rooflines": stage_rooflines(basis, w, my_sizes, fams),
-            # size-independent self-check of the timed path: must not depend on the number of ranks
-            "check": check,
         }
-        if kfrac != 0.0 and fams["exl_element_gemm"]["calls"] > 0:
-            # exact-exchange workloads: the dominant kernel of the exchange build is the in-element task-list GEMM
-            # (k_dgemm_tasklist_wl: C[p^2 x pairs] = ktei[p^2 x 4 p^2] RB[4 p^2 x pairs] per table slot and element).
-            # achieved = USEFUL flops (no tile padding) / HIP-event time of its launches in the timed region.
-            g_ms = fams["exl_element_gemm"]["ms_per_step"] * args.steps
-            g_n = fams["exl_element_gemm"]["calls"]
-            g_gflop = fams["exl_element_gemm_gflop"]["ms_per_step"] * args.steps  # accumulated GFLOP (see exchange_lr.hip)
-            tf = g_gflop / g_ms if g_ms > 0 else 0.0  # GFLOP / ms = TFLOP/s
-            ktraffic, ktraffic_file = None, None
+        if args.full:
+            my_sizes = [n for ib, n in enumerate(sizes) if ib % world == 0]
+            # Dominant kernel: k_trdb_gemv, the trailing-matrix sweep y = A22 v of the Householder tridiagonalisation
+            # (one launch per column, all symmetry blocks batched).  Algorithmic bytes: every Householder
+            # column streams one triangle of the trailing matrix once, 4 (n-k)^2 B; summed over the columns of a
+            # block that is (4/3) n^3 B.  Duration: HIP events around every launch on the launch stream.
+            gemv_ms, gemv_launches = ctx_gemv
+            launches_per_step = float(gemv_launches) / (args.steps if trd_kernel == "k_trdp" else 1.0)
+            alg_bytes_step = sum(sum(4.0 * float(n - k - 1) ** 2 for k in range(n - 2)) for n in my_sizes)
+            alg_bytes = alg_bytes_step / launches_per_step if launches_per_step else 0.0
+            avg_ms = gemv_ms / gemv_launches if gemv_launches else 0.0
+            trd_ms = fams["eig_tridiag"]["ms_per_step"]
+            achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            # HBM-side bytes per launch of the same kernel from the committed PMC passes of this command
+            # (tools/gpu_round.sh: separate FETCH_SIZE / WRITE_SIZE runs, FETCH_SIZE doubled as the gfx950 guide
+            # prescribes; tools/pmc_traffic.py).  The counters cannot be collected from inside this process.
+            traffic = None
+            traffic_file = None
             try:
-                import glob
-                cand = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_exchange_pmc_traffic_%s.json" % args.workload)))
-                if cand:
-                    ktraffic_file = cand[-1]
-                    with open(ktraffic_file) as fh:
+                if world == 1:
+                    import glob
+                    pat = "r[0-9][0-9]_pmc_traffic.json" if args.workload == "n2_pbe_nbf4230" else "r[0-9][0-9]_exchange_pmc_traffic_%s.json" % args.workload
+                    traffic_file = sorted(glob.glob(os.path.join(ROOT, "profiles", pat)))[-1]
+                    with open(traffic_file) as fh:
                         tj = json.load(fh)
                     meta = tj.pop("_meta", {})
-                    if meta.get("kernel_sources_sha256", kernel_sources_sha()) == kernel_sources_sha():
-                        for kname, rec in tj.items():  # the element GEMM is the <128, 128, false> (or <128, 64, false>) instance; <..., true> are the cross products
-                            if "k_dgemm_tasklist_wl" in kname and "false>" in kname and rec.get("traffic_bytes_per_launch") is not None:
-                                ktraffic = max(ktraffic or 0.0, rec["traffic_bytes_per_launch"])
+                    if meta.get("kernel_sources_sha256", kernel_sources_sha()) == kernel_sources_sha():  # stale figures are dropped
+                        if trdp_shapes:
+                            # all launches of one eigensolve (one per phase, each its own template instance
+                            # "void hfg::k_trdp<R, U, false>"), averaged per launch like `achieved`
+                            tot, cnt = 0.0, 0.0
+                            for nm, rec_s in trdp_shapes.items():
+                                key = "void hfg::" + nm[:-1] + ", false>"
+                                if key in tj and tj[key].get("traffic_bytes_per_launch") is not None:
+                                    tot += tj[key]["traffic_bytes_per_launch"] * rec_s["launches_per_step"]
+                                    cnt += rec_s["launches_per_step"]
+                            if cnt == sum(r["launches_per_step"] for r in trdp_shapes.values()) and cnt > 0:
+                                traffic = tot / cnt
+                        else:
+                            for kname, rec in tj.items():  # "hfg::k_trdf<1024>" or "hfg::k_trdb_gemv"
+                                if ("hfg::" + trd_kernel) in kname:
+                                    traffic = rec.get("traffic_bytes_per_launch")
             except Exception:
-                ktraffic = None
-            out["roofline_tridiagonalisation"] = out["roofline"]
-            out["roofline"] = {"bound": "mfma", "achieved": tf, "peak": 78.6, "unit": "TFLOP/s", "frac": tf / 78.6,
-                               "traffic": ktraffic,
-                               "traffic_source": ("profiles/%s (committed rocprofv3 --pmc passes, tools/exchange_pmc.sh; not measured "
-                                                  "in this run)" % os.path.basename(ktraffic_file)) if ktraffic is not None else None,
-                               "kernel": "hfg::k_dgemm_tasklist_wl (in-element GEMM of the exchange build)",
-                               "useful_gflop_per_launch": g_gflop / g_n if g_n else 0.0, "avg_launch_us": g_ms / g_n * 1e3 if g_n else 0.0,
-                               "launches_per_step": g_n / float(args.steps),
-                               "note": "FP64 MFMA (v_mfma_f64_16x16x4_f64); peak 78.6 TFLOP/s is AMD's data-sheet figure, "
-                                       "reproduced at 77 TFLOP/s by tests/gpu_probe/fp64_rate.hip"}
-        if not args.no_cpu_baseline and world == 1:
-            P = step.numpy(step.P, (N, N))
-            F = step.numpy(step.F, (N, N))
-            try:
-                out["cpu_baseline"] = cpu_baseline(w, bval, lval, mval, ldft, mdft, P, F, Sinvh, blocks)
-            except Exception as e:  # the checker library is test infrastructure; report rather than die
-                out["cpu_baseline"] = {"value": None, "unit": "ms", "cores": 1, "kind": "port", "sample": "failed: %s" % e}
+                traffic = None
+            out.update({
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                             "frac": achieved / 8000.0, "traffic": traffic,
+                             "traffic_source": ("profiles/%s (committed rocprofv3 --pmc passes of this command, not "
+                                                "measured in this run)" % os.path.basename(traffic_file)) if traffic is not None else None,
+                             "kernel": "hfg::" + trd_kernel, "algorithmic_bytes_per_launch": alg_bytes,
+                             "avg_launch_us": avg_ms * 1e3, "launches_per_step": launches_per_step,
+                             "launches_by_tile_shape": trdp_shapes,
+                             "note": ("persistent cooperative launches, one per phase of an eigensolve (a phase ends when the "
+                                      "trailing matrices fit the next narrower register tile), the trailing matrices resident in "
+                                      "the register file: the algorithmic bytes (one triangle of the trailing matrix per Householder "
+                                      "column, SURVEY 8d) never cross HBM; achieved = algorithmic bytes of an eigensolve / time of its "
+                                      "launches; bound by one exchange between workgroups per column (DESIGN.md 3.4)")
+                             if trd_kernel == "k_trdp" else
+                             "latency-bound: one dependent launch per Householder column (see DESIGN.md 3.4)"},
+                "stages_ms": {k: round(v["ms_per_step"], 4) for k, v in fams.items()},
+                # the other stages against their own bounds (stage time of this run, algorithmic work)
+                "stage_rooflines": stage_rooflines(basis, w, my_sizes, fams),
+                # size-independent self-check of the timed path: must not depend on the number of ranks
+                "check": check,
+            })
+            if kfrac != 0.0 and fams["exl_element_gemm"]["calls"] > 0:
+                # exact-exchange workloads: the dominant kernel of the exchange build is the in-element task-list GEMM
+                # (k_dgemm_tasklist_wl: C[p^2 x pairs] = ktei[p^2 x 4 p^2] RB[4 p^2 x pairs] per table slot and element).
+                # achieved = USEFUL flops (no tile padding) / HIP-event time of its launches in the timed region.
+                g_ms = fams["exl_element_gemm"]["ms_per_step"] * args.steps
+                g_n = fams["exl_element_gemm"]["calls"]
+                g_gflop = fams["exl_element_gemm_gflop"]["ms_per_step"] * args.steps  # accumulated GFLOP (see exchange_lr.hip)
+                tf = g_gflop / g_ms if g_ms > 0 else 0.0  # GFLOP / ms = TFLOP/s
+                ktraffic, ktraffic_file = None, None
+                try:
+                    import glob
+                    cand = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_exchange_pmc_traffic_%s.json" % args.workload)))
+                    if cand:
+                        ktraffic_file = cand[-1]
+                        with open(ktraffic_file) as fh:
+                            tj = json.load(fh)
+                        meta = tj.pop("_meta", {})
+                        if meta.get("kernel_sources_sha256", kernel_sources_sha()) == kernel_sources_sha():
+                            for kname, rec in tj.items():  # the element GEMM is the <128, 128, false> (or <128, 64, false>) instance; <..., true> are the cross products
+                                if "k_dgemm_tasklist_wl" in kname and "false>" in kname and rec.get("traffic_bytes_per_launch") is not None:
+                                    ktraffic = max(ktraffic or 0.0, rec["traffic_bytes_per_launch"])
+                except Exception:
+                    ktraffic = None
+                out["roofline_tridiagonalisation"] = out["roofline"]
+                out["roofline"] = {"bound": "mfma", "achieved": tf, "peak": 78.6, "unit": "TFLOP/s", "frac": tf / 78.6,
+                                   "traffic": ktraffic,
+                                   "traffic_source": ("profiles/%s (committed rocprofv3 --pmc passes, tools/exchange_pmc.sh; not measured "
+                                                      "in this run)" % os.path.basename(ktraffic_file)) if ktraffic is not None else None,
+                                   "kernel": "hfg::k_dgemm_tasklist_wl (in-element GEMM of the exchange build)",
+                                   "useful_gflop_per_launch": g_gflop / g_n if g_n else 0.0, "avg_launch_us": g_ms / g_n * 1e3 if g_n else 0.0,
+                                   "launches_per_step": g_n / float(args.steps),
+                                   "note": "FP64 MFMA (v_mfma_f64_16x16x4_f64); peak 78.6 TFLOP/s is AMD's data-sheet figure, "
+                                           "reproduced at 77 TFLOP/s by tests/gpu_probe/fp64_rate.hip"}
+            if not args.no_cpu_baseline and world == 1:
+                P = step.numpy(step.P, (N, N))
+                F = step.numpy(step.F, (N, N))
+                try:
+                    out["cpu_baseline"] = cpu_baseline(w, bval, lval, mval, ldft, mdft, P, F, Sinvh, blocks)
+                except Exception as e:  # the checker library is test infrastructure; report rather than die
+                    out["cpu_baseline"] = {"value": None, "unit": "ms", "cores": 1, "kind": "port", "sample": "failed: %s" % e}
         print(json.dumps(out))
     if world > 1 or parallel.forced():
         import torch.distributed as dist

@@ -65,35 +65,35 @@ def test_legendre_PQ_vs_reference_fortran(hf):
                 assert abs(Q[L, M] - Qr[L, M]) <= qtol * abs(Qr[L, M]), ("Q", c["mu"], L, M, Q[L, M], Qr[L, M])
 
 
+LEGENDRE_SCF_CASE = dict(Z1=1, Z2=1, Rbond=1.4, lmmax=[3], nelem=2, nnodes=6, method="HF", convthr=1e-9)
+
+
 def test_reference_legendre_library_does_not_move_energies():
-    """Runs the oracle SCF twice: with the product's P/Q implementation and with the reference's own Fortran
-    library (oracle/_ref, only present in the build container) plugged into compute_tei exactly as
-    LegendreTable::compute does (legendretable.cpp:60-97).  The converged energies must agree far below the
-    1e-8 Eh parity bar, i.e. the reference library's limited Q accuracy is immaterial."""
-    ref_path = os.path.join(ROOT, "oracle", "_ref", "libref_legendre.so")
-    if not os.path.exists(ref_path):
-        pytest.skip("oracle/_ref not built (reference sources absent on this machine)")
-    import ctypes
+    """Runs the oracle SCF twice: with the product's P/Q implementation and with the values of the reference's own
+    Fortran library plugged into compute_tei exactly as LegendreTable::compute does (legendretable.cpp:60-97).  The
+    library's values at every xi this SCF asks for are the fixture legendre_reference_scf.npz
+    (tests/golden/make_legendre_scf_golden.py).  The converged energies must agree far below the 1e-8 Eh parity bar,
+    i.e. the reference library's limited Q accuracy is immaterial."""
     import oracle_lib as orc
-    ref = ctypes.CDLL(ref_path)
+    gold = np.load(os.path.join(GOLD, "legendre_reference_scf.npz"))
+    gxi, gP, gQ = gold["xi"], gold["P"], gold["Q"]
     dp = ctypes.POINTER(ctypes.c_double)
-    for f in (ref.calc_Plm_arr, ref.calc_Qlm_arr):
-        f.argtypes = [dp, ctypes.c_int, ctypes.c_int, ctypes.c_double]
     CB = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, dp, dp)
     tiny = np.finfo(float).tiny
-    cwd = os.getcwd()
+    misses = []
 
     def provider(Lmax, Mmax, lpad, xi, P, Q):
-        Lp = Lmax + lpad
         if xi == 1.0:
             for i in range((Lmax + 1) * (Mmax + 1)):
                 P[i] = 0.0
                 Q[i] = 0.0
             return
-        a = np.zeros((Lp + 1, Lp + 1))
-        b = np.zeros((Lp + 1, Lp + 1))
-        ref.calc_Plm_arr(a.ctypes.data_as(dp), Lp, Lp, xi)
-        ref.calc_Qlm_arr(b.ctypes.data_as(dp), Lp, Lp, xi)
+        assert (Lmax, Mmax, lpad) == (int(gold["Lmax"]), int(gold["Mmax"]), int(gold["lpad"]))
+        k = int(np.clip(np.searchsorted(gxi, xi), 1, len(gxi) - 1))
+        k = k if abs(gxi[k] - xi) < abs(gxi[k - 1] - xi) else k - 1
+        if abs(gxi[k] - xi) > 1e-14 * xi:
+            misses.append(xi)
+        a, b = gP[k], gQ[k]
         for M in range(Mmax + 1):
             for L in range(Lmax + 1):
                 pv, qv = a[M, L], b[M, L]
@@ -104,15 +104,13 @@ def test_reference_legendre_library_does_not_move_energies():
     L = orc.lib()
     L.orc_set_legendre_provider.argtypes = [CB]
     L.orc_set_legendre_provider.restype = None
-    kw = dict(Z1=1, Z2=1, Rbond=1.4, lmmax=[3], nelem=2, nnodes=6, method="HF", convthr=1e-9)
-    own = orc.scf_diatomic(**kw)
+    own = orc.scf_diatomic(**LEGENDRE_SCF_CASE)
     try:
-        os.chdir("/tmp")  # the Fortran library writes fort.9 into the cwd
         L.orc_set_legendre_provider(cb)
-        viaref = orc.scf_diatomic(**kw)
+        viaref = orc.scf_diatomic(**LEGENDRE_SCF_CASE)
     finally:
         L.orc_set_legendre_provider(ctypes.cast(None, CB))
-        os.chdir(cwd)
+    assert not misses, "xi not in the fixture: %s" % misses[:5]
     assert own["converged"] and viaref["converged"]
     assert abs(own["Etot"] - viaref["Etot"]) < 1e-10, (own["Etot"], viaref["Etot"])
 

@@ -15,7 +15,7 @@ rocprofv3 -L > $OUT/counters_available.txt 2>&1 || echo "(rocprofv3 -L: $?)"
 P1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_F64"
 P2="SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_INSTS_LDS SQ_INSTS_VALU"
 for w in gemm bench; do
-  if [ $w = gemm ]; then CMD="python3 $REPO/tools/gemm_bench.py"; else CMD="python3 $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline"; fi
+  if [ $w = gemm ]; then CMD="python3 $REPO/tools/gemm_bench.py"; else CMD="python3 $REPO/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline"; fi
   rocprofv3 --pmc $P1 --output-format csv -d $OUT/p1_$w -o p1 -- $CMD > $OUT/p1_$w.log 2>&1 || echo "(rocprofv3 pass 1 $w: exit $?)"
   rocprofv3 --pmc $P2 --output-format csv -d $OUT/p2_$w -o p2 -- $CMD > $OUT/p2_$w.log 2>&1 || echo "(rocprofv3 pass 2 $w: exit $?)"
   cd $REPO
