@@ -405,6 +405,20 @@ class AtomicTwoDBasis(TwoDBasis):
         _check(f(ctxh, self.h, which, int(L), idx, _p(out), ctypes.byref(r), ctypes.byref(c)))
         return out
 
+    RADIAL_TABLES = {"bf": 0, "df": 1, "lf": 2, "r": 3}
+
+    def radial_table(self, name, iel):
+        """RadialBasis::get_bf / get_df / get_lf (B/r and its first and second radial derivatives) at the quadrature points
+        of element iel, nquad x Nprim(iel); "r": the radial coordinates of those points"""
+        f = lib().hfg_basis_radial_table
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_int64),
+                      ctypes.POINTER(ctypes.c_int64)]
+        r, c = ctypes.c_int64(), ctypes.c_int64()
+        _check(f(self.h, self.RADIAL_TABLES[name], int(iel), None, ctypes.byref(r), ctypes.byref(c)))
+        out = np.zeros((r.value, c.value), order="F")
+        _check(f(self.h, self.RADIAL_TABLES[name], int(iel), _p(out), ctypes.byref(r), ctypes.byref(c)))
+        return out[:, 0] if name == "r" else out
+
     def compute_yukawa(self, lam):
         """TwoDBasis::compute_yukawa (src/atomic/TwoDBasis.cpp:741): tables of exp(-lambda r12)/r12 (host)"""
         _check(lib().hfg_compute_rs_tei(self.h, 1, float(lam)))
@@ -634,6 +648,46 @@ def lobatto_nodes(n):
     x = np.zeros(n)
     lib().hfg_lobatto_nodes(int(n), _p(x))
     return x
+
+
+def xc_eval(func_id, rho, sigma=None, lapl=None, tau=None, nspin=1, thr=0.0):
+    """one functional at points, libxc's xc_mgga_exc_vxc layout (hfg_xc_eval; host only, no device): nspin 1 takes arrays of
+    shape (np,), nspin 2 rho, lapl, tau of shape (np, 2) and sigma of shape (np, 3) (aa, ab, bb).  Returns a dict with exc
+    (per particle) and vrho, vsigma, vlapl, vtau in the shapes of the inputs."""
+    nspin = int(nspin)
+    rho = np.ascontiguousarray(rho, dtype=np.float64)
+    npt = rho.shape[0]
+    shp = {"rho": (npt,) if nspin == 1 else (npt, 2), "sigma": (npt,) if nspin == 1 else (npt, 3)}
+    shp["lapl"] = shp["tau"] = shp["rho"]
+    if rho.shape != shp["rho"]:
+        raise ValueError("rho must have shape %s" % (shp["rho"],))
+    ins = {}
+    for k, v in (("sigma", sigma), ("lapl", lapl), ("tau", tau)):
+        ins[k] = np.zeros(shp[k]) if v is None else np.ascontiguousarray(np.broadcast_to(v, shp[k]), dtype=np.float64)
+    out = {"exc": np.zeros(npt)}
+    for k, src in (("vrho", "rho"), ("vsigma", "sigma"), ("vlapl", "lapl"), ("vtau", "tau")):
+        out[k] = np.zeros(shp[src])
+    f = lib().hfg_xc_eval
+    f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [c_double_p] * 9 + [ctypes.c_double]
+    _check(f(int(func_id), nspin, npt, _p(rho), _p(ins["sigma"]), _p(ins["lapl"]), _p(ins["tau"]), _p(out["exc"]),
+             _p(out["vrho"]), _p(out["vsigma"]), _p(out["vlapl"]), _p(out["vtau"]), float(thr)))
+    return out
+
+
+def xc_func_ids(method):
+    """--method string -> (x_func, c_func) libxc ids (the drivers' parse_xc_func)"""
+    x, c = ctypes.c_int(), ctypes.c_int()
+    f = lib().hfg_xc_func_ids
+    f.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    _check(f(method.encode(), ctypes.byref(x), ctypes.byref(c)))
+    return x.value, c.value
+
+
+def xc_func_name(func_id):
+    f = lib().hfg_xc_func_name
+    f.restype = ctypes.c_char_p
+    f.argtypes = [ctypes.c_int]
+    return f(int(func_id)).decode()
 
 
 def scf_set_iguess(iguess):

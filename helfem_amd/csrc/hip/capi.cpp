@@ -3,6 +3,7 @@
 #include "common.h"
 #include "../host/checkpoint.h"
 #include "../host/diis.h"
+#include "../host/dftfuncs.h"
 #include "tables.h"
 #include <cstring>
 #include <mutex>
@@ -23,6 +24,8 @@ void xc_fock_pol_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, con
 void model_potential_dev(hfg_ctx *ctx, hfg_basis *basis, int kind1, int Z1, double d1, double H1, int kind2, int Z2,
                          double d2, double H2, double *dH);
 void fock_release(hfg_dev_tables *t);
+void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double *sigma, const double *lapl, const double *tau,
+                  double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau, double thr);
 size_t fock_compact_size(hfg_basis *basis);
 void fock_compact_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dFc,
                       double *dScal, double thr);
@@ -826,6 +829,42 @@ int hfg_model_potential(hfg_ctx *ctx, hfg_basis *b, const hfg_model_pot *p1, con
   }
   HFG_CATCH
 }
+int hfg_xc_eval(int func_id, int nspin, int64_t np, const double *rho, const double *sigma, const double *lapl, const double *tau,
+                double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau, double thr) {
+  HFG_TRY
+  if (np < 0) throw std::logic_error("hfg_xc_eval: negative point count\n");
+  xc_eval_host(func_id, nspin, (size_t)np, rho, sigma, lapl, tau, exc, vrho, vsigma, vlapl, vtau, thr);
+  HFG_CATCH
+}
+
+int hfg_xc_func_ids(const char *method, int *x_func, int *c_func) {
+  HFG_TRY
+  if (!method || !x_func || !c_func) throw std::logic_error("hfg_xc_func_ids: null argument\n");
+  helfem::parse_xc_func(*x_func, *c_func, method);
+  HFG_CATCH
+}
+
+const char *hfg_xc_func_name(int func_id) { return helfem::xc_func_name(func_id); }
+
+int hfg_basis_radial_table(const hfg_basis *b, int which, int iel, double *out, int64_t *rows, int64_t *cols) {
+  HFG_TRY
+  if (!b || !rows || !cols) throw std::logic_error("hfg_basis_radial_table: null argument\n");
+  if (!b->kind) throw std::logic_error("hfg_basis_radial_table: atomic bases only\n");
+  const helfem::atomic::TwoDBasis &B = b->ab;
+  if (which < 0 || which > 3 || iel < 0 || (size_t)iel >= B.Nel()) throw std::logic_error("hfg_basis_radial_table: index out of range\n");
+  helfem::Mat m;
+  if (which == 3) {
+    const helfem::Vec r = B.get_r(iel);
+    m = helfem::Mat(r.size(), 1);
+    for (size_t i = 0; i < r.size(); i++) m(i, 0) = r[i];
+  } else
+    m = which == 0 ? B.get_bf(iel) : which == 1 ? B.get_df(iel) : B.get_lf(iel);
+  *rows = (int64_t)m.n_rows;
+  *cols = (int64_t)m.n_cols;
+  if (out) std::copy(m.d.begin(), m.d.end(), out);
+  HFG_CATCH
+}
+
 int hfg_xc_fock(hfg_ctx *ctx, hfg_basis *b, int x_func, int c_func, const double *P, double *H, double *Exc,
                 double *Nel, double *Ekin, double thr) {
   HFG_TRY

@@ -307,26 +307,29 @@ __global__ void k_coulomb_bra(const double *__restrict__ Jaux, int A, int E, int
 // X1 radial contraction of the density: D0[Q][x][y] = sum_ij B_i(q) Pc[x][y][e][j][i] B_j(q),
 //    D1[Q][x][y] = sum_ij B'_i(q) Pc[..][j][i] B_j(q)            (replaces Pv = P conj(bf), dftgrid.cpp:62)
 //    (meta-GGA: D2[Q][x][y] = sum_ij B'_i Pc B'_j for the kinetic energy density)
+//    (Laplacian: D3[Q][x][y] = sum_ij B_i Pc L_j with the radial table L = g'' + 2 g'/r of the y shell's functions)
 __global__ __launch_bounds__(256) void k_xc_density_radial(const double *__restrict__ Pc, const double *__restrict__ B,
-                                                           const double *__restrict__ dB, int A, int E, int p, int nq,
-                                                           int do_grad, int do_tau, int rank, int nranks,
-                                                           double *__restrict__ D0, double *__restrict__ D1,
-                                                           double *__restrict__ D2) {
+                                                           const double *__restrict__ dB, const double *__restrict__ Lr, int A,
+                                                           int E, int p, int nq, int do_grad, int do_tau, int do_lapl, int rank,
+                                                           int nranks, double *__restrict__ D0, double *__restrict__ D1,
+                                                           double *__restrict__ D2, double *__restrict__ D3) {
   // One workgroup per (shell pair, element).  The p x p block of P and the element's B, B' tables sit in LDS (the
   // tables transposed to [i][q]: consecutive q <-> consecutive banks); thread (q, jc) forms the rows j = jc, jc+NJ, ...
   // of T = P b(q), contracts them with b_j, b'_j, and the NJ partial results of a point are summed through LDS in a
   // fixed order.
-  extern __shared__ double sh[];  // P[pp], Bt[p][nq], dBt[p][nq], part[3][NJ][nq]
+  extern __shared__ double sh[];  // P[pp], Bt[p][nq], dBt[p][nq], part[3 (4 with do_lapl)][NJ][nq], Lt[p][nq] (do_lapl)
   const int xy = blockIdx.x, e = blockIdx.y;
   const int pp = p * p;
   double *sP = sh, *sB = sh + pp, *sdB = sB + p * nq;
   const int NJ = blockDim.x / nq > 0 ? min((int)(blockDim.x / nq), p) : 1;
   double *part = sdB + p * nq;
+  double *sL = part + (do_lapl ? 4 : 3) * NJ * nq;
   for (int t = threadIdx.x; t < pp; t += blockDim.x) sP[t] = Pc[((size_t)xy * E + e) * pp + t];
   for (int t = threadIdx.x; t < p * nq; t += blockDim.x) {
     int q = t / p, i = t % p;
     sB[i * nq + q] = B[((size_t)e * nq + q) * p + i];
     sdB[i * nq + q] = dB[((size_t)e * nq + q) * p + i];
+    if (do_lapl) sL[i * nq + q] = Lr[((size_t)e * nq + q) * p + i];
   }
   __syncthreads();
   const size_t AA = (size_t)A * A;
@@ -334,7 +337,7 @@ __global__ __launch_bounds__(256) void k_xc_density_radial(const double *__restr
   for (int q0 = 0; q0 < nq; q0 += blockDim.x / NJ) {
     const int ql = threadIdx.x % (blockDim.x / NJ), jc = threadIdx.x / (blockDim.x / NJ);
     const int q = q0 + ql;
-    double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+    double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
     if (q < nq && jc < NJ)
       for (int j = jc; j < p; j += NJ) {
         double s0 = 0.0, s1 = 0.0;
@@ -346,24 +349,28 @@ __global__ __launch_bounds__(256) void k_xc_density_radial(const double *__restr
         d0 += s0 * sB[j * nq + q];
         d1 += s1 * sB[j * nq + q];
         d2 += s1 * sdB[j * nq + q];
+        if (do_lapl) d3 += s0 * sL[j * nq + q];
       }
     if (q < nq && jc < NJ) {
       part[(0 * NJ + jc) * nq + q] = d0;
       part[(1 * NJ + jc) * nq + q] = d1;
       part[(2 * NJ + jc) * nq + q] = d2;
+      if (do_lapl) part[(3 * NJ + jc) * nq + q] = d3;
     }
     __syncthreads();
     if (jc == 0 && q < nq && (e * nq + q) % nranks == rank) {  // radial quadrature points are the multi-GPU shards of XC
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
       for (int k = 0; k < NJ; k++) {
         a0 += part[(0 * NJ + k) * nq + q];
         a1 += part[(1 * NJ + k) * nq + q];
         a2 += part[(2 * NJ + k) * nq + q];
+        if (do_lapl) a3 += part[(3 * NJ + k) * nq + q];
       }
       const size_t Q = (size_t)e * nq + q;
       D0[Q * AA + xy] = a0;
       if (do_grad) D1[Q * AA + xy] = a1;
       if (do_tau) D2[Q * AA + xy] = a2;
+      if (do_lapl) D3[Q * AA + xy] = a3;
     }
     __syncthreads();
   }
@@ -372,32 +379,36 @@ __global__ __launch_bounds__(256) void k_xc_density_radial(const double *__restr
 // X2 theta contraction per (m-group pair): V[k][Q][ga][gb][i],
 //    k=0: sum Theta_a D0_ab Theta_b ; k=1: sum dTheta_a D0_ab Theta_b ; k=2: sum Theta_a D1_ab Theta_b
 //    meta-GGA: k=3: sum Theta_a D2_ab Theta_b ; k=4: sum dTheta_a D0_ab dTheta_b
+//    Laplacian: k=5: sum Theta_a (D3_ab - l_b(l_b+1)/r^2 D0_ab) Theta_b   (eval_lf, atomic/TwoDBasis.cpp:1423-1445)
 __global__ void k_xc_density_theta(const double *__restrict__ D0, const double *__restrict__ D1,
-                                   const double *__restrict__ D2, const double *__restrict__ Th,
-                                   const double *__restrict__ dTh, int A, int nth, int G,
+                                   const double *__restrict__ D2, const double *__restrict__ D3, const double *__restrict__ Th,
+                                   const double *__restrict__ dTh, const int *__restrict__ shell_l,
+                                   const double *__restrict__ rad_sh, int A, int nth, int G,
                                    const int *__restrict__ grp_off, const int *__restrict__ grp_shell, int do_grad,
-                                   int do_tau, size_t NQ, int rank, int nranks, double *__restrict__ V) {
-  extern __shared__ double sh[];  // d0[na*nb], d1[na*nb], d2[na*nb]
+                                   int do_tau, int do_lapl, size_t NQ, int rank, int nranks, double *__restrict__ V) {
+  extern __shared__ double sh[];  // d0[na*nb], d1[na*nb], d2[na*nb], d3[na*nb] (do_lapl)
   size_t Q = blockIdx.x;
   if ((int)(Q % nranks) != rank) return;
   int ga = blockIdx.y / G, gb = blockIdx.y % G;
   int a0 = grp_off[ga], na = grp_off[ga + 1] - a0;
   int b0 = grp_off[gb], nb = grp_off[gb + 1] - b0;
-  double *d0 = sh, *d1 = sh + na * nb, *d2 = sh + 2 * na * nb;
+  double *d0 = sh, *d1 = sh + na * nb, *d2 = sh + 2 * na * nb, *d3 = sh + 3 * na * nb;
   size_t AA = (size_t)A * A;
+  const double ir2 = do_lapl ? 1.0 / (rad_sh[Q] * rad_sh[Q]) : 0.0;
   for (int t = threadIdx.x; t < na * nb; t += blockDim.x) {
     int ia = t / nb, ib = t % nb;
     int a = grp_shell[a0 + ia], b = grp_shell[b0 + ib];
     d0[t] = D0[Q * AA + (size_t)a * A + b];
     d1[t] = do_grad ? D1[Q * AA + (size_t)a * A + b] : 0.0;
     d2[t] = do_tau ? D2[Q * AA + (size_t)a * A + b] : 0.0;
+    if (do_lapl) d3[t] = D3[Q * AA + (size_t)a * A + b] - (double)(shell_l[b] * (shell_l[b] + 1)) * ir2 * d0[t];
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nth; i += blockDim.x) {
-    double r = 0.0, s = 0.0, u = 0.0, k3 = 0.0, k4 = 0.0;
+    double r = 0.0, s = 0.0, u = 0.0, k3 = 0.0, k4 = 0.0, k5 = 0.0;
     for (int ia = 0; ia < na; ia++) {
       int a = grp_shell[a0 + ia];
-      double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+      double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s5 = 0.0;
       for (int ib = 0; ib < nb; ib++) {
         double tb = Th[(size_t)grp_shell[b0 + ib] * nth + i];
         s0 += d0[ia * nb + ib] * tb;
@@ -406,6 +417,7 @@ __global__ void k_xc_density_theta(const double *__restrict__ D0, const double *
           s2 += d2[ia * nb + ib] * tb;
           s3 += d0[ia * nb + ib] * dTh[(size_t)grp_shell[b0 + ib] * nth + i];
         }
+        if (do_lapl) s5 += d3[ia * nb + ib] * tb;
       }
       double ta = Th[(size_t)a * nth + i];
       r += ta * s0;
@@ -417,6 +429,7 @@ __global__ void k_xc_density_theta(const double *__restrict__ D0, const double *
         k3 += ta * s2;
         k4 += dTh[(size_t)a * nth + i] * s3;
       }
+      if (do_lapl) k5 += ta * s5;
     }
     size_t o = ((Q * G + ga) * G + gb) * nth + i;
     size_t stride = NQ * G * G * nth;
@@ -429,6 +442,7 @@ __global__ void k_xc_density_theta(const double *__restrict__ D0, const double *
       V[3 * stride + o] = k3;
       V[4 * stride + o] = k4;
     }
+    if (do_lapl) V[5 * stride + o] = k5;
   }
 }
 
@@ -438,14 +452,17 @@ __global__ void k_xc_density_theta(const double *__restrict__ D0, const double *
 //       Fo[1][..]           = sum_j gr_nu cos(D phi_j)
 //       Fo[2][..]           = sum_j gr_mu cos(D phi_j)            D = m_ga - m_gb
 //    (dftgrid.cpp:69-86, 412-416, 471-477, 510-531, 693-707)
+//    Laplacian (do_lapl, atomic dftgrid.cpp:105-120, 557-571): lapl = 2 (kin + lap) with kin = 2 tau and lap = sum_j V5 cos,
+//    the tau-type potential becomes w (vtau/2 + 2 vlapl), and Fo[5][..] = sum_j w vlapl cos(D phi_j) feeds the
+//    increment_mgga_lapl term
 __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict__ rad_w,
                           const double *__restrict__ rad_sh, const double *__restrict__ th_s,
                           const double *__restrict__ th_w, const int *__restrict__ grp_m,
                           const double *__restrict__ cosd, const double *__restrict__ sind, int Dmax, int G, int nth,
-                          int nphi, double Rh, int geom, int x_func, int c_func, int do_grad, int do_tau, double thr,
-                          size_t NQ, int rank, int nranks, double *__restrict__ Fo,
+                          int nphi, double Rh, int geom, int x_func, int c_func, int do_grad, int do_tau, int do_lapl,
+                          double thr, size_t NQ, int rank, int nranks, double *__restrict__ Fo,
                           double *__restrict__ partial /* [3][NQ] */) {
-  extern __shared__ double sh[];  // pot[5][nth*nphi], red[3*nwave]
+  extern __shared__ double sh[];  // pot[5 (6 with do_lapl)][nth*nphi], red[3*nwave]
   size_t Q = blockIdx.x;
   if ((int)(Q % nranks) != rank) {
     if (threadIdx.x == 0) {
@@ -456,8 +473,8 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
     return;
   }
   int ng = nth * nphi;
-  double *p0 = sh, *p1 = sh + ng, *p2 = sh + 2 * ng, *p3 = sh + 3 * ng, *p4 = sh + 4 * ng;
-  double *red = sh + 5 * ng;
+  double *p0 = sh, *p1 = sh + ng, *p2 = sh + 2 * ng, *p3 = sh + 3 * ng, *p4 = sh + 4 * ng, *p5 = sh + 5 * ng;
+  double *red = sh + (do_lapl ? 6 : 5) * ng;
   double shm = rad_sh[Q], wr = rad_w[Q];
   double dphi = 2.0 * HFG_PI / nphi;
   size_t stride = NQ * G * G * nth;
@@ -479,7 +496,7 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
       hphi = shm * sth;
       w = th_w[i] * dphi * wr * shm * shm;
     }
-    double rho = 0.0, gmu = 0.0, gnu = 0.0, gphi = 0.0, tau = 0.0;
+    double rho = 0.0, gmu = 0.0, gnu = 0.0, gphi = 0.0, tau = 0.0, lap = 0.0;
     for (int ga = 0; ga < G; ga++)
       for (int gb = 0; gb < G; gb++) {
         int D = grp_m[ga] - grp_m[gb];
@@ -487,6 +504,7 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
         size_t o = ((Q * G + ga) * G + gb) * nth + i;
         double vr = V[o];
         rho += cd * vr;
+        if (do_lapl) lap += cd * V[5 * stride + o];
         if (do_tau)  // tau = 1/2 sum_c Re[(P conj d_c bf) . d_c bf] / h_c^2   (dftgrid.cpp:90-112)
           tau += 0.5 * cd * (V[3 * stride + o] / (hmu * hmu) + V[4 * stride + o] / (hnu * hnu) +
                              (double)(grp_m[ga] * grp_m[gb]) * vr / (hphi * hphi));
@@ -504,22 +522,27 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
       gphi *= 2.0 / hphi;
       sigma = gmu * gmu + gnu * gnu + gphi * gphi;
     }
-    double exc = 0.0, vrho = 0.0, vsig = 0.0, vtau = 0.0;
+    double exc = 0.0, vrho = 0.0, vsig = 0.0, vtau = 0.0, vlap = 0.0;
     if (rho >= thr && rho > 0.0) {
       const bool live = 0.5 * rho >= thr;  // the spin channels of the exchange sum carry rho/2 each
+      const double lapl = 2.0 * (2.0 * tau + lap);
       if (x_func > 0) {
-        if (xc::is_mgga(x_func)) xc::eval_add_mgga(x_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
+        if (xc::is_mgga_lapl(x_func)) xc::eval_add_mgga_lapl(x_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
+        else if (xc::is_mgga(x_func)) xc::eval_add_mgga(x_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
         else xc::eval_add(x_func, rho, sigma, live, exc, vrho, vsig);
       }
       if (c_func > 0) {
-        if (xc::is_mgga(c_func)) xc::eval_add_mgga(c_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
+        if (xc::is_mgga_lapl(c_func)) xc::eval_add_mgga_lapl(c_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
+        else if (xc::is_mgga(c_func)) xc::eval_add_mgga(c_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
         else xc::eval_add(c_func, rho, sigma, live, exc, vrho, vsig);
       }
+      if (!isfinite(vlap)) vlap = 0.0;  // check_xc, dftgrid.cpp:336-339
     }
     nel += w * rho;
     exc_sum += w * exc * rho;
     kin_sum += w * tau;
-    if (do_tau) p4[pt] = 0.5 * w * vtau;  // vt of dftgrid.cpp:534-535
+    if (do_tau) p4[pt] = do_lapl ? w * (0.5 * vtau + 2.0 * vlap) : 0.5 * w * vtau;  // vt / vtl of dftgrid.cpp:534-535, 557-562
+    if (do_lapl) p5[pt] = w * vlap;
     p0[pt] = w * vrho;
     if (do_grad) {
       double f = 2.0 * w * vsig;
@@ -561,7 +584,7 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
     int D = grp_m[ga] - grp_m[gb];
     const double *cd = cosd + (size_t)(D + Dmax) * nphi;
     const double *sd = sind + (size_t)(D + Dmax) * nphi;
-    double fa = 0.0, fs = 0.0, fb = 0.0, ft = 0.0;
+    double fa = 0.0, fs = 0.0, fb = 0.0, ft = 0.0, fl = 0.0;
     double mga = grp_m[ga];
     for (int j = 0; j < nphi; j++) {
       int pt = i * nphi + j;
@@ -572,8 +595,10 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
         fb += p1[pt] * cd[j];
       }
       if (do_tau) ft += p4[pt] * cd[j];
+      if (do_lapl) fl += p5[pt] * cd[j];
     }
     size_t o = ((Q * G + ga) * G + gb) * nth + i;
+    if (do_lapl) Fo[5 * stride + o] = fl;
     if (do_tau) {
       // the three tau terms of eval_Fxc (dftgrid.cpp:533-540) share the phi sum; the scale factors depend on
       // theta only.  Halves as for the LDA term: the radial stage adds the (x,y) and (y,x) blocks.
@@ -604,13 +629,14 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
                               const double *__restrict__ rad_sh, const double *__restrict__ th_s,
                               const double *__restrict__ th_w, const int *__restrict__ grp_m,
                               const double *__restrict__ cosd, const double *__restrict__ sind, int Dmax, int G, int nth,
-                              int nphi, double Rh, int geom, int x_func, int c_func, int do_grad, int do_tau, double thr,
-                              size_t NQ, int rank, int nranks, double *__restrict__ Fo,
+                              int nphi, double Rh, int geom, int x_func, int c_func, int do_grad, int do_tau, int do_lapl,
+                              double thr, size_t NQ, int rank, int nranks, double *__restrict__ Fo,
                               double *__restrict__ partial /* [3][NQ] */, int rowc) {
   // meta-GGA (do_tau): V and Fo carry five planes per spin (the tau planes 3, 4 as in k_xc_grid), LDS one more potential
   // plane per spin.  The theta rows go through LDS rowc at a time (the phi transform is row by row): rowc = nth unless the
   // planes of the whole grid exceed a CU's LDS (lmax beyond ~26 with mmax = 2).
-  extern __shared__ double sh[];  // pot[npot][rowc*nphi] (npot = 8, or 10 with tau), red[3*nwave]
+  // Laplacian (do_lapl): a sixth plane per spin in V and Fo and in LDS (the vlapl potential), as in k_xc_grid.
+  extern __shared__ double sh[];  // pot[2*npot][rowc*nphi] (npot = 4, 5 with tau, 6 with lapl), red[3*nwave]
   size_t Q = blockIdx.x;
   if ((int)(Q % nranks) != rank) {
     if (threadIdx.x == 0) {
@@ -621,8 +647,8 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
     return;
   }
   const int ng = rowc * nphi;        // plane stride in LDS
-  const int npl = do_tau ? 5 : 3;    // planes per spin in V and Fo
-  const int npot = do_tau ? 5 : 4;   // potential planes per spin in LDS
+  const int npl = do_lapl ? 6 : (do_tau ? 5 : 3);   // planes per spin in V and Fo
+  const int npot = do_lapl ? 6 : (do_tau ? 5 : 4);  // potential planes per spin in LDS
   double *red = sh + 2 * npot * ng;
   double shm = rad_sh[Q], wr = rad_w[Q];
   double dphi = 2.0 * HFG_PI / nphi;
@@ -647,6 +673,7 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
       w = th_w[i] * dphi * wr * shm * shm;
     }
     double rho[2] = {0.0, 0.0}, gmu[2] = {0.0, 0.0}, gnu[2] = {0.0, 0.0}, gphi[2] = {0.0, 0.0}, tau[2] = {0.0, 0.0};
+    double lap[2] = {0.0, 0.0};
     for (int ga = 0; ga < G; ga++)
       for (int gb = 0; gb < G; gb++) {
         int D = grp_m[ga] - grp_m[gb];
@@ -657,6 +684,7 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
           const double *Vs = V + (size_t)sp * npl * stride;
           double vr = Vs[o];
           rho[sp] += cd * vr;
+          if (do_lapl) lap[sp] += cd * Vs[5 * stride + o];
           if (do_tau)  // dftgrid.cpp:159-200: tau of each spin density
             tau[sp] += 0.5 * cd * (Vs[3 * stride + o] / (hmu * hmu) + Vs[4 * stride + o] / (hnu * hnu) +
                                    (double)(grp_m[ga] * grp_m[gb]) * vr / (hphi * hphi));
@@ -678,23 +706,35 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
       sab = gmu[0] * gmu[1] + gnu[0] * gnu[1] + gphi[0] * gphi[1];
       sbb = gmu[1] * gmu[1] + gnu[1] * gnu[1] + gphi[1] * gphi[1];
     }
-    double exc = 0.0, va = 0.0, vb = 0.0, vsaa = 0.0, vsab = 0.0, vsbb = 0.0, vta = 0.0, vtb = 0.0;
+    double exc = 0.0, va = 0.0, vb = 0.0, vsaa = 0.0, vsab = 0.0, vsbb = 0.0, vta = 0.0, vtb = 0.0, vla = 0.0, vlb = 0.0;
     const double rt = rho[0] + rho[1];
     if (rt >= thr && rt > 0.0) {
       double ra = fmax(rho[0], thr), rb = fmax(rho[1], thr);
+      // dftgrid.cpp:206-229: lapl_s = 2 (kin_s + lap_s), kin_s = 2 tau_s
+      const double la = 2.0 * (2.0 * tau[0] + lap[0]), lb = 2.0 * (2.0 * tau[1] + lap[1]);
       for (int f = 0; f < 2; f++) {
         const int id = f ? c_func : x_func;
         if (id <= 0) continue;
-        if (xc::is_mgga(id)) xc::eval_add_mgga_pol(id, ra, rb, saa, sab, sbb, tau[0], tau[1], rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa, vsab, vsbb, vta, vtb);
+        if (xc::is_mgga_lapl(id))
+          xc::eval_add_mgga_lapl_pol(id, ra, rb, saa, sab, sbb, tau[0], tau[1], la, lb, rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa,
+                                     vsab, vsbb, vta, vtb, vla, vlb);
+        else if (xc::is_mgga(id)) xc::eval_add_mgga_pol(id, ra, rb, saa, sab, sbb, tau[0], tau[1], rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa, vsab, vsbb, vta, vtb);
         else xc::eval_add_pol(id, ra, rb, saa, sab, sbb, rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa, vsab, vsbb);
       }
+      if (!isfinite(vla)) vla = 0.0;  // check_xc, dftgrid.cpp:336-339
+      if (!isfinite(vlb)) vlb = 0.0;
     }
     nel += w * rt;
     exc_sum += w * exc * rt;
     kin_sum += w * (tau[0] + tau[1]);
     sh[0 * ng + pt] = w * va;
     sh[npot * ng + pt] = w * vb;
-    if (do_tau) {
+    if (do_lapl) {  // vtl_a, vtl_b of dftgrid.cpp:643-660
+      sh[4 * ng + pt] = w * (0.5 * vta + 2.0 * vla);
+      sh[(npot + 4) * ng + pt] = w * (0.5 * vtb + 2.0 * vlb);
+      sh[5 * ng + pt] = w * vla;
+      sh[(npot + 5) * ng + pt] = w * vlb;
+    } else if (do_tau) {
       sh[4 * ng + pt] = 0.5 * w * vta;
       sh[(npot + 4) * ng + pt] = 0.5 * w * vtb;
     }
@@ -720,7 +760,8 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
     const double *cd = cosd + (size_t)(D + Dmax) * nphi;
     const double *sd = sind + (size_t)(D + Dmax) * nphi;
     const double *p0 = sh + (size_t)(npot * sp) * ng, *p1 = p0 + ng, *p2 = p0 + 2 * ng, *p3 = p0 + 3 * ng, *p4 = p0 + 4 * ng;
-    double fa = 0.0, fs = 0.0, fb = 0.0, ft = 0.0;
+    const double *p5 = p0 + 5 * ng;
+    double fa = 0.0, fs = 0.0, fb = 0.0, ft = 0.0, fl = 0.0;
     double mga = grp_m[ga];
     for (int j = 0; j < nphi; j++) {
       int pt = il * nphi + j;
@@ -731,9 +772,11 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
         fb += p1[pt] * cd[j];
       }
       if (do_tau) ft += p4[pt] * cd[j];
+      if (do_lapl) fl += p5[pt] * cd[j];
     }
     size_t o = ((Q * G + ga) * G + gb) * nth + i;
     double *Fs = Fo + (size_t)sp * npl * stride;
+    if (do_lapl) Fs[5 * stride + o] = fl;
     if (do_tau) {  // the three tau terms of eval_Fxc, as in k_xc_grid
       double sth = th_s[i], hmu, hnu, hphi;
       if (geom == 0) {
@@ -782,12 +825,13 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
 
 // X4 theta expansion: GA[Q][a][b] = sum_i Theta_a Theta_b Fo0 + dTheta_a Theta_b Fo1 ; GB[Q][a][b] = sum_i Theta_a Theta_b Fo2
 //    meta-GGA: GA += sum_i dTheta_a dTheta_b Fo4 ; GC[Q][a][b] = sum_i Theta_a Theta_b Fo3
+//    Laplacian: GL[Q][a][b] = sum_i Theta_a Theta_b Fo5
 __global__ void k_xc_fock_theta(const double *__restrict__ Fo, const double *__restrict__ Th,
                                 const double *__restrict__ dTh, int A, int nth, int G,
                                 const int *__restrict__ grp_off, const int *__restrict__ grp_shell, int do_grad,
-                                int do_tau, size_t NQ, int rank, int nranks, double *__restrict__ GA,
-                                double *__restrict__ GB, double *__restrict__ GC) {
-  // LDS: f0..f4[nth], then the Theta / dTheta rows of the two shell groups, [i][shell] (the pair loop reads them with
+                                int do_tau, int do_lapl, size_t NQ, int rank, int nranks, double *__restrict__ GA,
+                                double *__restrict__ GB, double *__restrict__ GC, double *__restrict__ GL) {
+  // LDS: f0..f4[nth] (f5 with do_lapl), then the Theta / dTheta rows of the two shell groups, [i][shell] (the pair loop reads them with
   // consecutive b across threads; from global memory the loop was latency-bound: 0.26 ms per build at Nbf = 4230)
   extern __shared__ double sh[];
   size_t Q = blockIdx.x;
@@ -797,14 +841,15 @@ __global__ void k_xc_fock_theta(const double *__restrict__ Fo, const double *__r
   int b0 = grp_off[gb], nb = grp_off[gb + 1] - b0;
   size_t stride = NQ * G * G * nth;
   size_t o = ((Q * G + ga) * G + gb) * nth;
-  double *f0 = sh, *f1 = sh + nth, *f2 = sh + 2 * nth, *f3 = sh + 3 * nth, *f4 = sh + 4 * nth;
-  double *sTa = sh + 5 * nth, *sDa = sTa + (size_t)nth * na, *sTb = sDa + (size_t)nth * na, *sDb = sTb + (size_t)nth * nb;
+  double *f0 = sh, *f1 = sh + nth, *f2 = sh + 2 * nth, *f3 = sh + 3 * nth, *f4 = sh + 4 * nth, *f5 = sh + 5 * nth;
+  double *sTa = sh + (do_lapl ? 6 : 5) * nth, *sDa = sTa + (size_t)nth * na, *sTb = sDa + (size_t)nth * na, *sDb = sTb + (size_t)nth * nb;
   for (int i = threadIdx.x; i < nth; i += blockDim.x) {
     f0[i] = Fo[o + i];
     f1[i] = do_grad ? Fo[stride + o + i] : 0.0;
     f2[i] = do_grad ? Fo[2 * stride + o + i] : 0.0;
     f3[i] = do_tau ? Fo[3 * stride + o + i] : 0.0;
     f4[i] = do_tau ? Fo[4 * stride + o + i] : 0.0;
+    if (do_lapl) f5[i] = Fo[5 * stride + o + i];
   }
   for (int t = threadIdx.x; t < nth * na; t += blockDim.x) {
     int ia = t / nth, i = t % nth;  // consecutive threads read consecutive theta points of one shell
@@ -823,7 +868,7 @@ __global__ void k_xc_fock_theta(const double *__restrict__ Fo, const double *__r
   for (int t = threadIdx.x; t < na * nb; t += blockDim.x) {
     const int ia = t / nb, ib = t % nb;
     int a = grp_shell[a0 + ia], b = grp_shell[b0 + ib];
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (int i = 0; i < nth; i++) {
       const double tai = sTa[i * na + ia], dai = sDa[i * na + ia], tbi = sTb[i * nb + ib];
       s0 += (tai * f0[i] + dai * f1[i]) * tbi;
@@ -832,23 +877,28 @@ __global__ void k_xc_fock_theta(const double *__restrict__ Fo, const double *__r
         s0 += dai * sDb[i * nb + ib] * f4[i];
         s2 += tai * tbi * f3[i];
       }
+      if (do_lapl) s3 += tai * tbi * f5[i];
     }
     GA[Q * AA + (size_t)a * A + b] = s0;
     if (do_grad) GB[Q * AA + (size_t)a * A + b] = s1;
     if (do_tau) GC[Q * AA + (size_t)a * A + b] = s2;
+    if (do_lapl) GL[Q * AA + (size_t)a * A + b] = s3;
   }
 }
 
 // X4 for shell groups whose Theta tables do not fit a CU's LDS (lmax beyond ~33 with mmax = 2): the theta points go
 // through LDS nthc at a time and every thread keeps the sums of its (a, b) pairs in registers across the chunks
 // (at most XC_FT_MAXPP pairs per thread: groups of up to 64 shells)
+// (LAPL: the Laplacian plane Fo5 -> GL as in k_xc_fock_theta; a template parameter, so that the instance without it keeps
+// its register budget)
 constexpr int XC_FT_MAXPP = 16;
+template <bool LAPL>
 __global__ __launch_bounds__(256) void k_xc_fock_theta_chunked(const double *__restrict__ Fo, const double *__restrict__ Th,
                                                                const double *__restrict__ dTh, int A, int nth, int G,
                                                                const int *__restrict__ grp_off, const int *__restrict__ grp_shell,
                                                                int do_grad, int do_tau, size_t NQ, int rank, int nranks,
                                                                double *__restrict__ GA, double *__restrict__ GB,
-                                                               double *__restrict__ GC, int nthc) {
+                                                               double *__restrict__ GC, double *__restrict__ GL, int nthc) {
   extern __shared__ double sh[];
   size_t Q = blockIdx.x;
   if ((int)(Q % nranks) != rank) return;
@@ -857,11 +907,14 @@ __global__ __launch_bounds__(256) void k_xc_fock_theta_chunked(const double *__r
   int b0 = grp_off[gb], nb = grp_off[gb + 1] - b0;
   size_t stride = NQ * G * G * nth;
   size_t o = ((Q * G + ga) * G + gb) * nth;
-  double *f0 = sh, *f1 = sh + nthc, *f2 = sh + 2 * nthc, *f3 = sh + 3 * nthc, *f4 = sh + 4 * nthc;
-  double *sTa = sh + 5 * nthc, *sDa = sTa + (size_t)nthc * na, *sTb = sDa + (size_t)nthc * na, *sDb = sTb + (size_t)nthc * nb;
-  double s0[XC_FT_MAXPP], s1[XC_FT_MAXPP], s2[XC_FT_MAXPP];
+  double *f0 = sh, *f1 = sh + nthc, *f2 = sh + 2 * nthc, *f3 = sh + 3 * nthc, *f4 = sh + 4 * nthc, *f5 = sh + 5 * nthc;
+  double *sTa = sh + (LAPL ? 6 : 5) * nthc, *sDa = sTa + (size_t)nthc * na, *sTb = sDa + (size_t)nthc * na, *sDb = sTb + (size_t)nthc * nb;
+  double s0[XC_FT_MAXPP], s1[XC_FT_MAXPP], s2[XC_FT_MAXPP], s3[LAPL ? XC_FT_MAXPP : 1];
 #pragma unroll
   for (int q = 0; q < XC_FT_MAXPP; q++) s0[q] = s1[q] = s2[q] = 0.0;
+  if (LAPL)
+#pragma unroll
+    for (int q = 0; q < (LAPL ? XC_FT_MAXPP : 1); q++) s3[q] = 0.0;
   for (int c0 = 0; c0 < nth; c0 += nthc) {
     const int len = min(nthc, nth - c0);
     if (c0) __syncthreads();
@@ -871,6 +924,7 @@ __global__ __launch_bounds__(256) void k_xc_fock_theta_chunked(const double *__r
       f2[i] = do_grad ? Fo[2 * stride + o + c0 + i] : 0.0;
       f3[i] = do_tau ? Fo[3 * stride + o + c0 + i] : 0.0;
       f4[i] = do_tau ? Fo[4 * stride + o + c0 + i] : 0.0;
+      if (LAPL) f5[i] = Fo[5 * stride + o + c0 + i];
     }
     for (int t = threadIdx.x; t < len * na; t += blockDim.x) {
       int ia = t / len, i = t % len;
@@ -890,7 +944,7 @@ __global__ __launch_bounds__(256) void k_xc_fock_theta_chunked(const double *__r
       const int t = threadIdx.x + q * 256;
       if (t < na * nb) {
         const int ia = t / nb, ib = t % nb;
-        double t0 = s0[q], t1 = s1[q], t2 = s2[q];
+        double t0 = s0[q], t1 = s1[q], t2 = s2[q], t3 = LAPL ? s3[LAPL ? q : 0] : 0.0;
         for (int i = 0; i < len; i++) {
           const double tai = sTa[i * na + ia], dai = sDa[i * na + ia], tbi = sTb[i * nb + ib];
           t0 += (tai * f0[i] + dai * f1[i]) * tbi;
@@ -899,10 +953,12 @@ __global__ __launch_bounds__(256) void k_xc_fock_theta_chunked(const double *__r
             t0 += dai * sDb[i * nb + ib] * f4[i];
             t2 += tai * tbi * f3[i];
           }
+          if (LAPL) t3 += tai * tbi * f5[i];
         }
         s0[q] = t0;
         s1[q] = t1;
         s2[q] = t2;
+        if (LAPL) s3[LAPL ? q : 0] = t3;
       }
     }
   }
@@ -916,6 +972,7 @@ __global__ __launch_bounds__(256) void k_xc_fock_theta_chunked(const double *__r
       GA[Q * AA + (size_t)a * A + b] = s0[q];
       if (do_grad) GB[Q * AA + (size_t)a * A + b] = s1[q];
       if (do_tau) GC[Q * AA + (size_t)a * A + b] = s2[q];
+      if (LAPL) GL[Q * AA + (size_t)a * A + b] = s3[LAPL ? q : 0];
     }
   }
 }
@@ -923,11 +980,15 @@ __global__ __launch_bounds__(256) void k_xc_fock_theta_chunked(const double *__r
 // X5 radial expansion into the compact Fock blocks:
 //    Hc[x][y][e][n'][n] = sum_q B_n B_n' (GA_xy + GA_yx) + B'_n B_n' GB_xy + B_n B'_n' GB_yx
 //    meta-GGA: + B'_n B'_n' (GC_xy + GC_yx)
+//    Laplacian (increment_mgga_lapl, dftgrid.h:257-281): + B_n L_n' GL_xy + L_n B_n' GL_yx, and the shell part of eval_lf,
+//    -(l_y(l_y+1) GL_xy + l_x(l_x+1) GL_yx)/r^2, folded into the B_n B_n' weight
 __global__ void k_xc_fock_radial(const double *__restrict__ GA, const double *__restrict__ GB,
-                                 const double *__restrict__ GC, const double *__restrict__ B,
-                                 const double *__restrict__ dB, int A, int E, int p, int nq, int do_grad, int do_tau,
-                                 int rank, int nranks, double *__restrict__ Hc) {
-  extern __shared__ double sh[];  // gs[nq], g1[nq], g2[nq], g3[nq], B[nq][p], dB[nq][p] of this element
+                                 const double *__restrict__ GC, const double *__restrict__ GL, const double *__restrict__ B,
+                                 const double *__restrict__ dB, const double *__restrict__ Lr, const int *__restrict__ shell_l,
+                                 const double *__restrict__ rad_sh, int A, int E, int p, int nq, int do_grad, int do_tau,
+                                 int do_lapl, int rank, int nranks, double *__restrict__ Hc) {
+  // gs[nq], g1[nq], g2[nq], g3[nq], B[nq][p], dB[nq][p] of this element, U[nq][p], W[nq][p]; do_lapl: L[nq][p], V[nq][p]
+  extern __shared__ double sh[];
   int xy = blockIdx.x, e = blockIdx.y;
   int x = xy / A, y = xy % A;
   int yx = y * A + x;
@@ -942,21 +1003,45 @@ __global__ void k_xc_fock_radial(const double *__restrict__ GA, const double *__
     g2[q] = (own && do_grad) ? GB[Q * AA + yx] : 0.0;
     g3[q] = (own && do_tau) ? GC[Q * AA + xy] + GC[Q * AA + yx] : 0.0;
   }
+  double *sU = sdB + nq * p, *sW = sU + nq * p;
+  double *sL = sW + nq * p, *sV = sL + nq * p;
   for (int t = threadIdx.x; t < nq * p; t += blockDim.x) {
     sB[t] = B[(size_t)e * nq * p + t];
     sdB[t] = dB[(size_t)e * nq * p + t];
+    if (do_lapl) sL[t] = Lr[(size_t)e * nq * p + t];
   }
   __syncthreads();
   // U[q][m] = gs B_m + g2 B'_m,  W[q][m] = g1 B_m + g3 B'_m:  H[n][m] = sum_q B_n U[q][m] + B'_n W[q][m]  (four LDS reads
   // per point and output instead of eight: the loop is LDS-bound)
-  double *sU = sdB + nq * p, *sW = sU + nq * p;
+  int pp = p * p;
+  if (do_lapl) {
+    // U += GL_xy L_m with the shell terms in the B B weight, V[q][m] = GL_yx B_m:  H[n][m] += sum_q L_n V[q][m]
+    const int lx = shell_l[x] * (shell_l[x] + 1), ly = shell_l[y] * (shell_l[y] + 1);
+    for (int t = threadIdx.x; t < nq * p; t += blockDim.x) {
+      const int q = t / p;
+      const size_t Q = (size_t)e * nq + q;
+      const bool own = ((int)(Q % nranks) == rank);
+      const double gl1 = own ? GL[Q * AA + xy] : 0.0, gl2 = own ? GL[Q * AA + yx] : 0.0;
+      const double ir2 = 1.0 / (rad_sh[Q] * rad_sh[Q]);
+      sU[t] = (gs[q] - (ly * gl1 + lx * gl2) * ir2) * sB[t] + g2[q] * sdB[t] + gl1 * sL[t];
+      sW[t] = g1[q] * sB[t] + g3[q] * sdB[t];
+      sV[t] = gl2 * sB[t];
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < pp; t += blockDim.x) {
+      int n = t % p, m = t / p;
+      double acc = 0.0;
+      for (int q = 0; q < nq; q++) acc += sB[q * p + n] * sU[q * p + m] + sdB[q * p + n] * sW[q * p + m] + sL[q * p + n] * sV[q * p + m];
+      Hc[((size_t)xy * E + e) * pp + t] = acc;
+    }
+    return;
+  }
   for (int t = threadIdx.x; t < nq * p; t += blockDim.x) {
     const int q = t / p;
     sU[t] = gs[q] * sB[t] + g2[q] * sdB[t];
     sW[t] = g1[q] * sB[t] + g3[q] * sdB[t];
   }
   __syncthreads();
-  int pp = p * p;
   for (int t = threadIdx.x; t < pp; t += blockDim.x) {
     int n = t % p, m = t / p;
     double acc = 0.0;
@@ -1040,16 +1125,16 @@ __global__ void k_mp_fill(const double *__restrict__ rad_w, const double *__rest
 // launchers
 // -------------------------------------------------------------------------------------------------
 static int round_up64(int n) { return ((n + 63) / 64) * 64; }
-static size_t xc_fock_radial_lds(int p, int nq) {
-  const size_t shb = (size_t)(4 * nq + 4 * nq * p) * sizeof(double);
+static size_t xc_fock_radial_lds(int p, int nq, int do_lapl = 0) {
+  const size_t shb = (size_t)(4 * nq + (do_lapl ? 6 : 4) * nq * p) * sizeof(double);
   if (shb > 150 * 1024) throw std::runtime_error("radial quadrature too large for the XC Fock kernel's LDS tables");
   if (shb > 64 * 1024)
     HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_radial, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
   return shb;
 }
-// LDS of k_xc_fock_theta: five potential rows and the Theta, dTheta rows of two shell groups
-static size_t xc_fock_theta_lds(int nth, int maxgrp) {
-  size_t shb = (size_t)(5 * nth + 4 * nth * maxgrp) * sizeof(double);
+// LDS of k_xc_fock_theta: five (six with the Laplacian) potential rows and the Theta, dTheta rows of two shell groups
+static size_t xc_fock_theta_lds(int nth, int maxgrp, int do_lapl) {
+  size_t shb = (size_t)((do_lapl ? 6 : 5) * nth + 4 * nth * maxgrp) * sizeof(double);
   if (shb > 160 * 1024) throw std::runtime_error("angular grid too large for the XC Fock kernel's LDS tables");  // callers use launch_xc_fock_theta
   if (shb > 64 * 1024)
     HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_theta, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
@@ -1064,29 +1149,36 @@ static size_t xc_lds_limit() {
 // X4 launch: the one-pass kernel when its tables fit a CU's LDS, the chunked one otherwise
 static void launch_xc_fock_theta(hfg_ctx *ctx, size_t NQ, int G, int nth, int maxgrp, const double *Fo, const double *Th, const double *dTh,
                                  int A, const int *grp_off, const int *grp_shell, int do_grad, int do_tau, int rank, int nranks,
-                                 double *GA, double *GB, double *GC) {
-  const size_t need = (size_t)(5 * nth + 4 * nth * maxgrp) * sizeof(double);
+                                 double *GA, double *GB, double *GC, int do_lapl = 0, double *GL = nullptr) {
+  const int nf = do_lapl ? 6 : 5;  // potential rows
+  const size_t need = (size_t)(nf * nth + 4 * nth * maxgrp) * sizeof(double);
   if (need <= xc_lds_limit()) {
-    hipLaunchKernelGGL(k_xc_fock_theta, dim3((unsigned)NQ, G * G), dim3(256), xc_fock_theta_lds(nth, maxgrp), ctx->stream, Fo, Th, dTh, A, nth,
-                       G, grp_off, grp_shell, do_grad, do_tau, NQ, rank, nranks, GA, GB, GC);
+    hipLaunchKernelGGL(k_xc_fock_theta, dim3((unsigned)NQ, G * G), dim3(256), xc_fock_theta_lds(nth, maxgrp, do_lapl), ctx->stream, Fo, Th, dTh, A,
+                       nth, G, grp_off, grp_shell, do_grad, do_tau, do_lapl, NQ, rank, nranks, GA, GB, GC, GL);
     return;
   }
   if (maxgrp * maxgrp > XC_FT_MAXPP * 256) throw std::runtime_error("angular basis too large for the XC Fock kernels (more than 64 shells of one m)");
-  int nthc = (int)(xc_lds_limit() / sizeof(double) / (5 + 4 * maxgrp));
+  int nthc = (int)(xc_lds_limit() / sizeof(double) / (nf + 4 * maxgrp));
   if (nthc < 4) throw std::runtime_error("angular basis too large for the XC Fock kernels' LDS tables");
   nthc = std::min(nthc, nth);
-  const size_t shb = (size_t)(5 * nthc + 4 * nthc * maxgrp) * sizeof(double);
+  const size_t shb = (size_t)(nf * nthc + 4 * nthc * maxgrp) * sizeof(double);
+  if (do_lapl) {
+    if (shb > 64 * 1024)
+      HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_theta_chunked<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
+    hipLaunchKernelGGL(k_xc_fock_theta_chunked<true>, dim3((unsigned)NQ, G * G), dim3(256), shb, ctx->stream, Fo, Th, dTh, A, nth, G, grp_off,
+                       grp_shell, do_grad, do_tau, NQ, rank, nranks, GA, GB, GC, GL, nthc);
+    return;
+  }
   if (shb > 64 * 1024)
-    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_theta_chunked, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  hipLaunchKernelGGL(k_xc_fock_theta_chunked, dim3((unsigned)NQ, G * G), dim3(256), shb, ctx->stream, Fo, Th, dTh, A, nth, G, grp_off, grp_shell,
-                     do_grad, do_tau, NQ, rank, nranks, GA, GB, GC, nthc);
+    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_theta_chunked<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
+  hipLaunchKernelGGL(k_xc_fock_theta_chunked<false>, dim3((unsigned)NQ, G * G), dim3(256), shb, ctx->stream, Fo, Th, dTh, A, nth, G, grp_off,
+                     grp_shell, do_grad, do_tau, NQ, rank, nranks, GA, GB, GC, (double *)nullptr, nthc);
 }
 
 // LDS of k_xc_density_radial (256 threads): P block, the two transposed tables, the partial sums of the j classes
-static size_t xc_fock_radial_lds(int p, int nq);
-static size_t xc_density_radial_lds(int p, int nq) {
+static size_t xc_density_radial_lds(int p, int nq, int do_lapl = 0) {
   const int NJ = (256 / nq > 0) ? std::min(256 / nq, p) : 1;
-  size_t shb = (size_t)(p * p + 2 * p * nq + 3 * NJ * nq) * sizeof(double);
+  size_t shb = (size_t)(p * p + 2 * p * nq + 3 * NJ * nq + (do_lapl ? NJ * nq + p * nq : 0)) * sizeof(double);
   if (shb > 150 * 1024) throw std::runtime_error("radial quadrature too large for the XC density kernel's LDS tables");
   if (shb > 64 * 1024)  // elements of more than ~24 nodes with the default 5 quadrature points per node
     HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_density_radial, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
@@ -1095,7 +1187,7 @@ static size_t xc_density_radial_lds(int p, int nq) {
 
 struct FockAux {
   DevBuf<int> pure_shell, pure_n, lmpos;
-  DevBuf<double> Pc, Jc, Pc2, Jc2, Paux, Y, Jaux, D0, D1, D2, V, Fo, GA, GB, GC, partial, scal;
+  DevBuf<double> Pc, Jc, Pc2, Jc2, Paux, Y, Jaux, D0, D1, D2, D3, V, Fo, GA, GB, GC, GL, partial, scal;
 };
 
 static std::map<hfg_dev_tables *, FockAux *> g_aux;
@@ -1205,7 +1297,10 @@ void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const do
   const int A = t->A, E = t->E, p = t->p, nq = t->nq, G = t->G, nth = t->ntheta, nphi = t->nphi;
   const size_t NQ = (size_t)E * nq, AA = (size_t)A * A;
   int do_grad = ((x_func > 0 && xc::is_gga(x_func)) || (c_func > 0 && xc::is_gga(c_func))) ? 1 : 0;
-  int do_tau = ((x_func > 0 && xc::is_mgga(x_func)) || (c_func > 0 && xc::is_mgga(c_func))) ? 1 : 0;
+  // Laplacian-dependent meta-GGAs (the atomic program only; both available ones need tau as well)
+  const int do_lapl = ((x_func > 0 && xc::is_mgga_lapl(x_func)) || (c_func > 0 && xc::is_mgga_lapl(c_func))) ? 1 : 0;
+  if (do_lapl && t->geom != 1) throw std::logic_error("Laplacian not implemented!\n");  // diatomic dftgrid.cpp:115-116, 209-210
+  int do_tau = ((x_func > 0 && xc::is_mgga(x_func)) || (c_func > 0 && xc::is_mgga(c_func)) || do_lapl) ? 1 : 0;
   // meta-GGAs: a floor under the density threshold.  Below 1e-50 the tau-dependent expressions overflow (tau_unif ~ n^(5/3),
   // p ~ sigma / n^(8/3)) and return NaN where the point carries nothing; libxc keeps such points out with its own tau and
   // sigma thresholds, --dftthr 0 would switch the density threshold off.  Far-field densities of an SCF density are
@@ -1219,30 +1314,36 @@ void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const do
     a.D2.resize(NQ * AA);
     a.GC.resize(NQ * AA);
   }
+  if (do_lapl) {
+    a.D3.resize(NQ * AA);
+    a.GL.resize(NQ * AA);
+  }
   const size_t nv = NQ * G * G * nth;
-  a.V.resize(5 * nv);
-  a.Fo.resize(5 * nv);
+  a.V.resize((do_lapl ? 6 : 5) * nv);
+  a.Fo.resize((do_lapl ? 6 : 5) * nv);
   a.partial.resize(3 * NQ);
   int maxgrp = 0;
   for (int g = 0; g < G; g++) maxgrp = std::max(maxgrp, t->h_grp_off[g + 1] - t->h_grp_off[g]);
 
-  hipLaunchKernelGGL(k_xc_density_radial, dim3(A * A, E), dim3(256), xc_density_radial_lds(p, nq),
-                     ctx->stream, dPc, t->rad_B.p, t->rad_dB.p, A, E, p, nq, do_grad, do_tau, ctx->shard_rank, ctx->shard_n, a.D0.p,
-                     a.D1.p, a.D2.p);
+  hipLaunchKernelGGL(k_xc_density_radial, dim3(A * A, E), dim3(256), xc_density_radial_lds(p, nq, do_lapl),
+                     ctx->stream, dPc, t->rad_B.p, t->rad_dB.p, (const double *)t->rad_L.p, A, E, p, nq, do_grad, do_tau, do_lapl,
+                     ctx->shard_rank, ctx->shard_n, a.D0.p, a.D1.p, a.D2.p, a.D3.p);
   hipLaunchKernelGGL(k_xc_density_theta, dim3((unsigned)NQ, G * G), dim3(std::min(256, round_up64(nth))),
-                     3 * maxgrp * maxgrp * sizeof(double), ctx->stream, a.D0.p, a.D1.p, a.D2.p, t->Th.p, t->dTh.p, A, nth, G,
-                     t->grp_off.p, t->grp_shell.p, do_grad, do_tau, NQ, ctx->shard_rank, ctx->shard_n, a.V.p);
-  size_t shb = (size_t)(5 * nth * nphi + 3 * 4) * sizeof(double);
+                     (do_lapl ? 4 : 3) * maxgrp * maxgrp * sizeof(double), ctx->stream, a.D0.p, a.D1.p, a.D2.p, (const double *)a.D3.p,
+                     t->Th.p, t->dTh.p, t->shell_l.p, t->rad_sh.p, A, nth, G, t->grp_off.p, t->grp_shell.p, do_grad, do_tau, do_lapl,
+                     NQ, ctx->shard_rank, ctx->shard_n, a.V.p);
+  size_t shb = (size_t)((do_lapl ? 6 : 5) * nth * nphi + 3 * 4) * sizeof(double);
+  if (do_lapl && shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the grid kernel's LDS planes");
   if (shb > 64 * 1024)
     HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_grid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
   hipLaunchKernelGGL(k_xc_grid, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
                      t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
-                     x_func, c_func, do_grad, do_tau, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p);
+                     x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p);
   launch_xc_fock_theta(ctx, NQ, G, nth, maxgrp, a.Fo.p, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, do_grad, do_tau, ctx->shard_rank,
-                       ctx->shard_n, a.GA.p, a.GB.p, a.GC.p);
-  hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))), xc_fock_radial_lds(p, nq),
-                     ctx->stream, a.GA.p, a.GB.p, a.GC.p, t->rad_B.p, t->rad_dB.p, A, E, p, nq, do_grad, do_tau,
-                     ctx->shard_rank, ctx->shard_n, dHc);
+                       ctx->shard_n, a.GA.p, a.GB.p, a.GC.p, do_lapl, a.GL.p);
+  hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))), xc_fock_radial_lds(p, nq, do_lapl),
+                     ctx->stream, a.GA.p, a.GB.p, a.GC.p, (const double *)a.GL.p, t->rad_B.p, t->rad_dB.p, (const double *)t->rad_L.p,
+                     t->shell_l.p, t->rad_sh.p, A, E, p, nq, do_grad, do_tau, do_lapl, ctx->shard_rank, ctx->shard_n, dHc);
   hipLaunchKernelGGL(k_xc_sum_partials, dim3(1), dim3(64), 0, ctx->stream, a.partial.p, NQ, dScal);
   HFG_HIP_CHECK(hipGetLastError());
 }
@@ -1280,6 +1381,67 @@ void set_xc_params(hfg_ctx *ctx, int x_func, const double *x_pars, int nx, int c
   slot = (slot + 1) % 8;
 }
 
+/// libxc's xc_mgga_exc_vxc array layout on host arrays for one functional id (hfg_xc_eval): the point code of the grid kernels,
+/// compiled for the host, with their threshold rules (density threshold, the meta-GGA floor 1e-40 under it, exchange channels
+/// below it left out, non-finite vlapl zeroed).  nspin 1: rho, sigma, lapl, tau, exc, vrho, vsigma, vlapl, vtau hold one value
+/// per point; nspin 2: rho[2], sigma[3] (aa, ab, bb), lapl[2], tau[2] per point, and the potentials likewise.  Missing inputs
+/// (NULL) are zero, missing outputs are skipped.
+void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double *sigma, const double *lapl, const double *tau,
+                  double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau, double thr) {
+  if (id <= 0 || !xc::is_supported(id)) throw std::runtime_error("Functional not found!");
+  if (nspin != 1 && nspin != 2) throw std::logic_error("hfg_xc_eval: nspin must be 1 or 2\n");
+  if (!rho) throw std::logic_error("hfg_xc_eval: rho is required\n");
+  if (xc::is_mgga(id) || xc::is_mgga_lapl(id)) thr = std::max(thr, 1e-40);
+  auto in = [](const double *a, size_t i) { return a ? a[i] : 0.0; };
+  auto out = [](double *a, size_t i, double v) {
+    if (a) a[i] = v;
+  };
+  for (size_t i = 0; i < np; i++) {
+    if (nspin == 1) {
+      const double r = rho[i], s = in(sigma, i), l = in(lapl, i), t = in(tau, i);
+      double e = 0.0, vr = 0.0, vs = 0.0, vt = 0.0, vl = 0.0;
+      if (r >= thr && r > 0.0) {
+        const bool live = 0.5 * r >= thr;
+        if (xc::is_mgga_lapl(id)) xc::eval_add_mgga_lapl(id, r, s, t, l, live, e, vr, vs, vt, vl);
+        else if (xc::is_mgga(id)) xc::eval_add_mgga(id, r, s, t, live, e, vr, vs, vt);
+        else xc::eval_add(id, r, s, live, e, vr, vs);
+        if (!std::isfinite(vl)) vl = 0.0;
+      }
+      out(exc, i, e);
+      out(vrho, i, vr);
+      out(vsigma, i, vs);
+      out(vlapl, i, vl);
+      out(vtau, i, vt);
+      continue;
+    }
+    const double r0 = rho[2 * i], r1 = rho[2 * i + 1], rt = r0 + r1;
+    double e = 0.0, va = 0.0, vb = 0.0, vsaa = 0.0, vsab = 0.0, vsbb = 0.0, vta = 0.0, vtb = 0.0, vla = 0.0, vlb = 0.0;
+    if (rt >= thr && rt > 0.0) {
+      const double ra = std::max(r0, thr), rb = std::max(r1, thr);
+      const double saa = in(sigma, 3 * i), sab = in(sigma, 3 * i + 1), sbb = in(sigma, 3 * i + 2);
+      const double ta = in(tau, 2 * i), tb = in(tau, 2 * i + 1), la = in(lapl, 2 * i), lb = in(lapl, 2 * i + 1);
+      if (xc::is_mgga_lapl(id))
+        xc::eval_add_mgga_lapl_pol(id, ra, rb, saa, sab, sbb, ta, tb, la, lb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb, vta, vtb,
+                                   vla, vlb);
+      else if (xc::is_mgga(id))
+        xc::eval_add_mgga_pol(id, ra, rb, saa, sab, sbb, ta, tb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb, vta, vtb);
+      else xc::eval_add_pol(id, ra, rb, saa, sab, sbb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb);
+      if (!std::isfinite(vla)) vla = 0.0;
+      if (!std::isfinite(vlb)) vlb = 0.0;
+    }
+    out(exc, i, e);
+    out(vrho, 2 * i, va);
+    out(vrho, 2 * i + 1, vb);
+    out(vsigma, 3 * i, vsaa);
+    out(vsigma, 3 * i + 1, vsab);
+    out(vsigma, 3 * i + 2, vsbb);
+    out(vlapl, 2 * i, vla);
+    out(vlapl, 2 * i + 1, vlb);
+    out(vtau, 2 * i, vta);
+    out(vtau, 2 * i + 1, vtb);
+  }
+}
+
 void xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dH, double *dScal,
                  double thr) {
   hfg_dev_tables *t = tables_of(ctx, basis);
@@ -1305,13 +1467,16 @@ void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, cons
   const int A = t->A, E = t->E, p = t->p, nq = t->nq, G = t->G, nth = t->ntheta, nphi = t->nphi;
   const size_t NQ = (size_t)E * nq, AA = (size_t)A * A;
   int do_grad = ((x_func > 0 && xc::is_gga(x_func)) || (c_func > 0 && xc::is_gga(c_func))) ? 1 : 0;
-  int do_tau = ((x_func > 0 && xc::is_mgga(x_func)) || (c_func > 0 && xc::is_mgga(c_func))) ? 1 : 0;
+  // Laplacian-dependent meta-GGAs (the atomic program only; both available ones need tau as well)
+  const int do_lapl = ((x_func > 0 && xc::is_mgga_lapl(x_func)) || (c_func > 0 && xc::is_mgga_lapl(c_func))) ? 1 : 0;
+  if (do_lapl && t->geom != 1) throw std::logic_error("Laplacian not implemented!\n");  // diatomic dftgrid.cpp:115-116, 209-210
+  int do_tau = ((x_func > 0 && xc::is_mgga(x_func)) || (c_func > 0 && xc::is_mgga(c_func)) || do_lapl) ? 1 : 0;
   // meta-GGAs: a floor under the density threshold.  Below 1e-50 the tau-dependent expressions overflow (tau_unif ~ n^(5/3),
   // p ~ sigma / n^(8/3)) and return NaN where the point carries nothing; libxc keeps such points out with its own tau and
   // sigma thresholds, --dftthr 0 would switch the density threshold off.  Far-field densities of an SCF density are
   // rounding noise of the eigensolver at that level (tests/test_gpu_fullsize.py::test_fullsize_xc_without_density_threshold).
   if (do_tau) thr = std::max(thr, 1e-40);
-  const int npl = do_tau ? 5 : 3;
+  const int npl = do_lapl ? 6 : (do_tau ? 5 : 3);
   a.D0.resize(NQ * AA);
   a.D1.resize(NQ * AA);
   a.GA.resize(NQ * AA);
@@ -1320,6 +1485,10 @@ void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, cons
     a.D2.resize(NQ * AA);
     a.GC.resize(NQ * AA);
   }
+  if (do_lapl) {
+    a.D3.resize(NQ * AA);
+    a.GL.resize(NQ * AA);
+  }
   const size_t nv = NQ * G * G * nth;
   a.V.resize(2 * npl * nv);
   a.Fo.resize(2 * npl * nv);
@@ -1327,29 +1496,31 @@ void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, cons
   int maxgrp = 0;
   for (int g = 0; g < G; g++) maxgrp = std::max(maxgrp, t->h_grp_off[g + 1] - t->h_grp_off[g]);
   for (int sp = 0; sp < 2; sp++) {
-    hipLaunchKernelGGL(k_xc_density_radial, dim3(A * A, E), dim3(256), xc_density_radial_lds(p, nq),
-                       ctx->stream, sp ? dPcb : dPca, t->rad_B.p, t->rad_dB.p, A, E, p, nq, do_grad, do_tau, ctx->shard_rank,
-                       ctx->shard_n, a.D0.p, a.D1.p, a.D2.p);
+    hipLaunchKernelGGL(k_xc_density_radial, dim3(A * A, E), dim3(256), xc_density_radial_lds(p, nq, do_lapl),
+                       ctx->stream, sp ? dPcb : dPca, t->rad_B.p, t->rad_dB.p, (const double *)t->rad_L.p, A, E, p, nq, do_grad, do_tau,
+                       do_lapl, ctx->shard_rank, ctx->shard_n, a.D0.p, a.D1.p, a.D2.p, a.D3.p);
     hipLaunchKernelGGL(k_xc_density_theta, dim3((unsigned)NQ, G * G), dim3(std::min(256, round_up64(nth))),
-                       3 * maxgrp * maxgrp * sizeof(double), ctx->stream, a.D0.p, a.D1.p, (const double *)a.D2.p, t->Th.p, t->dTh.p,
-                       A, nth, G, t->grp_off.p, t->grp_shell.p, do_grad, do_tau, NQ, ctx->shard_rank, ctx->shard_n,
-                       a.V.p + (size_t)sp * npl * nv);
+                       (do_lapl ? 4 : 3) * maxgrp * maxgrp * sizeof(double), ctx->stream, a.D0.p, a.D1.p, (const double *)a.D2.p,
+                       (const double *)a.D3.p, t->Th.p, t->dTh.p, t->shell_l.p, t->rad_sh.p, A, nth, G, t->grp_off.p, t->grp_shell.p,
+                       do_grad, do_tau, do_lapl, NQ, ctx->shard_rank, ctx->shard_n, a.V.p + (size_t)sp * npl * nv);
   }
+  const int npot2 = do_lapl ? 12 : (do_tau ? 10 : 8);  // LDS potential planes, both spins
   int rowc = nth;  // theta rows per pass through LDS
-  while ((size_t)((do_tau ? 10 : 8) * rowc * nphi + 3 * 4) * sizeof(double) > xc_lds_limit() && rowc > 1) rowc = (rowc + 1) / 2;
-  size_t shb = (size_t)((do_tau ? 10 : 8) * rowc * nphi + 3 * 4) * sizeof(double);
+  while ((size_t)(npot2 * rowc * nphi + 3 * 4) * sizeof(double) > xc_lds_limit() && rowc > 1) rowc = (rowc + 1) / 2;
+  size_t shb = (size_t)(npot2 * rowc * nphi + 3 * 4) * sizeof(double);
   if (shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the polarised grid kernel's LDS tile");
   if (shb > 64 * 1024)
     HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_grid_pol, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
   hipLaunchKernelGGL(k_xc_grid_pol, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
                      t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
-                     x_func, c_func, do_grad, do_tau, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, rowc);
+                     x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, rowc);
   for (int sp = 0; sp < 2; sp++) {
     launch_xc_fock_theta(ctx, NQ, G, nth, maxgrp, a.Fo.p + (size_t)sp * npl * nv, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, do_grad,
-                         do_tau, ctx->shard_rank, ctx->shard_n, a.GA.p, a.GB.p, a.GC.p);
-    hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))), xc_fock_radial_lds(p, nq),
-                       ctx->stream, a.GA.p, a.GB.p, (const double *)a.GC.p, t->rad_B.p, t->rad_dB.p, A, E, p, nq, do_grad, do_tau,
-                       ctx->shard_rank, ctx->shard_n, sp ? dHcb : dHca);
+                         do_tau, ctx->shard_rank, ctx->shard_n, a.GA.p, a.GB.p, a.GC.p, do_lapl, a.GL.p);
+    hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))), xc_fock_radial_lds(p, nq, do_lapl),
+                       ctx->stream, a.GA.p, a.GB.p, (const double *)a.GC.p, (const double *)a.GL.p, t->rad_B.p, t->rad_dB.p,
+                       (const double *)t->rad_L.p, t->shell_l.p, t->rad_sh.p, A, E, p, nq, do_grad, do_tau, do_lapl, ctx->shard_rank,
+                       ctx->shard_n, sp ? dHcb : dHca);
   }
   hipLaunchKernelGGL(k_xc_sum_partials, dim3(1), dim3(64), 0, ctx->stream, a.partial.p, NQ, dScal);
   HFG_HIP_CHECK(hipGetLastError());
@@ -1397,8 +1568,8 @@ void model_potential_dev(hfg_ctx *ctx, hfg_basis *basis, int kind1, int Z1, doub
   launch_xc_fock_theta(ctx, NQ, G, nth, maxgrp, a.Fo.p, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, 0, 0, 0, 1, a.GA.p, a.GB.p,
                        (double *)nullptr);
   hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))),
-                     xc_fock_radial_lds(p, nq), ctx->stream, a.GA.p, a.GB.p, (const double *)nullptr, t->rad_B.p,
-                     t->rad_dB.p, A, E, p, nq, 0, 0, 0, 1, a.Jc.p);
+                     xc_fock_radial_lds(p, nq), ctx->stream, a.GA.p, a.GB.p, (const double *)nullptr, (const double *)nullptr, t->rad_B.p,
+                     t->rad_dB.p, (const double *)nullptr, t->shell_l.p, t->rad_sh.p, A, E, p, nq, 0, 0, 0, 0, 1, a.Jc.p);
   scatter_dense(ctx, basis, a.Jc.p, dH);
   HFG_HIP_CHECK(hipGetLastError());
 }

@@ -25,7 +25,7 @@ struct BasisView {
   std::function<double(int, int, int)> c0, c2;         // (x,y,L)
   std::function<const helfem::Mat &(int, int, int)> disj, tei;  // (type, tab, e)
   std::function<int(int)> lo;                          // first primitive held by element e
-  std::function<helfem::Mat(int)> bf, df;
+  std::function<helfem::Mat(int)> bf, df, lf;  // lf: atomic only
   std::function<helfem::Vec(int)> wrad, rcoord;  // rcoord: sinh(mu) (prolate) or r (spherical)
 
   int LMind(int L, int M) const {
@@ -140,6 +140,7 @@ BasisView view_of(const hfg_basis *basis, bool rs = false) {
     v.lo = [](int e) { return e == 0 ? 1 : 0; };
     v.bf = [b](int e) { return b->get_bf(e); };
     v.df = [b](int e) { return b->get_df(e); };
+    v.lf = [b](int e) { return b->get_lf(e); };
     v.wrad = [b](int e) { return b->get_wrad(e); };
     v.rcoord = [b](int e) { return b->get_r(e); };
     if (rs) {
@@ -390,6 +391,19 @@ static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_
     t->rad_dB.upload(dB, s);
     t->rad_w.upload(rw, s);
     t->rad_sh.upload(rsh, s);
+    if (b.lf) {
+      // radial part of the Laplacian (eval_lf, atomic/TwoDBasis.cpp:1423-1445) without its shell term -l(l+1) g/r^2, which the
+      // kernels apply from the B table: L_i = g_i'' + 2 g_i'/r
+      std::vector<double> Lr((size_t)E * nq * p, 0.0);
+      for (int e = 0; e < E; e++) {
+        helfem::Mat df = b.df(e), lf = b.lf(e);
+        helfem::Vec r = b.rcoord(e);
+        const int lo = b.lo(e);
+        for (int q = 0; q < nq; q++)
+          for (size_t i = 0; i < lf.n_cols; i++) Lr[((size_t)e * nq + q) * p + i + lo] = lf(q, i) + 2.0 * df(q, i) / r[q];
+      }
+      t->rad_L.upload(Lr, s);
+    }
 
     helfem::Vec xc, wc;
     helfem::chebyshev_rule(ldft, xc, wc);

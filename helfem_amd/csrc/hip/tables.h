@@ -57,6 +57,7 @@ struct hfg_dev_tables {
   // ---- XC grid ----
   int ntheta = 0, nphi = 0, G = 0;  // G = number of distinct m values
   hfg::DevBuf<double> rad_B, rad_dB;       // [E][nq][p]
+  hfg::DevBuf<double> rad_L;               // [E][nq][p] atomic only: g'' + 2 g'/r of g = B/r (TwoDBasis::get_lf)
   hfg::DevBuf<double> rad_w, rad_sh;       // [E][nq]  radial weight (wq*len/2), sinh(mu)
   hfg::DevBuf<double> th_c, th_s, th_w;    // [ntheta] cos, sin, Chebyshev weight
   hfg::DevBuf<double> Th, dTh;             // [A][ntheta]

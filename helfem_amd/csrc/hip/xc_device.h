@@ -85,6 +85,16 @@ struct XCPar {
 #define HFG_XCPAR_DEFAULTS \
   { 1.0, 0.8040, 0.06672455060314922 * HFG_PI * HFG_PI / 3.0, 0.06672455060314922, (1.0 - 0.6931471805599453) / (HFG_PI * HFG_PI), 1.0 }
 static __constant__ XCPar c_xcpar = HFG_XCPAR_DEFAULTS;
+// the parameters as the point code reads them: the constant-memory copy on the device; the defaults in a host build of the
+// same code (hfg_xc_eval), which takes no external parameters
+__host__ __device__ inline const XCPar &xcpar() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return c_xcpar;
+#else
+  static const XCPar h = HFG_XCPAR_DEFAULTS;
+  return h;
+#endif
+}
 
 __host__ __device__ inline Dual eps_lda_x(Dual rho) { return (-0.75 * cbrt(3.0 / HFG_PI)) * dcbrt(rho); }
 
@@ -204,8 +214,8 @@ __host__ __device__ inline Dual eps_lda_c_pw(Dual rho) {
 }
 
 __host__ __device__ inline Dual eps_gga_x_pbe(Dual rho, Dual sigma) {
-  const double kappa = c_xcpar.x_kappa;
-  const double mu = c_xcpar.x_mu;
+  const double kappa = xcpar().x_kappa;
+  const double mu = xcpar().x_mu;
   Dual exu = eps_lda_x(rho);
   Dual kf = dcbrt((3.0 * HFG_PI * HFG_PI) * rho);
   Dual s2 = sigma / (4.0 * kf * kf * rho * rho);
@@ -214,10 +224,10 @@ __host__ __device__ inline Dual eps_gga_x_pbe(Dual rho, Dual sigma) {
 }
 
 __host__ __device__ inline Dual eps_gga_c_pbe(Dual rho, Dual sigma) {
-  const double beta = c_xcpar.c_beta;
-  const double gamma = c_xcpar.c_gamma;
+  const double beta = xcpar().c_beta;
+  const double gamma = xcpar().c_gamma;
   const double B = beta / gamma;
-  const double BB = c_xcpar.c_BB;
+  const double BB = xcpar().c_BB;
   Dual rs = dcbrt(3.0 / (4.0 * HFG_PI) / rho);
   Dual ec = eps_pw92(rs, true);
   Dual kf = dcbrt((3.0 * HFG_PI * HFG_PI) * rho);
@@ -232,11 +242,12 @@ __host__ __device__ inline Dual eps_gga_c_pbe(Dual rho, Dual sigma) {
 }
 
 __host__ __device__ inline bool is_gga(int id) {
-  return id == 101 || id == 130 || id == 406 || id == 202 || id == 231 || id == 106 || id == 131 || id == 402;
+  return id == 101 || id == 130 || id == 406 || id == 202 || id == 231 || id == 106 || id == 131 || id == 402 || id == 206 ||
+         id == 72;
 }
 __host__ __device__ inline bool is_supported(int id) {
   return id == 1 || id == 7 || id == 8 || id == 12 || id == 13 || id == 101 || id == 130 || id == 406 || id == 202 || id == 231 ||
-         id == 546 || id == 641 || id == 178 || id == 106 || id == 131 || id == 402;
+         id == 546 || id == 641 || id == 178 || id == 106 || id == 131 || id == 402 || id == 206 || id == 72;
 }
 
 __host__ __device__ inline bool is_exchange(int id) { return id == 1 || id == 101 || id == 546 || id == 641 || id == 202 || id == 106; }
@@ -256,7 +267,7 @@ __host__ __device__ inline void eval_add(int id, double rho, double sigma, bool 
     if (id == 402) id = -402;  // 0.19 lda_c_vwn_rpa + 0.81 gga_c_lyp
   }
   switch (id) {
-    case 1: e = c_xcpar.x_alpha * eps_lda_x(r); break;
+    case 1: e = xcpar().x_alpha * eps_lda_x(r); break;
     case 7: e = eps_lda_c_vwn(r); break;
     case 12: e = eps_lda_c_pw(r); break;
     case 13: e = eps_pw92(dcbrt(3.0 / (4.0 * HFG_PI) / r), true); break;  // lda_c_pw_mod
@@ -466,10 +477,10 @@ __host__ __device__ inline T pol_eps_pw(T rs, T z, bool mod) {
 template <class T>
 __host__ __device__ inline T pol_eps_pbe_c(T n, T rs, T z, T sig, bool ext = false) {
   // ext: the stand-alone gga_c_pbe takes the external parameters; TPSS's inner PBE keeps the published constants
-  const double beta = ext ? c_xcpar.c_beta : 0.06672455060314922;
-  const double gamma = ext ? c_xcpar.c_gamma : (1.0 - 0.6931471805599453) / (HFG_PI * HFG_PI);
+  const double beta = ext ? xcpar().c_beta : 0.06672455060314922;
+  const double gamma = ext ? xcpar().c_gamma : (1.0 - 0.6931471805599453) / (HFG_PI * HFG_PI);
   const double B = beta / gamma;
-  const double BB = ext ? c_xcpar.c_BB : 1.0;
+  const double BB = ext ? xcpar().c_BB : 1.0;
   T ec = pol_eps_pw(rs, z, true);
   T phi = 0.5 * (tpow23(1.0 + z) + tpow23(1.0 - z));
   T phi3 = phi * phi * phi;
@@ -542,7 +553,7 @@ __host__ __device__ inline void eval_add_pol_basic(int id, double ra, double rb,
     Dual sa = mk(4.0 * saa, 0.0, 1.0), sb = mk(4.0 * sbb, 0.0, 1.0);
     Dual ea, eb;
     switch (id) {
-      case 1: ea = c_xcpar.x_alpha * eps_lda_x(a); eb = c_xcpar.x_alpha * eps_lda_x(b); break;
+      case 1: ea = xcpar().x_alpha * eps_lda_x(a); eb = xcpar().x_alpha * eps_lda_x(b); break;
       case 546: ea = eps_lda_x_sr(a, 0.3, 2); eb = eps_lda_x_sr(b, 0.3, 2); break;
       case 641: ea = eps_lda_x_sr(a, 0.3, 1); eb = eps_lda_x_sr(b, 0.3, 1); break;
       case -178: ea = eps_cam_lda0_x(a); eb = eps_cam_lda0_x(b); break;
@@ -758,6 +769,234 @@ __host__ __device__ inline void eval_add_mgga_pol(int id, double ra, double rb, 
   vsbb += en.d[4];
   vta += en.d[5];
   vtb += en.d[6];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Laplacian-dependent meta-GGAs (the atomic program's do_lapl path, src/atomic/dftgrid.cpp:105-120, 206-229, 557-571).
+// N-slot forward-mode duals: unpolarised slots (rho, sigma, tau, lapl); polarised slots (rho_a, rho_b, sigma_aa,
+// sigma_ab, sigma_bb, tau_a, tau_b, lapl_a, lapl_b).  tau is libxc's, 1/2 sum |grad phi|^2.
+// ---------------------------------------------------------------------------------------------------------
+template <int N>
+struct DN {
+  double v, d[N];
+};
+template <int N>
+__host__ __device__ inline DN<N> dn(double v) {
+  DN<N> r;
+  r.v = v;
+  for (int k = 0; k < N; k++) r.d[k] = 0.0;
+  return r;
+}
+template <int N>
+__host__ __device__ inline DN<N> dnvar(double v, int k) {
+  DN<N> r = dn<N>(v);
+  r.d[k] = 1.0;
+  return r;
+}
+/// f(x) with f'(x) = df
+template <int N>
+__host__ __device__ inline DN<N> dnf(const DN<N> &x, double f, double df) {
+  DN<N> r;
+  r.v = f;
+  for (int k = 0; k < N; k++) r.d[k] = df * x.d[k];
+  return r;
+}
+template <int N>
+__host__ __device__ inline DN<N> operator+(const DN<N> &x, const DN<N> &y) {
+  DN<N> r;
+  r.v = x.v + y.v;
+  for (int k = 0; k < N; k++) r.d[k] = x.d[k] + y.d[k];
+  return r;
+}
+template <int N>
+__host__ __device__ inline DN<N> operator-(const DN<N> &x, const DN<N> &y) {
+  DN<N> r;
+  r.v = x.v - y.v;
+  for (int k = 0; k < N; k++) r.d[k] = x.d[k] - y.d[k];
+  return r;
+}
+template <int N>
+__host__ __device__ inline DN<N> operator*(const DN<N> &x, const DN<N> &y) {
+  DN<N> r;
+  r.v = x.v * y.v;
+  for (int k = 0; k < N; k++) r.d[k] = x.d[k] * y.v + x.v * y.d[k];
+  return r;
+}
+template <int N>
+__host__ __device__ inline DN<N> operator/(const DN<N> &x, const DN<N> &y) {
+  const double inv = 1.0 / y.v, q = x.v * inv;
+  DN<N> r;
+  r.v = q;
+  for (int k = 0; k < N; k++) r.d[k] = (x.d[k] - q * y.d[k]) * inv;
+  return r;
+}
+template <int N>
+__host__ __device__ inline DN<N> operator+(const DN<N> &x, double c) { return dnf(x, x.v + c, 1.0); }
+template <int N>
+__host__ __device__ inline DN<N> operator+(double c, const DN<N> &x) { return dnf(x, x.v + c, 1.0); }
+template <int N>
+__host__ __device__ inline DN<N> operator-(const DN<N> &x, double c) { return dnf(x, x.v - c, 1.0); }
+template <int N>
+__host__ __device__ inline DN<N> operator-(double c, const DN<N> &x) { return dnf(x, c - x.v, -1.0); }
+template <int N>
+__host__ __device__ inline DN<N> operator*(const DN<N> &x, double c) { return dnf(x, x.v * c, c); }
+template <int N>
+__host__ __device__ inline DN<N> operator*(double c, const DN<N> &x) { return dnf(x, x.v * c, c); }
+template <int N>
+__host__ __device__ inline DN<N> operator/(const DN<N> &x, double c) { return x * (1.0 / c); }
+template <int N>
+__host__ __device__ inline DN<N> operator/(double c, const DN<N> &x) { return dnf(x, c / x.v, -c / (x.v * x.v)); }
+template <int N>
+__host__ __device__ inline DN<N> dncbrt(const DN<N> &x) {
+  const double c = cbrt(x.v);
+  return dnf(x, c, c / (3.0 * x.v));
+}
+template <int N>
+__host__ __device__ inline DN<N> dnexp(const DN<N> &x) {
+  const double e = exp(x.v);
+  return dnf(x, e, e);
+}
+template <int N>
+__host__ __device__ inline DN<N> dnexpm1(const DN<N> &x) { return dnf(x, expm1(x.v), exp(x.v)); }
+
+/// the root x of (x - 2) e^{2x/3} / x = u (Becke, Roussel, PRA 39, 3761 (1989), eq 21 with u = Q / ((2/3) pi^{2/3} rho^{5/3})).
+/// The left side increases from -inf (x -> 0) through 0 (x = 2) to +inf, so the root is unique: x in (0, 2) for u < 0, x > 2
+/// for u > 0.  Newton on F(x) = ln|x - 2| + 2x/3 - ln x - ln|u| (monotone on either branch), kept inside the bracket by
+/// bisection, to full precision.
+__host__ __device__ inline double br89_root(double u) {
+  if (u == 0.0) return 2.0;
+  const double lu = log(fabs(u));
+  const double sgn = u > 0.0 ? 1.0 : -1.0;  // sgn * F increases with x on the branch
+  double lo, hi, x;
+  if (u > 0.0) {
+    lo = 2.0;
+    hi = fmax(4.0, 1.5 * (lu + 0.6931471805599453) + 1.0);
+    x = fmin(2.0 + 2.0 * u * 0.26359713811572677, 0.5 * (lo + hi));  // 2 + 2 e^{-4/3} u near x = 2
+  } else {
+    lo = 0.0;
+    hi = 2.0;
+    x = 2.0 / (1.0 - u);
+  }
+  for (int it = 0; it < 200; it++) {
+    const double F = log(fabs(x - 2.0)) + x * (2.0 / 3.0) - log(x) - lu;
+    if (sgn * F > 0.0) hi = x;
+    else lo = x;
+    const double dF = 1.0 / (x - 2.0) + 2.0 / 3.0 - 1.0 / x;
+    double xn = x - F / dF;
+    if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
+    const bool done = fabs(xn - x) <= 2e-16 * xn || hi - lo <= 2e-16 * hi;
+    x = xn;
+    if (done) break;
+  }
+  return x;
+}
+
+/// Becke-Roussel 89 exchange of one spin channel as an energy per volume, (1/2) rho_s U_s with
+///   U_s = -(1 - e^{-x} - x e^{-x}/2) / b,  b = x e^{-x/3} / (8 pi rho_s)^{1/3},
+///   Q_s = (lapl_s - 2 gamma D_s)/6,  D_s = 2 tau_s - sigma_ss/(4 rho_s),  gamma = 0.8  (libxc mgga_x_br89 = 206).
+/// x depends on the point through u alone: its derivatives come from dx/du = 1 / (d/dx [(x-2) e^{2x/3}/x]), not from the
+/// iterations.
+template <int N>
+__host__ __device__ inline DN<N> br89_channel(const DN<N> &r, const DN<N> &s, const DN<N> &t, const DN<N> &l) {
+  const double gam = 0.8, c23 = (2.0 / 3.0) * 2.1450293971110255;  // (2/3) pi^{2/3}
+  DN<N> D = 2.0 * t - s / (4.0 * r);
+  DN<N> Q = (l - (2.0 * gam) * D) / 6.0;
+  DN<N> r13 = dncbrt(r);
+  DN<N> u = Q / (c23 * r * r13 * r13);
+  const double xv = br89_root(u.v);
+  const double dk = exp(xv * (2.0 / 3.0)) * 2.0 * (xv * xv - 2.0 * xv + 3.0) / (3.0 * xv * xv);
+  DN<N> x = dnf(u, xv, 1.0 / dk);
+  // (1 - e^{-x} - x e^{-x}/2) e^{x/3} / x, with 1 - e^{-x} = -expm1(-x) (small x: the bracket is x/2 + O(x^3))
+  DN<N> em = -1.0 * dnexpm1(-1.0 * x);
+  DN<N> ex3 = dnexp(x / 3.0);
+  DN<N> e23 = dnexp(x * (-2.0 / 3.0));
+  DN<N> g = (ex3 * em - 0.5 * x * e23) / x;
+  return (-0.5 * 2.9291837751230463) * r * r13 * g;  // (8 pi)^{1/3}
+}
+
+/// Colle-Salvetti correlation (Theor. Chim. Acta 37, 329 (1975)) in the form of Lee, Yang, Parr, PRB 37, 785 (1988), eq 1,
+/// energy per volume, with t_HF = tau - lapl/8 and t_W = sigma/(8 rho) - lapl/8 (libxc mgga_c_cs = 72):
+///   e = -a/(1 + d rho^{-1/3}) {rho + b rho^{-2/3} [t_HF - 2 t_W] e^{-c rho^{-1/3}}}.
+/// Replacing t_HF by its second-order gradient expansion C_F rho^{5/3} + t_W/9 + lapl/18 gives the LYP integrand before the
+/// integration by parts (their eq 3), which gga_c_lyp carries after it.
+template <int N>
+__host__ __device__ inline DN<N> cs_unpol(const DN<N> &r, const DN<N> &s, const DN<N> &t, const DN<N> &l) {
+  DN<N> rm13 = 1.0 / dncbrt(r);
+  DN<N> den = 1.0 + HFG_LYP_D * rm13;
+  DN<N> thf = t - l / 8.0, tw = s / (8.0 * r) - l / 8.0;
+  DN<N> br = HFG_LYP_B * rm13 * rm13 * (thf - 2.0 * tw) * dnexp((-HFG_LYP_C) * rm13);
+  return (-HFG_LYP_A) * (r + br) / den;
+}
+/// spin-resolved form (LYP eq 11 before their gradient expansion), gamma = 2 [1 - (rho_a^2 + rho_b^2)/rho^2]:
+///   e = -a gamma/(1 + d rho^{-1/3}) {rho + 2 b rho^{-5/3} [rho_a t_HF^a + rho_b t_HF^b - rho t_W] e^{-c rho^{-1/3}}},
+///   t_HF^s = tau_s - lapl_s/8,  t_W = sigma/(8 rho) - lapl/8 of the total density
+__host__ __device__ inline DN<9> cs_pol(const DN<9> &ra, const DN<9> &rb, const DN<9> &saa, const DN<9> &sab, const DN<9> &sbb,
+                                        const DN<9> &ta, const DN<9> &tb, const DN<9> &la, const DN<9> &lb) {
+  DN<9> n = ra + rb;
+  DN<9> rm13 = 1.0 / dncbrt(n);
+  DN<9> den = 1.0 + HFG_LYP_D * rm13;
+  DN<9> gam = 4.0 * ra * rb / (n * n);
+  DN<9> lt = la + lb;
+  DN<9> tw = (saa + 2.0 * sab + sbb) / (8.0 * n) - lt / 8.0;
+  DN<9> br = ra * (ta - la / 8.0) + rb * (tb - lb / 8.0) - n * tw;
+  DN<9> rm53 = rm13 * rm13 * rm13 * rm13 * rm13;
+  return (-HFG_LYP_A) * gam * (n + (2.0 * HFG_LYP_B) * rm53 * br * dnexp((-HFG_LYP_C) * rm13)) / den;
+}
+
+__host__ __device__ inline bool is_mgga_lapl(int id) { return id == 206 || id == 72; }
+
+/// adds a Laplacian-dependent meta-GGA's exc, vrho, vsigma, vtau, vlapl at one point (rho >= threshold assumed); live as in
+/// eval_add (the exchange channels carry rho/2 each)
+__host__ __device__ inline void eval_add_mgga_lapl(int id, double rho, double sigma, double tau, double lapl, bool live, double &exc,
+                                                   double &vrho, double &vsigma, double &vtau, double &vlapl) {
+  if (id == 206 && !live) return;
+  DN<4> r = dnvar<4>(rho, 0), s = dnvar<4>(sigma, 1), t = dnvar<4>(tau, 2), l = dnvar<4>(lapl, 3);
+  DN<4> en;
+  if (id == 206) en = 2.0 * br89_channel(0.5 * r, 0.25 * s, 0.5 * t, 0.5 * l);  // E_x[rho] = 2 e_x[rho/2]
+  else if (id == 72) en = cs_unpol(r, s, t, l);
+  else return;
+  exc += en.v / rho;
+  vrho += en.d[0];
+  vsigma += en.d[1];
+  vtau += en.d[2];
+  vlapl += en.d[3];
+}
+
+/// spin-polarised: adds exc (per particle of ra + rb), v_rho[2], v_sigma[3], v_tau[2], v_lapl[2]; ra, rb already raised to
+/// the threshold, live_a / live_b as in eval_add_mgga_pol.  BR89 is spin-resolved: E_x = sum_s e_x(channel s).
+__host__ __device__ inline void eval_add_mgga_lapl_pol(int id, double ra, double rb, double saa, double sab, double sbb, double ta,
+                                                       double tb, double la, double lb, bool live_a, bool live_b, double &exc,
+                                                       double &va, double &vb, double &vsaa, double &vsab, double &vsbb,
+                                                       double &vta, double &vtb, double &vla, double &vlb) {
+  const double rt = ra + rb;
+  if (id == 206) {
+    DN<4> ea = dn<4>(0.0), eb = dn<4>(0.0);
+    if (live_a) ea = br89_channel(dnvar<4>(ra, 0), dnvar<4>(saa, 1), dnvar<4>(ta, 2), dnvar<4>(la, 3));
+    if (live_b) eb = br89_channel(dnvar<4>(rb, 0), dnvar<4>(sbb, 1), dnvar<4>(tb, 2), dnvar<4>(lb, 3));
+    exc += (ea.v + eb.v) / rt;
+    va += ea.d[0];
+    vb += eb.d[0];
+    vsaa += ea.d[1];
+    vsbb += eb.d[1];
+    vta += ea.d[2];
+    vtb += eb.d[2];
+    vla += ea.d[3];
+    vlb += eb.d[3];
+    return;
+  }
+  if (id != 72) return;
+  DN<9> en = cs_pol(dnvar<9>(ra, 0), dnvar<9>(rb, 1), dnvar<9>(saa, 2), dnvar<9>(sab, 3), dnvar<9>(sbb, 4), dnvar<9>(ta, 5),
+                    dnvar<9>(tb, 6), dnvar<9>(la, 7), dnvar<9>(lb, 8));
+  exc += en.v / rt;
+  va += en.d[0];
+  vb += en.d[1];
+  vsaa += en.d[2];
+  vsab += en.d[3];
+  vsbb += en.d[4];
+  vta += en.d[5];
+  vtb += en.d[6];
+  vla += en.d[7];
+  vlb += en.d[8];
 }
 
 }  // namespace xc

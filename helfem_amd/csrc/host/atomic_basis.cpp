@@ -98,6 +98,33 @@ static void reduced_lip(const LIPBasis &p, const Vec &x, Mat &g, Mat &dg) {
     }
 }
 
+// second derivative of g_i(x) = B_i(x)/(x-x_0): the Lagrange product without its (x - x_0) factor, differentiated twice
+static Mat reduced_lip_d2(const LIPBasis &p, const Vec &x) {
+  const Vec &x0 = p.x0;
+  const size_t np = x0.size();
+  Mat d2(x.size(), p.enabled.size());
+  for (size_t ix = 0; ix < x.size(); ix++)
+    for (size_t c = 0; c < p.enabled.size(); c++) {
+      size_t fi = p.enabled[c];
+      if (fi == 0) throw std::logic_error("reduced LIP needs the first function dropped");
+      double val = 0.0;
+      for (size_t d1 = 1; d1 < np; d1++) {
+        if (d1 == fi) continue;
+        for (size_t e2 = 1; e2 < d1; e2++) {
+          if (e2 == fi) continue;
+          double t = 1.0 / (x0[fi] - x0[0]);
+          for (size_t ip = 1; ip < np; ip++) {
+            if (ip == fi || ip == d1 || ip == e2) continue;
+            t *= (x[ix] - x0[ip]) / (x0[fi] - x0[ip]);
+          }
+          val += 2.0 * t / ((x0[fi] - x0[d1]) * (x0[fi] - x0[e2]));
+        }
+      }
+      d2(ix, c) = val;
+    }
+  return d2;
+}
+
 Mat TwoDBasis::get_bf(size_t iel) const {
   double sc = fem.scaling_factor(iel);
   if (iel == 0) {
@@ -130,6 +157,25 @@ Mat TwoDBasis::get_df(size_t iel) const {
       d(i, j) = (-f(i, j) * invr + d(i, j)) * invr;
     }
   return d;
+}
+
+Mat TwoDBasis::get_lf(size_t iel) const {
+  double sc = fem.scaling_factor(iel);
+  if (iel == 0) {
+    // the exact counterpart of the reference's Taylor branch (RadialBasis.cpp:711-714): g is a polynomial in r here
+    Mat d2 = reduced_lip_d2(fem.get_basis(0), xq);
+    for (auto &v : d2.d) v /= sc * sc * sc;
+    return d2;
+  }
+  // RadialBasis.cpp:716-726: ((2 f/r - 2 f')/r + f'')/r
+  Mat f = fem.eval_dnf(xq, 0, iel), d = fem.eval_dnf(xq, 1, iel), l = fem.eval_dnf(xq, 2, iel);
+  Vec r = get_r(iel);
+  for (size_t j = 0; j < f.n_cols; j++)
+    for (size_t i = 0; i < f.n_rows; i++) {
+      double invr = 1.0 / r[i];
+      l(i, j) = ((2.0 * f(i, j) * invr - 2.0 * d(i, j)) * invr + l(i, j)) * invr;
+    }
+  return l;
 }
 
 Vec TwoDBasis::get_wrad(size_t iel) const {

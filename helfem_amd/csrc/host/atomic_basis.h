@@ -74,6 +74,9 @@ struct TwoDBasis {
   /// B_n(r)/r and d/dr (B_n(r)/r) at the quadrature points of element iel (nq x Nprim(iel))
   Mat get_bf(size_t iel) const;
   Mat get_df(size_t iel) const;
+  /// d^2/dr^2 (B_n(r)/r) (RadialBasis::get_lf, libhelfem/src/RadialBasis.cpp:701-728); element 0 differentiates the reduced
+  /// polynomial twice, as get_bf / get_df
+  Mat get_lf(size_t iel) const;
   Vec get_wrad(size_t iel) const;
   Vec get_r(size_t iel) const { return fem.eval_coord(xq, iel); }
   /// per-element operands of the in-element two-electron integrals for the GPU (hip/tei_dev.hip), in the layout of

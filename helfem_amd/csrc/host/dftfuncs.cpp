@@ -17,7 +17,8 @@ const Known known[] = {{"lda_x", 1}, {"lda_c_vwn", 7}, {"lda_c_vwn_rpa", 8}, {"l
                        {"hyb_gga_xc_b3lyp", 402},  // 0.08 lda_x + 0.72 gga_x_b88 + 0.19 lda_c_vwn_rpa + 0.81 gga_c_lyp + 0.20 exact exchange
                        {"hyb_gga_xc_pbeh", 406},  // PBE0: 0.75 gga_x_pbe + gga_c_pbe + 0.25 exact exchange
                        {"mgga_x_tpss", 202}, {"mgga_c_tpss", 231}, {"lda_x_erf", 546}, {"lda_x_yukawa", 641},
-                       {"hyb_lda_xc_cam_lda0", 178}};  // CAM-LDA0: erfc range separation, omega = 1/3
+                       {"hyb_lda_xc_cam_lda0", 178},  // CAM-LDA0: erfc range separation, omega = 1/3
+                       {"mgga_x_br89", 206}, {"mgga_c_cs", 72}};  // Laplacian-dependent: atomic program only
 
 int find_func(const std::string &name) {
   if (name.empty()) throw std::runtime_error("empty functional name\n");
@@ -64,6 +65,8 @@ void is_range_separated(int x_func, bool &erf, bool &yukawa) {
   erf = (x_func == 178);
   yukawa = false;
 }
+
+bool needs_laplacian(int id) { return id == 206 || id == 72; }
 
 const char *xc_func_name(int id) {
   if (id == -1) return "HF";

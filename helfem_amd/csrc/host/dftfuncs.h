@@ -15,4 +15,6 @@ void range_separation(int x_func, double &omega, double &alpha, double &beta);
 /// which screened kernel the functional uses (reference: is_range_separated, dftfuncs.cpp:464)
 void is_range_separated(int x_func, bool &erf, bool &yukawa);
 const char *xc_func_name(int func_id);
+/// the functional depends on the density Laplacian (mgga_x_br89, mgga_c_cs): supported by the atomic program only
+bool needs_laplacian(int func_id);
 }  // namespace helfem

@@ -173,7 +173,9 @@ int hfg_rs_exchange(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *K);
  * Functional ids are libxc's: 1 lda_x, 7 lda_c_vwn, 12 lda_c_pw, 101 gga_x_pbe, 130 gga_c_pbe, 406 hyb_gga_xc_pbeh
  * (its 0.25 exact exchange is the caller's K), 202 mgga_x_tpss, 231 mgga_c_tpss (Ekin returns the integral of tau),
  * 13 lda_c_pw_mod, 546 lda_x_erf, 641 lda_x_yukawa (omega = 0.3, libxc's default), 178 hyb_lda_xc_cam_lda0 (DFT part;
- * the caller adds 0.5 K - 0.25 K_erfc(omega = 1/3)); <=0 none.  The spin-polarised entry takes the same ids. */
+ * the caller adds 0.5 K - 0.25 K_erfc(omega = 1/3)), 206 mgga_x_br89 and 72 mgga_c_cs (these two depend on the density
+ * Laplacian: atomic bases only, a diatomic basis fails with "Laplacian not implemented!"); <=0 none.  The spin-polarised
+ * entry takes the same ids. */
 int hfg_xc_fock(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *P, double *H, double *Exc,
                 double *Nel, double *Ekin, double dens_thr);
 /* void DFTGrid::eval_Fxc(x_func,x_pars,c_func,c_pars,Pa,Pb,Ha,Hb,Exc,Nel,Ekin,beta,thr)   dftgrid.h:181,
@@ -190,6 +192,20 @@ int hfg_xc_fock_ext(hfg_ctx *ctx, hfg_basis *basis, int x_func, const double *x_
 int hfg_xc_fock_pol_ext(hfg_ctx *ctx, hfg_basis *basis, int x_func, const double *x_pars, int n_x_pars, int c_func,
                         const double *c_pars, int n_c_pars, const double *Pa, const double *Pb, double *Ha, double *Hb,
                         double *Exc, double *Nel, double *Ekin, double dens_thr);
+/* Point evaluation of one functional on host arrays in libxc's xc_mgga_exc_vxc layout (no context, no device): nspin 1:
+ * rho, sigma, lapl, tau and exc, vrho, vsigma, vlapl, vtau one value per point; nspin 2: rho[2], sigma[3] (aa, ab, bb),
+ * lapl[2], tau[2] per point, vrho, vsigma, vlapl, vtau likewise, exc per particle of the total density.  The same code as
+ * the grid kernels, with their threshold rules (dens_thr; exchange channels below it are left out).  NULL inputs are
+ * zero, NULL outputs are skipped; functionals without sigma / tau / lapl dependence return zero for those potentials. */
+int hfg_xc_eval(int func_id, int nspin, int64_t np, const double *rho, const double *sigma, const double *lapl, const double *tau,
+                double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau, double dens_thr);
+/* --method parsing of the drivers (dftfuncs.cpp:64-118): "x-c" names or numeric ids -> libxc ids; and id -> name */
+int hfg_xc_func_ids(const char *method, int *x_func, int *c_func);
+const char *hfg_xc_func_name(int func_id);
+/* Radial tables of an atomic basis at the quadrature points of element iel (nquad x Nprim(iel), column-major): which 0 =
+ * B/r (RadialBasis::get_bf), 1 = d/dr (B/r) (get_df), 2 = d^2/dr^2 (B/r) (get_lf), 3 = the radial coordinates
+ * (nquad x 1).  out = NULL returns the shape only. */
+int hfg_basis_radial_table(const hfg_basis *basis, int which, int iel, double *out, int64_t *rows, int64_t *cols);
 /* Initial-guess model potential: arma::mat TwoDGrid::model_potential(p1, p2) (src/diatomic/twodquadrature.cpp:351) on the
  * quadrature grid of hfg_basis_upload(ldft, mdft), or atomic::basis::TwoDBasis::model_potential(pot)
  * (src/atomic/TwoDBasis.cpp:458; the second centre is ignored).  kind: 0 point nucleus, 1 Green-Sellin-Zachor with the
