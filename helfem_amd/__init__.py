@@ -690,6 +690,16 @@ def xc_func_name(func_id):
     return f(int(func_id)).decode()
 
 
+def xc_exact_exchange(x_func):
+    """exact exchange the drivers add for an exchange id (hfg_xc_exact_exchange): (omega, alpha, beta) of
+    K = alpha K[1/r12] + beta K[screened kernel of range omega]"""
+    o, a, b = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    f = lib().hfg_xc_exact_exchange
+    f.argtypes = [ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 3
+    _check(f(int(x_func), ctypes.byref(o), ctypes.byref(a), ctypes.byref(b)))
+    return o.value, a.value, b.value
+
+
 def scf_set_iguess(iguess):
     """--iguess of the drivers for the following scf_* calls of this thread: 0 core Hamiltonian, 3 Thomas-Fermi"""
     _check(lib().hfg_scf_set_iguess(int(iguess)))

@@ -846,6 +846,13 @@ int hfg_xc_func_ids(const char *method, int *x_func, int *c_func) {
 
 const char *hfg_xc_func_name(int func_id) { return helfem::xc_func_name(func_id); }
 
+int hfg_xc_exact_exchange(int x_func, double *omega, double *alpha, double *beta) {
+  HFG_TRY
+  if (!omega || !alpha || !beta) throw std::logic_error("hfg_xc_exact_exchange: null argument\n");
+  helfem::range_separation(x_func, *omega, *alpha, *beta);
+  HFG_CATCH
+}
+
 int hfg_basis_radial_table(const hfg_basis *b, int which, int iel, double *out, int64_t *rows, int64_t *cols) {
   HFG_TRY
   if (!b || !rows || !cols) throw std::logic_error("hfg_basis_radial_table: null argument\n");

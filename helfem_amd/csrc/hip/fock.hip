@@ -20,6 +20,7 @@
 //    so results are bitwise reproducible run to run.
 #include "tables.h"
 #include "xc_device.h"
+#include "../host/dftfuncs.h"
 
 namespace hfg {
 
@@ -455,6 +456,9 @@ __global__ void k_xc_density_theta(const double *__restrict__ D0, const double *
 //    Laplacian (do_lapl, atomic dftgrid.cpp:105-120, 557-571): lapl = 2 (kin + lap) with kin = 2 tau and lap = sum_j V5 cos,
 //    the tau-type potential becomes w (vtau/2 + 2 vlapl), and Fo[5][..] = sum_j w vlapl cos(D phi_j) feeds the
 //    increment_mgga_lapl term
+//    EXT: the instantiation that also runs the xc::is_ext functionals (SCAN, SCAN0, PBEsol, revPBE); the host launches it
+//    only when one of the two ids is one of them, so the instantiation for every other functional keeps its code
+template <bool EXT>
 __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict__ rad_w,
                           const double *__restrict__ rad_sh, const double *__restrict__ th_s,
                           const double *__restrict__ th_w, const int *__restrict__ grp_m,
@@ -527,12 +531,14 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
       const bool live = 0.5 * rho >= thr;  // the spin channels of the exchange sum carry rho/2 each
       const double lapl = 2.0 * (2.0 * tau + lap);
       if (x_func > 0) {
-        if (xc::is_mgga_lapl(x_func)) xc::eval_add_mgga_lapl(x_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
+        if (EXT && xc::is_ext(x_func)) xc::eval_add_ext(x_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
+        else if (xc::is_mgga_lapl(x_func)) xc::eval_add_mgga_lapl(x_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
         else if (xc::is_mgga(x_func)) xc::eval_add_mgga(x_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
         else xc::eval_add(x_func, rho, sigma, live, exc, vrho, vsig);
       }
       if (c_func > 0) {
-        if (xc::is_mgga_lapl(c_func)) xc::eval_add_mgga_lapl(c_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
+        if (EXT && xc::is_ext(c_func)) xc::eval_add_ext(c_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
+        else if (xc::is_mgga_lapl(c_func)) xc::eval_add_mgga_lapl(c_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
         else if (xc::is_mgga(c_func)) xc::eval_add_mgga(c_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
         else xc::eval_add(c_func, rho, sigma, live, exc, vrho, vsig);
       }
@@ -625,6 +631,8 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
 
 // X3 for a spin-polarised density (DFTGridWorker::update_density(Pa,Pb), compute_xc, eval_Fxc(Ha,Hb,beta);
 //    dftgrid.cpp:119-170, 343-458, 547-613): V and Fo hold the alpha planes (0..2) followed by the beta planes (3..5).
+//    EXT as in k_xc_grid.
+template <bool EXT>
 __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__restrict__ rad_w,
                               const double *__restrict__ rad_sh, const double *__restrict__ th_s,
                               const double *__restrict__ th_w, const int *__restrict__ grp_m,
@@ -715,7 +723,9 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
       for (int f = 0; f < 2; f++) {
         const int id = f ? c_func : x_func;
         if (id <= 0) continue;
-        if (xc::is_mgga_lapl(id))
+        if (EXT && xc::is_ext(id))
+          xc::eval_add_ext_pol(id, ra, rb, saa, sab, sbb, tau[0], tau[1], rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa, vsab, vsbb, vta, vtb);
+        else if (xc::is_mgga_lapl(id))
           xc::eval_add_mgga_lapl_pol(id, ra, rb, saa, sab, sbb, tau[0], tau[1], la, lb, rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa,
                                      vsab, vsbb, vta, vtb, vla, vlb);
         else if (xc::is_mgga(id)) xc::eval_add_mgga_pol(id, ra, rb, saa, sab, sbb, tau[0], tau[1], rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa, vsab, vsbb, vta, vtb);
@@ -1334,11 +1344,17 @@ void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const do
                      NQ, ctx->shard_rank, ctx->shard_n, a.V.p);
   size_t shb = (size_t)((do_lapl ? 6 : 5) * nth * nphi + 3 * 4) * sizeof(double);
   if (do_lapl && shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the grid kernel's LDS planes");
-  if (shb > 64 * 1024)
-    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_grid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  hipLaunchKernelGGL(k_xc_grid, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
-                     t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
-                     x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p);
+  const bool ext = (x_func > 0 && xc::is_ext(x_func)) || (c_func > 0 && xc::is_ext(c_func));
+  const void *kgrid = ext ? (const void *)k_xc_grid<true> : (const void *)k_xc_grid<false>;
+  if (shb > 64 * 1024) HFG_HIP_CHECK(hipFuncSetAttribute(kgrid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
+  if (ext)
+    hipLaunchKernelGGL(k_xc_grid<true>, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
+                       t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
+                       x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p);
+  else
+    hipLaunchKernelGGL(k_xc_grid<false>, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
+                       t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
+                       x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p);
   launch_xc_fock_theta(ctx, NQ, G, nth, maxgrp, a.Fo.p, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, do_grad, do_tau, ctx->shard_rank,
                        ctx->shard_n, a.GA.p, a.GB.p, a.GC.p, do_lapl, a.GL.p);
   hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))), xc_fock_radial_lds(p, nq, do_lapl),
@@ -1353,25 +1369,20 @@ void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const do
 /// else throws (std::runtime_error, as libxc's "number of parameters" check does through the reference).
 void set_xc_params(hfg_ctx *ctx, int x_func, const double *x_pars, int nx, int c_func, const double *c_pars, int nc) {
   xc::XCPar par = HFG_XCPAR_DEFAULTS;
+  if (nx > 0 && !x_pars) throw std::runtime_error("Exchange functional parameters missing.\n");
+  if (nc > 0 && !c_pars) throw std::runtime_error("Correlation functional parameters missing.\n");
+  helfem::check_xc_params(x_func, nx, c_func, nc);
   if (nx > 0) {
-    if (!x_pars) throw std::runtime_error("Exchange functional parameters missing.\n");
-    if (x_func == 1 && nx == 1) par.x_alpha = x_pars[0];
-    else if (x_func == 101 && nx == 2) {
+    if (x_func == 1) par.x_alpha = x_pars[0];
+    else {
       par.x_kappa = x_pars[0];
       par.x_mu = x_pars[1];
-    } else
-      throw std::runtime_error("External parameters are not supported for exchange functional " + std::to_string(x_func) + " with " +
-                               std::to_string(nx) + " values (supported: lda_x {alpha}, gga_x_pbe {kappa, mu}).\n");
+    }
   }
   if (nc > 0) {
-    if (!c_pars) throw std::runtime_error("Correlation functional parameters missing.\n");
-    if (c_func == 130 && nc == 3) {
-      par.c_beta = c_pars[0];
-      par.c_gamma = c_pars[1];
-      par.c_BB = c_pars[2];
-    } else
-      throw std::runtime_error("External parameters are not supported for correlation functional " + std::to_string(c_func) + " with " +
-                               std::to_string(nc) + " values (supported: gga_c_pbe {beta, gamma, BB}).\n");
+    par.c_beta = c_pars[0];
+    par.c_gamma = c_pars[1];
+    par.c_BB = c_pars[2];
   }
   // the host copy must stay valid until the asynchronous copy has run: a small per-thread ring
   static thread_local xc::XCPar staged[8];
@@ -1402,7 +1413,8 @@ void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double 
       double e = 0.0, vr = 0.0, vs = 0.0, vt = 0.0, vl = 0.0;
       if (r >= thr && r > 0.0) {
         const bool live = 0.5 * r >= thr;
-        if (xc::is_mgga_lapl(id)) xc::eval_add_mgga_lapl(id, r, s, t, l, live, e, vr, vs, vt, vl);
+        if (xc::is_ext(id)) xc::eval_add_ext(id, r, s, t, live, e, vr, vs, vt);
+        else if (xc::is_mgga_lapl(id)) xc::eval_add_mgga_lapl(id, r, s, t, l, live, e, vr, vs, vt, vl);
         else if (xc::is_mgga(id)) xc::eval_add_mgga(id, r, s, t, live, e, vr, vs, vt);
         else xc::eval_add(id, r, s, live, e, vr, vs);
         if (!std::isfinite(vl)) vl = 0.0;
@@ -1420,7 +1432,9 @@ void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double 
       const double ra = std::max(r0, thr), rb = std::max(r1, thr);
       const double saa = in(sigma, 3 * i), sab = in(sigma, 3 * i + 1), sbb = in(sigma, 3 * i + 2);
       const double ta = in(tau, 2 * i), tb = in(tau, 2 * i + 1), la = in(lapl, 2 * i), lb = in(lapl, 2 * i + 1);
-      if (xc::is_mgga_lapl(id))
+      if (xc::is_ext(id))
+        xc::eval_add_ext_pol(id, ra, rb, saa, sab, sbb, ta, tb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb, vta, vtb);
+      else if (xc::is_mgga_lapl(id))
         xc::eval_add_mgga_lapl_pol(id, ra, rb, saa, sab, sbb, ta, tb, la, lb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb, vta, vtb,
                                    vla, vlb);
       else if (xc::is_mgga(id))
@@ -1509,11 +1523,17 @@ void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, cons
   while ((size_t)(npot2 * rowc * nphi + 3 * 4) * sizeof(double) > xc_lds_limit() && rowc > 1) rowc = (rowc + 1) / 2;
   size_t shb = (size_t)(npot2 * rowc * nphi + 3 * 4) * sizeof(double);
   if (shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the polarised grid kernel's LDS tile");
-  if (shb > 64 * 1024)
-    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_grid_pol, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  hipLaunchKernelGGL(k_xc_grid_pol, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
-                     t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
-                     x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, rowc);
+  const bool ext = (x_func > 0 && xc::is_ext(x_func)) || (c_func > 0 && xc::is_ext(c_func));
+  const void *kgrid = ext ? (const void *)k_xc_grid_pol<true> : (const void *)k_xc_grid_pol<false>;
+  if (shb > 64 * 1024) HFG_HIP_CHECK(hipFuncSetAttribute(kgrid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
+  if (ext)
+    hipLaunchKernelGGL(k_xc_grid_pol<true>, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
+                       t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
+                       x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, rowc);
+  else
+    hipLaunchKernelGGL(k_xc_grid_pol<false>, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
+                       t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
+                       x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, rowc);
   for (int sp = 0; sp < 2; sp++) {
     launch_xc_fock_theta(ctx, NQ, G, nth, maxgrp, a.Fo.p + (size_t)sp * npl * nv, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, do_grad,
                          do_tau, ctx->shard_rank, ctx->shard_n, a.GA.p, a.GB.p, a.GC.p, do_lapl, a.GL.p);

@@ -522,6 +522,7 @@ static void check_options(const hfg_scf_options &p) {
   if (p.program == 0 && (erf || yuk)) throw std::logic_error("Range separated functionals are not supported.\n");  // diatomic/main.cpp:393
   if (p.program == 0 && (helfem::needs_laplacian(x_func) || helfem::needs_laplacian(c_func)))
     throw std::logic_error("Laplacian not implemented!\n");  // diatomic dftgrid.cpp:115-116
+  helfem::check_xc_params(x_func, p.n_x_pars, c_func, p.n_c_pars);  // before the device: the refusal of set_xc_params
   int nela = p.nela, nelb = p.nelb, Q = p.Q, M = p.M > 0 ? p.M : 1;
   helfem::scf::parse_nela_nelb(nela, nelb, Q, M, p.program == 0 ? p.Z1 + p.Z2 : p.Z1);
   if (nela + nelb <= 0) throw std::logic_error("No electrons.\n");

@@ -213,9 +213,12 @@ __host__ __device__ inline Dual eps_lda_c_pw(Dual rho) {
   return eps_pw92(dcbrt(3.0 / (4.0 * HFG_PI) / rho), false);
 }
 
-__host__ __device__ inline Dual eps_gga_x_pbe(Dual rho, Dual sigma) {
-  const double kappa = xcpar().x_kappa;
-  const double mu = xcpar().x_mu;
+// PBE exchange with explicit (kappa, mu): gga_x_pbe (101) passes the external parameters of xcpar(), gga_x_pbe_r (revPBE,
+// 102; Zhang, Yang, PRL 80, 890 (1998)) kappa = 1.245 with PBE's mu, gga_x_pbe_sol (116; Perdew et al., PRL 100, 136406
+// (2008)) kappa = 0.804, mu = 10/81
+#define HFG_PBE_MU (0.06672455060314922 * HFG_PI * HFG_PI / 3.0)
+#define HFG_PBE_GAMMA ((1.0 - 0.6931471805599453) / (HFG_PI * HFG_PI))
+__host__ __device__ inline Dual eps_gga_x_pbe(Dual rho, Dual sigma, double kappa, double mu) {
   Dual exu = eps_lda_x(rho);
   Dual kf = dcbrt((3.0 * HFG_PI * HFG_PI) * rho);
   Dual s2 = sigma / (4.0 * kf * kf * rho * rho);
@@ -223,11 +226,9 @@ __host__ __device__ inline Dual eps_gga_x_pbe(Dual rho, Dual sigma) {
   return exu * Fx;
 }
 
-__host__ __device__ inline Dual eps_gga_c_pbe(Dual rho, Dual sigma) {
-  const double beta = xcpar().c_beta;
-  const double gamma = xcpar().c_gamma;
+// PBE correlation with explicit (beta, gamma, BB): gga_c_pbe (130) passes xcpar(), gga_c_pbe_sol (133) beta = 0.046
+__host__ __device__ inline Dual eps_gga_c_pbe(Dual rho, Dual sigma, double beta, double gamma, double BB) {
   const double B = beta / gamma;
-  const double BB = xcpar().c_BB;
   Dual rs = dcbrt(3.0 / (4.0 * HFG_PI) / rho);
   Dual ec = eps_pw92(rs, true);
   Dual kf = dcbrt((3.0 * HFG_PI * HFG_PI) * rho);
@@ -243,14 +244,17 @@ __host__ __device__ inline Dual eps_gga_c_pbe(Dual rho, Dual sigma) {
 
 __host__ __device__ inline bool is_gga(int id) {
   return id == 101 || id == 130 || id == 406 || id == 202 || id == 231 || id == 106 || id == 131 || id == 402 || id == 206 ||
-         id == 72;
+         id == 72 || id == 102 || id == 116 || id == 133 || id == 263 || id == 264 || id == 267;
 }
 __host__ __device__ inline bool is_supported(int id) {
   return id == 1 || id == 7 || id == 8 || id == 12 || id == 13 || id == 101 || id == 130 || id == 406 || id == 202 || id == 231 ||
-         id == 546 || id == 641 || id == 178 || id == 106 || id == 131 || id == 402 || id == 206 || id == 72;
+         id == 546 || id == 641 || id == 178 || id == 106 || id == 131 || id == 402 || id == 206 || id == 72 || id == 102 || id == 116 ||
+         id == 133 || id == 263 || id == 264 || id == 267;
 }
 
-__host__ __device__ inline bool is_exchange(int id) { return id == 1 || id == 101 || id == 546 || id == 641 || id == 202 || id == 106; }
+__host__ __device__ inline bool is_exchange(int id) {
+  return id == 1 || id == 101 || id == 546 || id == 641 || id == 202 || id == 106 || id == 102 || id == 116 || id == 263 || id == 264;
+}
 
 /// adds functional id's exc (per particle), vrho, vsigma at one point; rho >= threshold assumed.
 /// live: the density of one spin channel, rho/2, reaches the threshold.  Exchange is a sum over the spin channels and
@@ -274,9 +278,11 @@ __host__ __device__ inline void eval_add(int id, double rho, double sigma, bool 
     case 546: e = eps_lda_x_sr(r, 0.3, 2); break;                          // lda_x_erf, libxc default omega
     case 641: e = eps_lda_x_sr(r, 0.3, 1); break;                          // lda_x_yukawa, libxc default omega
     case 178: e = eps_cam_lda0_x(r) + eps_pw92(dcbrt(3.0 / (4.0 * HFG_PI) / r), true); break;  // hyb_lda_xc_cam_lda0, DFT part
-    case 101: e = eps_gga_x_pbe(r, s); break;
-    case 130: e = eps_gga_c_pbe(r, s); break;
-    case 406: e = 0.75 * eps_gga_x_pbe(r, s) + eps_gga_c_pbe(r, s); break;  // hyb_gga_xc_pbeh (PBE0), DFT part
+    case 101: e = eps_gga_x_pbe(r, s, xcpar().x_kappa, xcpar().x_mu); break;
+    case 130: e = eps_gga_c_pbe(r, s, xcpar().c_beta, xcpar().c_gamma, xcpar().c_BB); break;
+    case 406:  // hyb_gga_xc_pbeh (PBE0), DFT part
+      e = 0.75 * eps_gga_x_pbe(r, s, xcpar().x_kappa, xcpar().x_mu) + eps_gga_c_pbe(r, s, xcpar().c_beta, xcpar().c_gamma, xcpar().c_BB);
+      break;  // hyb_gga_xc_pbeh (PBE0), DFT part
     case 8: e = eps_lda_c_vwn_rpa(r); break;
     case 106: e = eps_gga_x_b88(r, s); break;
     case 131: e = eps_gga_c_lyp(r, s); break;
@@ -475,12 +481,10 @@ __host__ __device__ inline T pol_eps_pw(T rs, T z, bool mod) {
   return e0 - mac * f * (1.0 - z4) / fz20 + (e1 - e0) * f * z4;
 }
 template <class T>
-__host__ __device__ inline T pol_eps_pbe_c(T n, T rs, T z, T sig, bool ext = false) {
-  // ext: the stand-alone gga_c_pbe takes the external parameters; TPSS's inner PBE keeps the published constants
-  const double beta = ext ? xcpar().c_beta : 0.06672455060314922;
-  const double gamma = ext ? xcpar().c_gamma : (1.0 - 0.6931471805599453) / (HFG_PI * HFG_PI);
+__host__ __device__ inline T pol_eps_pbe_c(T n, T rs, T z, T sig, double beta, double gamma, double BB) {
+  // the stand-alone gga_c_pbe passes the external parameters, gga_c_pbe_sol beta = 0.046; TPSS's inner PBE the published
+  // constants
   const double B = beta / gamma;
-  const double BB = ext ? xcpar().c_BB : 1.0;
   T ec = pol_eps_pw(rs, z, true);
   T phi = 0.5 * (tpow23(1.0 + z) + tpow23(1.0 - z));
   T phi3 = phi * phi * phi;
@@ -558,7 +562,7 @@ __host__ __device__ inline void eval_add_pol_basic(int id, double ra, double rb,
       case 641: ea = eps_lda_x_sr(a, 0.3, 1); eb = eps_lda_x_sr(b, 0.3, 1); break;
       case -178: ea = eps_cam_lda0_x(a); eb = eps_cam_lda0_x(b); break;
       case 106: ea = eps_gga_x_b88(a, sa); eb = eps_gga_x_b88(b, sb); break;
-      default: ea = eps_gga_x_pbe(a, sa); eb = eps_gga_x_pbe(b, sb); break;
+      default: ea = eps_gga_x_pbe(a, sa, xcpar().x_kappa, xcpar().x_mu); eb = eps_gga_x_pbe(b, sb, xcpar().x_kappa, xcpar().x_mu); break;
     }
     Dual na = a * ea, nb = b * eb;  // energy per volume of the doubled densities
     if (!live_a) na = mk(0.0, 0.0, 0.0);
@@ -580,7 +584,7 @@ __host__ __device__ inline void eval_add_pol_basic(int id, double ra, double rb,
     case 8: e = pol_eps_vwn_rpa(rs, z); break;
     case 12: e = pol_eps_pw(rs, z, false); break;
     case 13: e = pol_eps_pw(rs, z, true); break;
-    case 130: e = pol_eps_pbe_c(n, rs, z, st, true); break;
+    case 130: e = pol_eps_pbe_c(n, rs, z, st, xcpar().c_beta, xcpar().c_gamma, xcpar().c_BB); break;
     default: return;
   }
   T3 en = n * e;
@@ -678,7 +682,7 @@ __host__ __device__ inline T7 mg_eps_tpss_c_pol(T7 ra, T7 rb, T7 saa, T7 sab, T7
   T7 rs = tcbrt((3.0 / (4.0 * HFG_PI)) / n);
   T7 zeta = (ra - rb) / n;
   T7 st = saa + 2.0 * sab + sbb;
-  T7 epbe = pol_eps_pbe_c(n, rs, zeta, st);
+  T7 epbe = pol_eps_pbe_c(n, rs, zeta, st, 0.06672455060314922, HFG_PBE_GAMMA, 1.0);
   T7 eta = tmaxv(mg_eps_pbe_c_fullpol(ra, saa), epbe);
   T7 etb = tmaxv(mg_eps_pbe_c_fullpol(rb, sbb), epbe);
   T7 tauw = st / (8.0 * n);
@@ -701,7 +705,7 @@ __host__ __device__ inline T7 mg_eps_tpss_c_pol(T7 ra, T7 rb, T7 saa, T7 sab, T7
 __host__ __device__ inline T3 mg_eps_tpss_c(T3 rho, T3 sig, T3 tau) {
   const double d = 2.8, C0 = 0.53;
   T3 rs = tcbrt((3.0 / (4.0 * HFG_PI)) / rho);
-  T3 epbe = pol_eps_pbe_c(rho, rs, t3(0.0), sig);
+  T3 epbe = pol_eps_pbe_c(rho, rs, t3(0.0), sig, 0.06672455060314922, HFG_PBE_GAMMA, 1.0);
   T3 esig = mg_eps_pbe_c_fullpol(0.5 * rho, 0.25 * sig);
   T3 etil = tmaxv(esig, epbe);
   T3 tauw = sig / (8.0 * rho);
@@ -712,7 +716,8 @@ __host__ __device__ inline T3 mg_eps_tpss_c(T3 rho, T3 sig, T3 tau) {
   return rev * (1.0 + d * rev * z2 * z);
 }
 
-__host__ __device__ inline bool is_mgga(int id) { return id == 202 || id == 231; }
+/// tau-dependent (SCAN's ids included: the grid kernels run them in their is_ext instantiation, below)
+__host__ __device__ inline bool is_mgga(int id) { return id == 202 || id == 231 || id == 263 || id == 264 || id == 267; }
 
 /// adds a meta-GGA's exc, vrho, vsigma, vtau at one point (rho >= threshold assumed)
 __host__ __device__ inline void eval_add_mgga(int id, double rho, double sigma, double tau, bool live, double &exc,
@@ -761,6 +766,242 @@ __host__ __device__ inline void eval_add_mgga_pol(int id, double ra, double rb, 
   T7 Ta = t7var(fmax(ta, 1e-40), 5), Tb = t7var(fmax(tb, 1e-40), 6);
   T7 e = mg_eps_tpss_c_pol(A, B, Saa, Sab, Sbb, Ta, Tb);
   T7 en = (A + B) * e;
+  exc += e.v;
+  va += en.d[0];
+  vb += en.d[1];
+  vsaa += en.d[2];
+  vsab += en.d[3];
+  vsbb += en.d[4];
+  vta += en.d[5];
+  vtb += en.d[6];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// SCAN (Sun, Ruzsinszky, Perdew, PRL 115, 036402 (2015), and its supplement): mgga_x_scan (libxc 263), mgga_c_scan (267),
+// hyb_mgga_x_scan0 (264: 0.75 SCAN exchange + 0.25 exact exchange over the full range); and the PBE variants with fixed
+// constants, gga_x_pbe_r (102), gga_x_pbe_sol (116), gga_c_pbe_sol (133).  These six ids (is_ext) are evaluated by
+// eval_add_ext / eval_add_ext_pol alone, which the grid kernels call only in a separate instantiation (fock.hip): the code
+// that runs every other functional is what it was.
+// Shared quantities (tau is libxc's, 1/2 sum |grad phi|^2):
+//   p = s^2 = sigma / (4 (3 pi^2)^{2/3} n^{8/3}),  tau_W = sigma/(8n),  alpha = (tau - tau_W)/tau_unif,
+//   tau_unif = (3/10)(3 pi^2)^{2/3} n^{5/3} d_s(zeta),  d_s = [(1+zeta)^{5/3} + (1-zeta)^{5/3}]/2
+// Exchange (unpolarised; polarised by spin scaling, E_x[a,b] = (E_x[2a] + E_x[2b])/2, as TPSS):
+//   F_x = {h1 + f_x(alpha) (h0 - h1)} g_x(s),  h0 = 1.174,  h1 = 1 + k1 - k1/(1 + x/k1),  k1 = 0.065,
+//   x = mu p [1 + (b4 p/mu) exp(-|b4| p/mu)] + [b1 p + b2 (1 - alpha) exp(-b3 (1 - alpha)^2)]^2,
+//   mu = 10/81, b2 = sqrt(5913/405000), b1 = (511/13500)/(2 b2), b3 = 1/2, b4 = mu^2/k1 - 1606/18225 - b1^2,
+//   f(alpha) = exp(-c1 alpha/(1 - alpha)) for alpha < 1, -d exp(c2/(1 - alpha)) for alpha > 1; f_x: (c1, c2, d) = (0.667, 0.8, 1.24)
+//   g_x = 1 - exp(-a1/sqrt(s)) = 1 - exp(-a1 p^{-1/4}),  a1 = 4.9479
+// Correlation (n, zeta, p, alpha of the total density, tau = tau_a + tau_b):
+//   e_c = e_c1 + f_c(alpha) (e_c0 - e_c1),  f_c: (c1, c2, d) = (0.64, 1.5, 0.7)
+//   e_c1 = e_LSDA + H1, e_LSDA = PW92 as in PBE (pol_eps_pw, modified), H1 = gamma phi^3 ln[1 + w1 (1 - (1 + 4 A t^2)^{-1/4})],
+//   w1 = exp(-e_LSDA/(gamma phi^3)) - 1, A = beta(rs)/(gamma w1), beta(rs) = 0.066725 (1 + 0.1 rs)/(1 + 0.1778 rs),
+//   gamma = (1 - ln 2)/pi^2, phi = [(1+zeta)^{2/3} + (1-zeta)^{2/3}]/2, t^2 = (3 pi^2/16)^{2/3} p/(phi^2 rs)
+//   e_c0 = (e_LDA0 + H0) G_c(zeta), e_LDA0 = -b1c/(1 + b2c sqrt(rs) + b3c rs), (b1c, b2c, b3c) = (0.0285764, 0.0889, 0.125541),
+//   H0 = b1c ln[1 + w0 (1 - (1 + 4 chi p)^{-1/4})], w0 = exp(-e_LDA0/b1c) - 1, chi = 0.128026,
+//   G_c = [1 - 2.3631 (d_x(zeta) - 1)] (1 - zeta^12), d_x = [(1+zeta)^{4/3} + (1-zeta)^{4/3}]/2
+// Numerical rules:
+//   - f(alpha) has an essential singularity at alpha = 1, where all its derivatives vanish.  Once its exponent is below
+//     -700, value and derivative are exactly 0: the chain rule would give 0 * inf = NaN where 1 - alpha underflows.
+//   - tau below tau_W (rounding in one-orbital regions) is raised to tau_W (tmaxv, as TPSS does), so alpha >= 0.
+//   - g_x is differentiated in p: where exp(-a1 p^{-1/4}) underflows (p -> 0) it is 1 with a zero derivative, no sqrt(0).
+//   - (1 -+ zeta)^{2/3} in phi has an infinite zeta derivative at |zeta| = 1, which a density whose minority spin is at the
+//     threshold reaches in rounding: there (1 -+ zeta <= DBL_EPSILON) its derivative is taken as 0, as libxc's zeta
+//     threshold does.
+// ---------------------------------------------------------------------------------------------------------
+__host__ __device__ inline T3 tchain(T3 x, double f, double df) { return t3f(x, f, df); }
+__host__ __device__ inline T7 tchain(T7 x, double f, double df) { return t7f(x, f, df); }
+/// x^a, x > 0
+template <class T>
+__host__ __device__ inline T tpowr(T x, double a) {
+  const double v = pow(x.v, a);
+  return tchain(x, v, a * v / x.v);
+}
+/// x^{5/3}, differentiable at 0
+template <class T>
+__host__ __device__ inline T tpow53(T x) {
+  const double c = cbrt(x.v);
+  return tchain(x, x.v * c * c, (5.0 / 3.0) * c * c);
+}
+/// (1 -+ zeta)^{2/3} of phi, derivative 0 within DBL_EPSILON of zeta = +-1
+template <class T>
+__host__ __device__ inline T scan_opz23(T x) {
+  const double c = cbrt(x.v);
+  return tchain(x, c * c, x.v > 2.220446049250313e-16 ? 2.0 / (3.0 * c) : 0.0);
+}
+/// f_x / f_c of alpha (see above), exactly 0 with a zero derivative at alpha = 1 and wherever the exponent is below -700
+template <class T>
+__host__ __device__ inline T scan_switch(T alpha, double c1, double c2, double d) {
+  const double u = 1.0 - alpha.v;
+  double f = 0.0, df = 0.0;
+  if (u > 0.0) {
+    const double ex = -c1 * alpha.v / u;
+    if (ex > -700.0) {
+      f = exp(ex);
+      df = -c1 * f / (u * u);
+    }
+  } else if (u < 0.0) {
+    const double ex = c2 / u;
+    if (ex > -700.0) {
+      f = -d * exp(ex);
+      df = c2 * f / (u * u);
+    }
+  }
+  return tchain(alpha, f, df);
+}
+/// g_x = 1 - exp(-a1 p^{-1/4}) as a function of p = s^2
+template <class T>
+__host__ __device__ inline T scan_gx(T p) {
+  const double a1 = 4.9479;
+  if (!(p.v > 0.0)) return tchain(p, 1.0, 0.0);
+  const double q = 1.0 / sqrt(sqrt(p.v));  // 1/sqrt(s)
+  if (a1 * q > 700.0) return tchain(p, 1.0, 0.0);
+  const double e = exp(-a1 * q);
+  return tchain(p, 1.0 - e, -0.25 * a1 * e * q / p.v);
+}
+
+/// SCAN exchange energy per particle of an unpolarised density
+template <class T>
+__host__ __device__ inline T scan_eps_x(T rho, T sig, T tau) {
+  const double c32 = 9.570780000627305;  // (3 pi^2)^{2/3}
+  const double k1 = 0.065, h0 = 1.174, mu = 10.0 / 81.0, b3 = 0.5;
+  const double b2 = 0.12083045973594572, b1 = 0.15663207743548518, b4 = 0.12183151020599578;  // see above; b4 > 0
+  T exu = (-0.75 * cbrt(3.0 / HFG_PI)) * tcbrt(rho);
+  T rho23 = tpow23(rho);
+  T p = sig / ((4.0 * c32) * rho * rho * rho23);
+  T tauw = sig / (8.0 * rho);
+  T alpha = (tmaxv(tau, tauw) - tauw) / ((0.3 * c32) * rho * rho23);
+  T oma = 1.0 - alpha;
+  T bx = b1 * p + b2 * oma * texp((-b3) * oma * oma);
+  T x = mu * p * (1.0 + (b4 / mu) * p * texp((-b4 / mu) * p)) + bx * bx;
+  T h1 = (1.0 + k1) - k1 / (1.0 + x / k1);
+  T F = (h1 + scan_switch(alpha, 0.667, 0.8, 1.24) * (h0 - h1)) * scan_gx(p);
+  return exu * F;
+}
+
+/// SCAN correlation energy per particle; z = zeta, sig = |grad n|^2, tau = tau_a + tau_b
+template <class T>
+__host__ __device__ inline T scan_eps_c(T n, T z, T sig, T tau) {
+  const double c32 = 9.570780000627305, ct2 = 1.5073033983379012;  // (3 pi^2)^{2/3}, (3 pi^2/16)^{2/3}
+  const double gamma = HFG_PBE_GAMMA;
+  const double b1c = 0.0285764, b2c = 0.0889, b3c = 0.125541, chi = 0.128026;
+  T rs = tcbrt((3.0 / (4.0 * HFG_PI)) / n);
+  T opz = 1.0 + z, omz = 1.0 - z;
+  T n23 = tpow23(n);
+  T p = sig / ((4.0 * c32) * n * n * n23);
+  T ds = 0.5 * (tpow53(opz) + tpow53(omz));
+  T tauw = sig / (8.0 * n);
+  T alpha = (tmaxv(tau, tauw) - tauw) / ((0.3 * c32) * n * n23 * ds);
+  // e_c1: PW92 plus H1
+  T elsda = pol_eps_pw(rs, z, true);
+  T phi = 0.5 * (scan_opz23(opz) + scan_opz23(omz));
+  T gphi3 = gamma * phi * phi * phi;
+  T t2 = ct2 * p / (phi * phi * rs);
+  T w1 = texpm1(-elsda / gphi3);
+  T A = 0.066725 * (1.0 + 0.1 * rs) / ((1.0 + 0.1778 * rs) * (gamma * w1));
+  T ec1 = elsda + gphi3 * tlog1p(w1 * (1.0 - tpowr(1.0 + 4.0 * A * t2, -0.25)));
+  // e_c0: the alpha = 0 limit
+  T elda0 = (-b1c) / (1.0 + b2c * tsqrt(rs) + b3c * rs);
+  T w0 = texpm1(-elda0 / b1c);
+  T H0 = b1c * tlog1p(w0 * (1.0 - tpowr(1.0 + (4.0 * chi) * p, -0.25)));
+  T dx = 0.5 * (tpow43(opz) + tpow43(omz));
+  T z2 = z * z;
+  T z4 = z2 * z2;
+  T Gc = (1.0 - 2.3631 * (dx - 1.0)) * (1.0 - z4 * z4 * z4);
+  T ec0 = (elda0 + H0) * Gc;
+  return ec1 + scan_switch(alpha, 0.64, 1.5, 0.7) * (ec0 - ec1);
+}
+
+__host__ __device__ inline bool is_ext(int id) { return id == 263 || id == 264 || id == 267 || id == 102 || id == 116 || id == 133; }
+__host__ __device__ inline double ext_pbe_kappa(int id) { return id == 102 ? 1.245 : 0.804; }
+__host__ __device__ inline double ext_pbe_mu(int id) { return id == 102 ? HFG_PBE_MU : 10.0 / 81.0; }
+
+/// adds an is_ext functional's exc, vrho, vsigma, vtau at one point (rho >= threshold assumed; live as in eval_add).  The
+/// meta-GGA floors of eval_add_mgga (1e-40 under sigma and tau) apply to SCAN.
+__host__ __device__ inline void eval_add_ext(int id, double rho, double sigma, double tau, bool live, double &exc, double &vrho,
+                                             double &vsigma, double &vtau) {
+  if (!live && is_exchange(id)) return;
+  if (id == 102 || id == 116 || id == 133) {
+    Dual r = mk(rho, 1.0, 0.0), s = mk(sigma, 0.0, 1.0);
+    Dual e = id == 133 ? eps_gga_c_pbe(r, s, 0.046, HFG_PBE_GAMMA, 1.0) : eps_gga_x_pbe(r, s, ext_pbe_kappa(id), ext_pbe_mu(id));
+    Dual en = r * e;
+    exc += e.v;
+    vrho += en.dr;
+    vsigma += en.ds;
+    return;
+  }
+  T3 r = t3(rho, 1.0, 0.0, 0.0), s = t3(fmax(sigma, 1e-40), 0.0, 1.0, 0.0), t = t3(fmax(tau, 1e-40), 0.0, 0.0, 1.0);
+  T3 e = id == 267 ? scan_eps_c(r, t3(0.0), s, t) : scan_eps_x(r, s, t);
+  if (id == 264) e = 0.75 * e;  // hyb_mgga_x_scan0, DFT part
+  T3 en = r * e;
+  exc += e.v;
+  vrho += en.a;
+  vsigma += en.b;
+  vtau += en.s;
+}
+
+/// spin-polarised is_ext functional: adds exc (per particle of ra + rb), v_rho[2], v_sigma[3], v_tau[2]; ra, rb already raised
+/// to the threshold, live_a / live_b as in eval_add_mgga_pol
+__host__ __device__ inline void eval_add_ext_pol(int id, double ra, double rb, double saa, double sab, double sbb, double ta,
+                                                 double tb, bool live_a, bool live_b, double &exc, double &va, double &vb,
+                                                 double &vsaa, double &vsab, double &vsbb, double &vta, double &vtb) {
+  const double rt = ra + rb;
+  if (id == 102 || id == 116) {  // spin scaling, as gga_x_pbe in eval_add_pol_basic
+    Dual na = mk(0.0), nb = mk(0.0);
+    if (live_a) {
+      Dual a = mk(2.0 * ra, 1.0, 0.0);
+      na = a * eps_gga_x_pbe(a, mk(4.0 * saa, 0.0, 1.0), ext_pbe_kappa(id), ext_pbe_mu(id));
+    }
+    if (live_b) {
+      Dual b = mk(2.0 * rb, 1.0, 0.0);
+      nb = b * eps_gga_x_pbe(b, mk(4.0 * sbb, 0.0, 1.0), ext_pbe_kappa(id), ext_pbe_mu(id));
+    }
+    exc += 0.5 * (na.v + nb.v) / rt;
+    va += na.dr;
+    vb += nb.dr;
+    vsaa += 2.0 * na.ds;
+    vsbb += 2.0 * nb.ds;
+    return;
+  }
+  if (id == 133) {
+    T3 a = t3(ra, 1.0, 0.0, 0.0), b = t3(rb, 0.0, 1.0, 0.0), st = t3(saa + 2.0 * sab + sbb, 0.0, 0.0, 1.0);
+    T3 n = a + b;
+    T3 e = pol_eps_pbe_c(n, tcbrt((3.0 / (4.0 * HFG_PI)) / n), (a - b) / n, st, 0.046, HFG_PBE_GAMMA, 1.0);
+    T3 en = n * e;
+    exc += e.v;
+    va += en.a;
+    vb += en.b;
+    vsaa += en.s;
+    vsab += 2.0 * en.s;
+    vsbb += en.s;
+    return;
+  }
+  if (id == 263 || id == 264) {
+    const double w = id == 264 ? 0.75 : 1.0;
+    T3 na = t3(0.0), nb = t3(0.0);
+    if (live_a) {
+      T3 Ra = t3(2.0 * ra, 1.0, 0.0, 0.0), Sa = t3(fmax(4.0 * saa, 1e-40), 0.0, 1.0, 0.0), Ta = t3(fmax(2.0 * ta, 1e-40), 0.0, 0.0, 1.0);
+      na = w * (Ra * scan_eps_x(Ra, Sa, Ta));
+    }
+    if (live_b) {
+      T3 Rb = t3(2.0 * rb, 1.0, 0.0, 0.0), Sb = t3(fmax(4.0 * sbb, 1e-40), 0.0, 1.0, 0.0), Tb = t3(fmax(2.0 * tb, 1e-40), 0.0, 0.0, 1.0);
+      nb = w * (Rb * scan_eps_x(Rb, Sb, Tb));
+    }
+    exc += 0.5 * (na.v + nb.v) / rt;
+    va += na.a;  // d/d ra [ n(2 ra, 4 saa, 2 ta)/2 ]
+    vb += nb.a;
+    vsaa += 2.0 * na.b;
+    vsbb += 2.0 * nb.b;
+    vta += na.s;
+    vtb += nb.s;
+    return;
+  }
+  if (id != 267) return;
+  T7 A = t7var(ra, 0), B = t7var(rb, 1);
+  T7 Saa = t7var(fmax(saa, 1e-40), 2), Sab = t7var(sab, 3), Sbb = t7var(fmax(sbb, 1e-40), 4);
+  T7 Ta = t7var(fmax(ta, 1e-40), 5), Tb = t7var(fmax(tb, 1e-40), 6);
+  T7 n = A + B;
+  T7 e = scan_eps_c(n, (A - B) / n, Saa + 2.0 * Sab + Sbb, Ta + Tb);
+  T7 en = n * e;
   exc += e.v;
   va += en.d[0];
   vb += en.d[1];

@@ -18,7 +18,10 @@ const Known known[] = {{"lda_x", 1}, {"lda_c_vwn", 7}, {"lda_c_vwn_rpa", 8}, {"l
                        {"hyb_gga_xc_pbeh", 406},  // PBE0: 0.75 gga_x_pbe + gga_c_pbe + 0.25 exact exchange
                        {"mgga_x_tpss", 202}, {"mgga_c_tpss", 231}, {"lda_x_erf", 546}, {"lda_x_yukawa", 641},
                        {"hyb_lda_xc_cam_lda0", 178},  // CAM-LDA0: erfc range separation, omega = 1/3
-                       {"mgga_x_br89", 206}, {"mgga_c_cs", 72}};  // Laplacian-dependent: atomic program only
+                       {"mgga_x_br89", 206}, {"mgga_c_cs", 72},  // Laplacian-dependent: atomic program only
+                       {"mgga_x_scan", 263}, {"mgga_c_scan", 267},
+                       {"hyb_mgga_x_scan0", 264},  // 0.75 mgga_x_scan + 0.25 exact exchange
+                       {"gga_x_pbe_sol", 116}, {"gga_c_pbe_sol", 133}, {"gga_x_pbe_r", 102}};  // PBEsol, revPBE exchange
 
 int find_func(const std::string &name) {
   if (name.empty()) throw std::runtime_error("empty functional name\n");
@@ -46,7 +49,7 @@ void parse_xc_func(int &x_func, int &c_func, const std::string &xc) {
 
 // fraction of exact exchange (libxc xc_hyb_exx_coef; dftfuncs.cpp:134-160 of the reference)
 double exact_exchange(int x_func) {
-  return x_func == -1 ? 1.0 : (x_func == 406 ? 0.25 : (x_func == 402 ? 0.20 : (x_func == 178 ? 0.5 : 0.0)));
+  return x_func == -1 ? 1.0 : ((x_func == 406 || x_func == 264) ? 0.25 : (x_func == 402 ? 0.20 : (x_func == 178 ? 0.5 : 0.0)));
 }
 
 // libxc's xc_hyb_cam_coef / hyb_type of the range-separated hybrids available here (dftfuncs.cpp:464-570 of the
@@ -67,6 +70,15 @@ void is_range_separated(int x_func, bool &erf, bool &yukawa) {
 }
 
 bool needs_laplacian(int id) { return id == 206 || id == 72; }
+
+void check_xc_params(int x_func, int nx, int c_func, int nc) {
+  if (nx > 0 && !((x_func == 1 && nx == 1) || (x_func == 101 && nx == 2)))
+    throw std::runtime_error("External parameters are not supported for exchange functional " + std::to_string(x_func) + " with " +
+                             std::to_string(nx) + " values (supported: lda_x {alpha}, gga_x_pbe {kappa, mu}).\n");
+  if (nc > 0 && !(c_func == 130 && nc == 3))
+    throw std::runtime_error("External parameters are not supported for correlation functional " + std::to_string(c_func) + " with " +
+                             std::to_string(nc) + " values (supported: gga_c_pbe {beta, gamma, BB}).\n");
+}
 
 const char *xc_func_name(int id) {
   if (id == -1) return "HF";

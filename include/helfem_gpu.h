@@ -174,7 +174,9 @@ int hfg_rs_exchange(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *K);
  * (its 0.25 exact exchange is the caller's K), 202 mgga_x_tpss, 231 mgga_c_tpss (Ekin returns the integral of tau),
  * 13 lda_c_pw_mod, 546 lda_x_erf, 641 lda_x_yukawa (omega = 0.3, libxc's default), 178 hyb_lda_xc_cam_lda0 (DFT part;
  * the caller adds 0.5 K - 0.25 K_erfc(omega = 1/3)), 206 mgga_x_br89 and 72 mgga_c_cs (these two depend on the density
- * Laplacian: atomic bases only, a diatomic basis fails with "Laplacian not implemented!"); <=0 none.  The spin-polarised
+ * Laplacian: atomic bases only, a diatomic basis fails with "Laplacian not implemented!"), 263 mgga_x_scan, 267 mgga_c_scan,
+ * 264 hyb_mgga_x_scan0 (DFT part: 0.75 mgga_x_scan; the caller adds 0.25 K), 102 gga_x_pbe_r (revPBE), 116 gga_x_pbe_sol,
+ * 133 gga_c_pbe_sol; <=0 none.  The spin-polarised
  * entry takes the same ids. */
 int hfg_xc_fock(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *P, double *H, double *Exc,
                 double *Nel, double *Ekin, double dens_thr);
@@ -202,6 +204,9 @@ int hfg_xc_eval(int func_id, int nspin, int64_t np, const double *rho, const dou
 /* --method parsing of the drivers (dftfuncs.cpp:64-118): "x-c" names or numeric ids -> libxc ids; and id -> name */
 int hfg_xc_func_ids(const char *method, int *x_func, int *c_func);
 const char *hfg_xc_func_name(int func_id);
+/* Exact exchange the drivers add for an exchange id (range_separation, dftfuncs.cpp:505): K = alpha K[1/r12] + beta K[screened
+ * kernel of range omega]; 1 for HF, 0.25 for hyb_gga_xc_pbeh and hyb_mgga_x_scan0, 0 for the pure functionals */
+int hfg_xc_exact_exchange(int x_func, double *omega, double *alpha, double *beta);
 /* Radial tables of an atomic basis at the quadrature points of element iel (nquad x Nprim(iel), column-major): which 0 =
  * B/r (RadialBasis::get_bf), 1 = d/dr (B/r) (get_df), 2 = d^2/dr^2 (B/r) (get_lf), 3 = the radial coordinates
  * (nquad x 1).  out = NULL returns the shape only. */
