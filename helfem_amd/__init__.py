@@ -191,6 +191,15 @@ def default_context():
     return _default_ctx
 
 
+def tuning_table():
+    """the HELFEM_* environment switches of the native library (hfg_tuning_table; no device needed): a list of dicts with
+    name, kind, default, value (in this process), read ("once" per process or "live" at every use) and meaning"""
+    buf = ctypes.create_string_buffer(1 << 16)
+    _check(lib().hfg_tuning_table(buf, ctypes.c_size_t(len(buf))))
+    keys = ("name", "kind", "default", "value", "read", "meaning")
+    return [dict(zip(keys, line.split("\t"))) for line in buf.value.decode().split("\n") if line]
+
+
 def lm_to_l_m(lmmax):
     """diatomic::basis::lm_to_l_m (basis.cpp:287)."""
     lmmax = list(lmmax)

@@ -11,8 +11,10 @@
 #include "../../../include/helfem_gpu.h"
 #include "../host/atomic_basis.h"
 #include "../host/diatomic_basis.h"
+#include "../host/tuning.h"
 
 namespace hfg {
+using helfem::TrdMode, helfem::tuning;  // the HELFEM_* switches (host/tuning.h)
 
 void set_error(const std::string &msg);
 

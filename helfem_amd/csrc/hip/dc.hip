@@ -939,8 +939,7 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
     // workgroups per CU).  The small kernel below, which this call replaced, spent 68 % of its LDS cycles in bank
     // conflicts (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, profiles/r03_gemm_sq_counters_bench_step.txt): its B tile is
     // read along k and stored transposed.  HELFEM_DC_GEMM=small keeps it as the checker.
-    static const bool small_gemm = getenv("HELFEM_DC_GEMM") && !strcmp(getenv("HELFEM_DC_GEMM"), "small");
-    if (small_gemm) {
+    if (tuning().dc_gemm_small) {
       int tiles = ((mx + 63) / 64) * ((mx + 63) / 64);
       hipLaunchKernelGGL(k_dgemm_tasks, dim3(tiles, nn), dim3(256), 0, s, w.tasks.p);
     } else
@@ -953,8 +952,7 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
     hipLaunchKernelGGL(k_dc_copyback, dim3((mx + 255) / 256, mx, nn), dim3(256), 0, s, b, w.nodes.p, node0);
   }
   HFG_HIP_CHECK(hipGetLastError());
-  static const bool dbg = getenv("HELFEM_DC_DBG") != nullptr;  // merge statistics: order, secular roots, rotations
-  if (dbg) {
+  if (tuning().dc_dbg) {  // merge statistics: order, secular roots, rotations
     std::vector<int> hk(w.hnodes.size()), hr(w.hnodes.size());
     HFG_HIP_CHECK(hipMemcpyAsync(hk.data(), w.kcount.p, sizeof(int) * hk.size(), hipMemcpyDeviceToHost, s));
     HFG_HIP_CHECK(hipMemcpyAsync(hr.data(), w.nrot.p, sizeof(int) * hr.size(), hipMemcpyDeviceToHost, s));

@@ -897,11 +897,6 @@ static void bt_wy_setup(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, c
   }
 }
 
-static bool bt_use_side() {
-  static const bool v = (getenv("HELFEM_BT_SIDE") && atoi(getenv("HELFEM_BT_SIDE")) == 1);
-  return v;
-}
-
 static void bt_wy_prepare(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, int nmax, bool on_side = false) {
   const int P = (nmax - 3) / BT_KB + 1;
   // HELFEM_BT_SIDE=1 queues this part on a second stream beside the divide-and-conquer stage.  Measured: the 0.25 ms it
@@ -909,7 +904,7 @@ static void bt_wy_prepare(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk,
   // tridiagonalisation alone went from 17.4 to 19.1 ms), so the default keeps everything on the context's stream.
   // (Round 3: with X Q folded beside the divide-and-conquer stage -- bt_wy_fold_x, which needs these operands -- the set-up
   // goes to the side stream with it; the launch chain whose launches a second stream slowed is no longer the default.)
-  const bool use_side = (bt_use_side() && !ctx->avoid_side) || on_side;
+  const bool use_side = (tuning().bt_side && !ctx->avoid_side) || on_side;
   hipStream_t main = ctx->stream, q = main;
   const bool prof = ctx->profiling;
   if (use_side) {
@@ -941,8 +936,7 @@ static void bt_wy_apply(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, i
   const int P = (nmax - 3) / BT_KB + 1, NP = (P + 1) / 2;
   constexpr int BT_S = 6;
   double *const *dptr = w.btptr.p;
-  if (bt_use_side() && !ctx->avoid_side) HFG_HIP_CHECK(hipStreamWaitEvent(s, ctx->side_ev[1], 0));  // (not reached when X Q was folded)
-  static const int acc_tile = getenv("HELFEM_ACC_TILE") ? atoi(getenv("HELFEM_ACC_TILE")) : 0;  // A/B runs: 64 or 128
+  if (tuning().bt_side && !ctx->avoid_side) HFG_HIP_CHECK(hipStreamWaitEvent(s, ctx->side_ev[1], 0));  // (not reached when X Q was folded)
   // pairs of reflector blocks, last to first: three launches and one read-modify-write of Z per 128 reflectors
   for (int g = NP - 1; g >= 0; g--) {
     gemm_tasklist64_dev(ctx, w.btslab.p + (size_t)g * BT_S * nblk, BT_S * nblk, BT_PW, nmax);
@@ -950,7 +944,7 @@ static void bt_wy_apply(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, i
     // traffic on every tile's critical path)
     hipLaunchKernelGGL(k_bt_wpair, dim3((nmax + 4 * BT_WREP - 1) / (4 * BT_WREP), nblk), dim3(256), 0, s, b, dptr + 3 * nblk, dptr + 4 * nblk,
                        dptr + 5 * nblk, BT_S, BT_GS, NP, g, 0);
-    gemm_tasklist_acc_dev(ctx, w.btupd.p + (size_t)g * nblk, nblk, nmax, nmax, acc_tile != 128);
+    gemm_tasklist_acc_dev(ctx, w.btupd.p + (size_t)g * nblk, nblk, nmax, nmax, tuning().acc_tile != 128);
   }
   HFG_HIP_CHECK(hipGetLastError());
 }
@@ -1025,22 +1019,19 @@ static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, con
     b.sweeps[i] = w.sweeps[i].p;
   }
   hipStream_t s = ctx->stream;
-  static const bool bt_column = (getenv("HELFEM_BT") && !strcmp(getenv("HELFEM_BT"), "column"));
-  const bool bt_wy = !bt_column && nmax >= 4 * BT_KB;
-  static const bool fold_on = !(getenv("HELFEM_BT_FOLD") && atoi(getenv("HELFEM_BT_FOLD")) == 0);
+  const bool bt_wy = !tuning().bt_column && nmax >= 4 * BT_KB;
   if (tridiagonalize_takes_chain(nblk, ns)) {  // thousands of dependent launches ahead: no second stream beside them
     ctx->avoid_side = true;
     ctx->drop_side();
   }
-  const bool fold = bt_wy && foldX != nullptr && fold_on && !ctx->avoid_side;
+  const bool fold = bt_wy && foldX != nullptr && tuning().bt_fold && !ctx->avoid_side;
   w.folded = fold;
   if (fold)
     for (int i = 0; i < nblk; i++) w.Y[i].resize((size_t)ns[i] * ns[i]);
   if (bt_wy) bt_wy_setup(ctx, w, b, nblk, ns, nmax, fold);
   {
     ProfScope ps(ctx, "eig_tridiag");
-    static const bool unblocked = (getenv("HELFEM_TRD") && !strcmp(getenv("HELFEM_TRD"), "unblocked"));
-    if (unblocked) {
+    if (tuning().trd_mode == TrdMode::unblocked) {
       // first-generation path (rank-2 update of the whole trailing matrix at every column), kept for A/B runs
       size_t shb = (size_t)(nmax + 4 * 64 + 8) * sizeof(double);
       if (shb > 64 * 1024)
@@ -1067,9 +1058,8 @@ static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, con
   if (fold) bt_wy_fold_x(ctx, w, b, nblk, ns, nmax, foldX);
   {
     ProfScope ps(ctx, "eig_tridiag_solve");
-    static const bool use_ql = (getenv("HELFEM_TRIDIAG") && !strcmp(getenv("HELFEM_TRIDIAG"), "ql"));
-    w.used_dc = !use_ql;
-    if (use_ql) {
+    w.used_dc = !tuning().tridiag_ql;
+    if (!w.used_dc) {
       // reference implementation kept for cross-checks: implicit QL by one lane, rotations logged then applied
       hipLaunchKernelGGL(k_set_identity, dim3((nmax + 255) / 256, nmax, nblk), dim3(256), 0, s, b);
       hipLaunchKernelGGL(k_tql_values, dim3(nblk), dim3(64), 0, s, b);
@@ -1311,10 +1301,9 @@ void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs,
         hipLaunchKernelGGL(k_gather_block, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, dS, N, drows + blk_ptr[ib],
                            dcols + blk_ptr[ib], n, Fb.p + (size_t)k * nmax * nmax, Xall.p + (size_t)k * nmax * nmax);
       }
-      static const bool rect = getenv("HELFEM_GEMM_RECT") && atoi(getenv("HELFEM_GEMM_RECT"));
       // two workgroups per tile (split K) when the batch's tiles would not fill the chip evenly: more than half, fewer
       // than all of the 2 x CU slots; HELFEM_GEMM_SPLITK = 0 / 1 forces it off / on
-      static const int force_split = getenv("HELFEM_GEMM_SPLITK") ? atoi(getenv("HELFEM_GEMM_SPLITK")) : -1;
+      const int force_split = tuning().gemm_splitk;
       long full_tiles = 0, low_tiles = 0;
       for (int k = 0; k < nb; k++) {
         const long t1 = (ns[k] + 127) / 128;
@@ -1339,7 +1328,7 @@ void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs,
       if (split_full) {
         for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(T1.p + (size_t)k * nmax * nmax, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
         gemm_tasklist_split2_dev(ctx, w.gtasks.p, nb, nm, nm);
-      } else if (rect) gemm_tasklist_rect_dev(ctx, w.gtasks.p, nb, nm, nm);
+      } else if (tuning().gemm_rect) gemm_tasklist_rect_dev(ctx, w.gtasks.p, nb, nm, nm);
       else gemm_tasklist_dev(ctx, w.gtasks.p, nb, nm, nm);
       if (split_low) {
         for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(w.A[k].p, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
@@ -1352,13 +1341,12 @@ void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs,
     eig_sym_batch(ctx, w, nb, ns.data(), Xptr);
     {
       ProfScope ps(ctx, "eig_backtransform");
-      static const bool rect = getenv("HELFEM_GEMM_RECT") && atoi(getenv("HELFEM_GEMM_RECT"));
       {
         ProfScope pp3(ctx, "eig_products");
         const GemmTask *last = w.gtasks.p + (w.folded ? 3 : 2) * (size_t)nb;
         if (w.tile64) gemm_tasklist64_dev(ctx, last, nb, nm, nm);
         else if (w.split_full) gemm_tasklist_split2_dev(ctx, last, nb, nm, nm);  // the block slots were zeroed above
-        else if (rect) gemm_tasklist_rect_dev(ctx, last, nb, nm, nm);
+        else if (tuning().gemm_rect) gemm_tasklist_rect_dev(ctx, last, nb, nm, nm);
         else gemm_tasklist_dev(ctx, last, nb, nm, nm);
       }
       std::vector<const double *> csrc;

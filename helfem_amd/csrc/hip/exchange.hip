@@ -281,10 +281,7 @@ void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, 
   ProfScope ps(ctx, "exchange");
   // fast path for the low-rank densities of SCF runs (exchange_lr.hip); HELFEM_EXCHANGE=general forces the
   // general kernels below, which take any symmetric P
-  {
-    const char *mode = getenv("HELFEM_EXCHANGE");
-    if (!(mode && std::string(mode) == "general") && exchange_lowrank_dev(ctx, t, dP, dK, Lknown, rknown)) return;
-  }
+  if (!helfem::tuning_live().exchange_general && exchange_lowrank_dev(ctx, t, dP, dK, Lknown, rknown)) return;  // (read at every call)
   ExAux &a = exaux_for(ctx, t);
   hipStream_t s = ctx->stream;
   const int A = t->A, R = t->R, E = t->E, p = t->p, Nd = t->Nd, N = t->N, Nlm = t->Ntab, ntt = t->ntt;

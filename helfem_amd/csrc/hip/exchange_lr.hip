@@ -34,7 +34,6 @@ void gemm_tasklist_wl_split2_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, cons
 void gemm_tasklist_split2_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
 
 constexpr int EXL_RMAX = 64;
-constexpr int EXL_GMAX = 16;  // factor groups (residual factorisations) at most
 constexpr int EXL_QMAX = 16;  // rows per thread in the factorisation kernel: N <= 1024 * EXL_QMAX
 
 // -------------------------------------------------------------------------------------------------
@@ -1117,8 +1116,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   // erfc kernel (pair_tei): no factorisation over elements; the element-pair products below need an exchange-ordered
   // copy of the pair tables
   if (t->pair_tei && (double)ntt * Ntab * E * E * p * p * p * p * sizeof(double) > 32e9) return false;
-  static const bool pair_off = getenv("HELFEM_EXL_PAIR") && atoi(getenv("HELFEM_EXL_PAIR")) == 0;
-  if (t->pair_tei && pair_off) return false;
+  if (t->pair_tei && !tuning().exl_pair) return false;
   ExLRAux &a = exlr_for(ctx, t);
   for (const ExLRAux::MRun &run : a.runs)
     if (run.nj > 256) return false;  // k_exl_V lists at most 256 coupled shells
@@ -1127,11 +1125,11 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   const int pp = p * p;
 
   // ---- factorise and verify ----
-  // Up to EXL_GMAX groups of EXL_RMAX factors: when the first group does not reproduce P, the residual matrix
+  // Up to HELFEM_EXL_GROUPS groups of EXL_RMAX factors: when the first group does not reproduce P, the residual matrix
   // P - L S L^T is factorised in turn, and so on; K is linear in P, so the groups' exchange matrices add up (a density of
   // rank 65 costs two passes, not the general kernels' seventy-fold).  All factorisations come first: an input that is not
   // of low rank is handed to the general kernels before any exchange work is done.
-  static const int gmax = getenv("HELFEM_EXL_GROUPS") ? std::max(1, std::min(EXL_GMAX, atoi(getenv("HELFEM_EXL_GROUPS")))) : 4;
+  const int gmax = tuning().exl_groups;
   a.L.resize((size_t)N * EXL_RMAX * gmax);
   a.sgn.resize((size_t)EXL_RMAX * gmax);
   a.info.resize(4);
@@ -1140,8 +1138,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   double pmax = 0.0;
   bool reproduced = false;
   const double *Pcur = dP;
-  static const bool no_hint = getenv("HELFEM_EXL_HINT") && atoi(getenv("HELFEM_EXL_HINT")) == 0;  // checker: always factorise
-  if (Lknown && rknown >= 0 && rknown <= EXL_RMAX && !no_hint) {
+  if (Lknown && rknown >= 0 && rknown <= EXL_RMAX && tuning().exl_hint) {  // (off, the checker: always factorise)
     if (rknown > 0) {
       HFG_HIP_CHECK(hipMemcpyAsync(a.L.p, Lknown, sizeof(double) * (size_t)N * rknown, hipMemcpyDeviceToDevice, s));
       HFG_HIP_CHECK(hipMemcpyAsync(a.sgn.p, a.ones.p, sizeof(double) * (size_t)rknown, hipMemcpyDeviceToDevice, s));
@@ -1176,7 +1173,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   for (int r : rg) rmax_g = std::max(rmax_g, r);
   {
     // the one-pair kernels (erfc pair tables, p > 16, HELFEM_EXL_RB=1) stage all (channel, factor) columns at once
-    const bool one_pair = t->pair_tei || p > 16 || (getenv("HELFEM_EXL_RB") && atoi(getenv("HELFEM_EXL_RB")) == 1);
+    const bool one_pair = t->pair_tei || p > 16 || tuning().exl_rb == 1;
     if (one_pair && (size_t)(4 * a.max_nch * rmax_g * p + a.max_nch * rmax_g) * sizeof(double) > 150 * 1024) return false;
   }
   if (rmax_g == 0) {  // P == 0
@@ -1207,10 +1204,9 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   hipLaunchKernelGGL(k_exl_V, dim3(NLM, A), dim3(256), 0, s, a.Ld.p, Nd, R, A, r, a.LM_L.p, a.LM_M.p, t->shell_m.p,
                      a.c0tab.p, a.c2tab.p, t->Lp1, two, a.V0.p, a.V2.p);
   // cross products by blocks of equal m (below) need the M-major column order, which only the fast alpha kernel writes
-  static const bool group_off = getenv("HELFEM_EXL_MGROUPS") && atoi(getenv("HELFEM_EXL_MGROUPS")) == 0;
   const size_t alds = (size_t)(two ? 2 : 1) * Nd * sizeof(double);
   const bool alpha_fast = !(p > EXL_AP || E * p > 512 || alds > 150 * 1024);
-  const bool grouped = !pair && a.cross_ok && alpha_fast && !group_off;
+  const bool grouped = !pair && a.cross_ok && alpha_fast && tuning().exl_mgroups;
   if (!pair) {
   if (!alpha_fast)
     hipLaunchKernelGGL(k_exl_alpha_gen, dim3((unsigned)ncol, A), dim3(128), 0, s, a.V0.p, a.V2.p, t->disj.p, t->LM_tab.p,
@@ -1274,13 +1270,10 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
       HFG_HIP_CHECK(hipStreamSynchronize(s));  // ct lives on this stack frame
       // few large tiles (ten products of 8 x 8 tiles at Nbf = 4230: 640 tiles on 512 slots run as two rounds): two
       // half-K workgroups per tile into a zeroed G fill the slots evenly (two addends per element: deterministic)
-      static const bool nosplit = getenv("HELFEM_EXL_SPLITK") && atoi(getenv("HELFEM_EXL_SPLITK")) == 0;
-      if (!nosplit && tiles < 2048 && ncol >= 512) {
+      if (tuning().exl_splitk && tiles < 2048 && ncol >= 512) {
         if (!grouped) HFG_HIP_CHECK(hipMemsetAsync(a.G.p, 0, sizeof(double) * ct.size() * Ap * Ap, s));
         // 128 x 64 tiles: the blocks of ~300 columns pad to 320 instead of 384 (11.6 -> 11.5 ms per build; HELFEM_EXL_CRECT=0: square)
-        static const bool crect = !(getenv("HELFEM_EXL_CRECT") && atoi(getenv("HELFEM_EXL_CRECT")) == 0);
-        static const bool cwl_off = getenv("HELFEM_EXL_WL") && atoi(getenv("HELFEM_EXL_WL")) == 0;
-        if (crect && grouped && !cwl_off) {
+        if (tuning().exl_crect && grouped && tuning().exl_wl) {
           // all tiles of a product on one XCD: its operand blocks are fetched once (2.4 GB were fetched for 0.3 GB of aP, aQw)
           std::vector<int2> &wl = a.h_cwl;
           wl.clear();
@@ -1290,7 +1283,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
           }
           a.cwl.upload(wl, s);
           gemm_tasklist_wl_split2_rect_dev(ctx, a.ctasks.p, a.cwl.p, (int)wl.size());
-        } else if (crect && grouped) gemm_tasklist_split2_rect_dev(ctx, a.ctasks.p, (int)ct.size(), maxMN, maxMN);
+        } else if (tuning().exl_crect && grouped) gemm_tasklist_split2_rect_dev(ctx, a.ctasks.p, (int)ct.size(), maxMN, maxMN);
         else gemm_tasklist_split2_dev(ctx, a.ctasks.p, (int)ct.size(), maxMN, maxMN);
       } else
         gemm_tasklist_dev(ctx, a.ctasks.p, (int)ct.size(), maxMN, maxMN);
@@ -1303,8 +1296,8 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   const int Kt = ntt * pp;
   // the matrix-core RB kernel writes columns of a.kK >= Kt rows (zero padded like the element tables): every k step of
   // the GEMM is then a full one; the vector kernels (checkers, p > 16) and the pair tables keep the unpadded columns
-  static const int rb_env = getenv("HELFEM_EXL_RB") ? atoi(getenv("HELFEM_EXL_RB")) : 0;
-  const bool rb_mfma = !pair && p <= 16 && rb_env != 1 && rb_env != 4;
+  const bool rb_one = tuning().exl_rb == 1, rb_four = tuning().exl_rb == 4;  // the one-pair and the 4 x 4 vector kernel (checkers)
+  const bool rb_mfma = !pair && p <= 16 && !rb_one && !rb_four;
   const int Kld = rb_mfma ? a.kK : Kt;
   size_t rb_tot = 0, c_tot = 0;
   int maxN = 0;
@@ -1380,8 +1373,6 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
                            a.tab_ch_off.p, a.tab_ch.p, t->LM_fac.p, sgrp, a.S_off.p, a.S_list.p, a.rb_off.p, tau0, Nd, R, E,
                            p, r, ntt, a.RB.p);
       else {
-        static const bool rb_one = getenv("HELFEM_EXL_RB") && atoi(getenv("HELFEM_EXL_RB")) == 1;  // the one-pair kernel (checker)
-        static const bool rb_four = getenv("HELFEM_EXL_RB") && atoi(getenv("HELFEM_EXL_RB")) == 4;  // the 4 x 4 vector kernel (checker)
         const size_t shb4 = (size_t)(4 * EXL_SB * EXL_CK * p + EXL_CK) * sizeof(double);
         if (!rb_one && !rb_four && p <= 16) {
           // the list of workgroups depends on the tables and on the shard only
@@ -1428,11 +1419,10 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
     // ... for the shorter pair lists; with the longer lists of larger angular bases the padding is small either way and
     // the square tiles' lower LDS traffic per flop wins (measured: Nbf = 4230, 1000 pairs per task on average, 11.6 against
     // 12.0 ms per build; Nbf = 6102, 28.6 against 29.4 the other way round)
-    static const int rect_env = getenv("HELFEM_EXL_RECT") ? atoi(getenv("HELFEM_EXL_RECT")) : -1;
+    const int rect_env = tuning().exl_rect;
     double ncols_tot = 0.0;
     for (const GemmTask &q : tasks) ncols_tot += (double)q.N;
     const bool rect_tiles = rect_env >= 0 ? rect_env != 0 : (ncols_tot < 1500.0 * (double)tasks.size());
-    static const bool wl_off = getenv("HELFEM_EXL_WL") && atoi(getenv("HELFEM_EXL_WL")) == 0;  // checker: plain task-list grid
     // bench.py: HIP events around this launch alone ("exl_element_gemm") and its USEFUL work in GFLOP, 2 p^2 pairs (ntt p^2)
     // per task without any padding, accumulated in the `ms` field of "exl_element_gemm_gflop"
     ProfScope pgemm(ctx, "exl_element_gemm");
@@ -1442,7 +1432,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
       ctx->prof["exl_element_gemm_gflop"].ms += gf;
       ctx->prof["exl_element_gemm_gflop"].launches += 1;
     }
-    if (!wl_off) {
+    if (tuning().exl_wl) {  // (off, the checker: plain task-list grid)
       // all tiles of a task on one XCD (its element table is then fetched from HBM once, not by all eight L2s)
       // short pair lists: 64 x 64 tiles (three workgroups per CU; 5.71 against 6.08 ms with 128 x 64 at Nbf = 4230); long lists:
       // 128 x 128 (15.5 against 15.8 ms with 64 x 64 at Nbf = 6102).  HELFEM_EXL_RECT = 0 / 1 / 2 forces 128 x 128 / 128 x 64 / 64 x 64

@@ -1150,25 +1150,19 @@ static size_t xc_fock_theta_lds(int nth, int maxgrp, int do_lapl) {
     HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_theta, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
   return shb;
 }
-// LDS the angular kernels may plan with; HELFEM_XC_LDS_LIMIT (bytes) lowers it so that the chunked paths can be exercised on
-// small bases (tests)
-static size_t xc_lds_limit() {
-  static const size_t v = getenv("HELFEM_XC_LDS_LIMIT") ? (size_t)atol(getenv("HELFEM_XC_LDS_LIMIT")) : (size_t)150 * 1024;
-  return v;
-}
 // X4 launch: the one-pass kernel when its tables fit a CU's LDS, the chunked one otherwise
 static void launch_xc_fock_theta(hfg_ctx *ctx, size_t NQ, int G, int nth, int maxgrp, const double *Fo, const double *Th, const double *dTh,
                                  int A, const int *grp_off, const int *grp_shell, int do_grad, int do_tau, int rank, int nranks,
                                  double *GA, double *GB, double *GC, int do_lapl = 0, double *GL = nullptr) {
   const int nf = do_lapl ? 6 : 5;  // potential rows
   const size_t need = (size_t)(nf * nth + 4 * nth * maxgrp) * sizeof(double);
-  if (need <= xc_lds_limit()) {
+  if (need <= tuning().xc_lds_limit) {
     hipLaunchKernelGGL(k_xc_fock_theta, dim3((unsigned)NQ, G * G), dim3(256), xc_fock_theta_lds(nth, maxgrp, do_lapl), ctx->stream, Fo, Th, dTh, A,
                        nth, G, grp_off, grp_shell, do_grad, do_tau, do_lapl, NQ, rank, nranks, GA, GB, GC, GL);
     return;
   }
   if (maxgrp * maxgrp > XC_FT_MAXPP * 256) throw std::runtime_error("angular basis too large for the XC Fock kernels (more than 64 shells of one m)");
-  int nthc = (int)(xc_lds_limit() / sizeof(double) / (nf + 4 * maxgrp));
+  int nthc = (int)(tuning().xc_lds_limit / sizeof(double) / (nf + 4 * maxgrp));
   if (nthc < 4) throw std::runtime_error("angular basis too large for the XC Fock kernels' LDS tables");
   nthc = std::min(nthc, nth);
   const size_t shb = (size_t)(nf * nthc + 4 * nthc * maxgrp) * sizeof(double);
@@ -1520,7 +1514,7 @@ void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, cons
   }
   const int npot2 = do_lapl ? 12 : (do_tau ? 10 : 8);  // LDS potential planes, both spins
   int rowc = nth;  // theta rows per pass through LDS
-  while ((size_t)(npot2 * rowc * nphi + 3 * 4) * sizeof(double) > xc_lds_limit() && rowc > 1) rowc = (rowc + 1) / 2;
+  while ((size_t)(npot2 * rowc * nphi + 3 * 4) * sizeof(double) > tuning().xc_lds_limit && rowc > 1) rowc = (rowc + 1) / 2;
   size_t shb = (size_t)(npot2 * rowc * nphi + 3 * 4) * sizeof(double);
   if (shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the polarised grid kernel's LDS tile");
   const bool ext = (x_func > 0 && xc::is_ext(x_func)) || (c_func > 0 && xc::is_ext(c_func));
@@ -1609,8 +1603,7 @@ void fock_compact_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, co
   // J and the XC matrix are independent given the compact density: the Coulomb kernels (one of them streams the 1 GB of
   // primitive integrals: HBM-bound) run on the context's side stream beside the XC kernels (LDS- and latency-bound)
   // -- HELFEM_FOCK_OVERLAP=0: one after the other on the main stream
-  static const bool overlap = !(getenv("HELFEM_FOCK_OVERLAP") && atoi(getenv("HELFEM_FOCK_OVERLAP")) == 0);
-  if ((x_func > 0 || c_func > 0) && overlap && !ctx->avoid_side) {
+  if ((x_func > 0 || c_func > 0) && tuning().fock_overlap && !ctx->avoid_side) {
     hipStream_t main = ctx->stream, q = ctx->side();
     gather_compact(ctx, basis, dP, a.Pc.p);
     HFG_HIP_CHECK(hipEventRecord(ctx->side_ev[0], main));

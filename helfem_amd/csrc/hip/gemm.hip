@@ -406,10 +406,7 @@ __global__ __launch_bounds__(256, 2) void k_dgemm_tasklist_split2(const GemmTask
 }
 
 /// HELFEM_MFMA=4x4x4 selects the v_mfma_f64_4x4x4_4b_f64 form of the tile engine (A/B runs; same speed, more LDS reads)
-static bool mfma4() {
-  static const bool v = (getenv("HELFEM_MFMA") && !strcmp(getenv("HELFEM_MFMA"), "4x4x4"));
-  return v;
-}
+static bool mfma4() { return tuning().mfma_4x4x4; }
 
 /// task lists whose products accumulate into C (beta != 0 in every active task): streaming epilogue
 void gemm_tasklist_acc_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, bool tile64) {
@@ -543,8 +540,7 @@ void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int max
 /// rounds) 47.7 against 52.1, and the 386 tiles of the eigensolve's three blocks 34 against 37 (profiles/r03_gemm_bench.txt).
 /// HELFEM_GEMM_TILE = 64 / 128 forces one.
 bool gemm_prefers_128(hfg_ctx *ctx, long tiles128) {
-  static const int force_tile = getenv("HELFEM_GEMM_TILE") ? atoi(getenv("HELFEM_GEMM_TILE")) : 0;
-  if (force_tile) return force_tile == 128;
+  if (tuning().gemm_tile) return tuning().gemm_tile == 128;
   static int slots = 0;
   if (!slots) {
     int ncu = 256;

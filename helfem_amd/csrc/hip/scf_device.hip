@@ -553,8 +553,7 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
   auto prepare_tables = [&]() {
     if (verbose) printf("Computing two-electron integrals\n");
     t0 = wall();
-    static const bool host_tei = getenv("HELFEM_TEI") && !strcmp(getenv("HELFEM_TEI"), "host");  // the checker of tei_dev.hip
-    if (host_tei) {
+    if (tuning().tei_host) {  // the checker of tei_dev.hip
       if (hb->kind) hb->ab.compute_tei(opt.kfrac != 0.0);
       else hb->b.compute_tei(opt.kfrac != 0.0);
       hb->tei_on_device = false;
@@ -689,8 +688,7 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
   // the restricted driver counts its one spin twice, as the reference does by passing Fa = Fb, Pa = Pb to uDIIS
   // DIIS error by symmetry blocks when every matrix in it is block diagonal (not with the CUHF constraint, whose lambda
   // comes from natural orbitals of the whole density); HELFEM_DIIS_BLOCKS=0 keeps the four dense N^3 products (checker)
-  static const bool blocks_off = getenv("HELFEM_DIIS_BLOCKS") && atoi(getenv("HELFEM_DIIS_BLOCKS")) == 0;
-  bool blocked_err = symm != 0 && dsym.size() > 1 && !rohf && !blocks_off;
+  bool blocked_err = symm != 0 && dsym.size() > 1 && !rohf && tuning().diis_blocks;
   if (blocked_err) d.blocked_error_setup(nspin, ptr, idx);
   helfem::DiisMixer mixer(true, opt.diiseps, opt.diisthr, true, verbose, (size_t)order);
   const double spinfac = restr ? 2.0 : 1.0;
@@ -830,11 +828,10 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
       double *Es[2] = {d.histE[slot].p, d.histE[slot].p + d.be.etot};  // the spins' blocks one after the other
       // P = C_occ C_occ^T of this iteration's orbitals: the error from the occupied columns (HELFEM_DIIS_LOWRANK=0: the
       // four n^3 products per block from F and P, the checker)
-      static const bool lowrank_off = getenv("HELFEM_DIIS_LOWRANK") && atoi(getenv("HELFEM_DIIS_LOWRANK")) == 0;
       const double *Cs[2] = {d.Ca.p, nspin == 2 ? d.Cb.p : nullptr};
       const int noccs[2] = {nela, nelb};
-      if (lowrank_off) d.blocked_error(Fs, Ps, Es);
-      else d.blocked_error_lowrank(Fs, Cs, noccs, Es);
+      if (tuning().diis_lowrank) d.blocked_error_lowrank(Fs, Cs, noccs, Es);
+      else d.blocked_error(Fs, Ps, Es);
     }
     for (int sp = 0; sp < nspin; sp++) {
       double *F = sp ? d.Fb.p : d.Fa.p;
@@ -907,7 +904,6 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
     if (damping && verbose) printf("Damping off-diagonal elements of Fock matrix by % .3f\n", opt.dampfock);
     // both spins' extrapolated (and damped) Fock matrices first, then ONE batched eigensolve for them: the
     // tridiagonalisation's chain of dependent launches is as long for six blocks as for three
-    static const bool pair_eig = !(getenv("HELFEM_EIG_PAIR") && atoi(getenv("HELFEM_EIG_PAIR")) == 0);
     if (nspin == 2) FdB.resize(NN);
     double *Fds[2] = {d.T1.p, nspin == 2 ? FdB.p : nullptr};
     for (int sp = 0; sp < nspin; sp++) {
@@ -935,7 +931,7 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
         HFG_HIP_CHECK(hipMemcpyAsync(Fd, d.Err.p, sizeof(double) * NN, hipMemcpyDeviceToDevice, s));
       }
     }
-    if (nspin == 2 && pair_eig)
+    if (nspin == 2 && tuning().eig_pair)
       eig_gsym_sub_pair_dev(ctx, n, Fds[0], Fds[1], d.Sinvh.p, (int)dsym.size(), ptr.data(), idx.data(), d.Ea.p, d.Ca.p, d.Eb.p, d.Cb.p);
     else
       for (int sp = 0; sp < nspin; sp++)

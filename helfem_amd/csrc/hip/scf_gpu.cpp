@@ -126,10 +126,7 @@ thread_local int g_readocc = 0;  // --readocc of the following hfg_scf_diatomic 
 thread_local std::vector<std::vector<int> > g_occs;
 thread_local int g_iguess = 0;  // --iguess of the following hfg_scf_* calls of this thread (hfg_scf_set_iguess)
 
-bool host_driver() {
-  const char *e = getenv("HELFEM_SCF");
-  return e && std::string(e) == "host";
-}
+bool host_driver() { return helfem::tuning_live().scf_host; }  // (read at every call)
 
 // set-up of src/diatomic/main.cpp:245-430 (basis, quadrature defaults, symmetry), then the device-resident loop
 helfem::scf::Result run_diatomic_device(hfg_ctx *ctx, const helfem::scf::Options &opt) {

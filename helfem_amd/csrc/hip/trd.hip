@@ -1151,18 +1151,34 @@ __global__ void k_trdb_finish(const TrdBatch *__restrict__ bp) {
 
 /// order from which the remaining columns are reduced inside one launch: HELFEM_TRD_TAIL = 0 none, 1 the LDS-resident
 /// kernel (128), 2 (default) the register-resident kernel (192)
-static int trd_tail_order() {
-  static const int mode = getenv("HELFEM_TRD_TAIL") ? atoi(getenv("HELFEM_TRD_TAIL")) : 2;
-  return mode == 0 ? 0 : (mode == 1 ? TT_MAX : TR_MAX);
+static int trd_tail_order() { return tuning().trd_tail == 0 ? 0 : (tuning().trd_tail == 1 ? TT_MAX : TR_MAX); }
+/// its first column: the first panel boundary where every trailing matrix has that order at most (nmax: no tail)
+static int trd_tail_start(int nmax, bool fused) {
+  if (!fused || trd_tail_order() == 0 || nmax < 3) return nmax;
+  const int j_tail = std::max(0, ((nmax - trd_tail_order() + TB_NB - 1) / TB_NB) * TB_NB);
+  return nmax - j_tail < 3 ? nmax : j_tail;
 }
 
-// Switch-over tile count of the symmetric sweep: panels whose full grid has more tiles than this run in symmetric mode.
-// Default 0 = every panel: measured (bench workload, HELFEM_TRDF_SYM_MIN = 16 ... 300 and "always") the step time does
+// HELFEM_TRDF_SYM_MIN, the switch-over tile count of the symmetric sweep: panels whose full grid has more tiles than this
+// run in symmetric mode.  Default 0 = every panel: measured (bench workload, HELFEM_TRDF_SYM_MIN = 16 ... 300 and "always") the step time does
 // not depend on it once the panels that exceed the CU count are symmetric, and sweeping one triangle everywhere halves
 // the sweep's HBM traffic (PMC: 14.4 MB -> what the algorithm needs, one triangle plus the diagonal tiles).
-static int trd_sym_min_tiles(hfg_ctx *) {
-  static const int v = getenv("HELFEM_TRDF_SYM_MIN") ? atoi(getenv("HELFEM_TRDF_SYM_MIN")) : 0;
-  return v;
+//
+// The k_trdf launch of column i, column c of the panel that starts at j0, for nblk matrices, the largest of order nmax:
+// the one place that derives its shape, for the factorisation and for its measurement replay (which passes dbg).
+// sweeping = false: the panel's last launch, which only finishes the column before it.
+static void trdf_launch(hipStream_t s, const TrdBatch *db, int nblk, int nmax, int i, int j0, int c, bool sweeping, int dbg = 0) {
+  const int m0 = nmax - j0 - 1, m = nmax - i - 1;  // the panel's first column decides the mode
+  const long full = (long)((m0 + 1 + TF_T - 1) / TF_T) * std::max(1, (m0 + TF_T - 1) / TF_T) * nblk;
+  // symmetric sweep (lower tiles only) for the panels whose full grid would not fit the chip in one round
+  // (HELFEM_TRDF_SYM: 0 never, 1 always, default by size)
+  const bool symm = tuning().trdf_sym >= 0 ? tuning().trdf_sym != 0 : full > tuning().trdf_sym_min;
+  const int nrt = (m + 1 + TF_T - 1) / TF_T, ncs = std::max(1, (m + TF_T - 1) / TF_T);
+  // (symmetric: nrt >= ceil((m + delta)/T) for either parity of n; the largest block decides, smaller ones need no more tiles)
+  const int grid = !sweeping ? nrt : symm ? nrt * (nrt + 1) / 2 : nrt * ncs;
+  const int sweep = (sweeping ? 1 : 0) | ((dbg & 7) << 1) | (symm ? 16 : 0);
+  if (tuning().trdf_nth == 512) hipLaunchKernelGGL(k_trdf<512>, dim3(grid, nblk), dim3(512), 0, s, db, i, c, sweep);  // A/B runs
+  else hipLaunchKernelGGL(k_trdf<1024>, dim3(grid, nblk), dim3(1024), 0, s, db, i, c, sweep);
 }
 
 struct TrdWork {
@@ -1273,15 +1289,11 @@ void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *
   if (shb > 64 * 1024)
     HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_trdb_gemv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
   // HELFEM_TRD=twokernel keeps the earlier two-launches-per-column variant (k_trdb_gemv + k_trdb_w)
-  static const bool twokernel = (getenv("HELFEM_TRD") && !strcmp(getenv("HELFEM_TRD"), "twokernel"));
-  const bool fused = !twokernel && nmax <= TF_T * (TF_MAXS - 1);
+  const bool fused = tuning().trd_mode != TrdMode::twokernel && nmax <= TF_T * (TF_MAXS - 1);
   w.last_fused = fused;
   // fused variant: the trailing updates A22 -= [V|W][W|V]^T of all blocks of a full panel are one task-list launch
   const int npanel = (nmax - 3) / TB_NB + 1;
-  static const int force_sym0 = getenv("HELFEM_TRDF_SYM") ? atoi(getenv("HELFEM_TRDF_SYM")) : -1;
-  static const bool band_off = getenv("HELFEM_TRD_BAND_UPDATE") && atoi(getenv("HELFEM_TRD_BAND_UPDATE")) == 0;
-  static const bool acc128 = getenv("HELFEM_ACC_TILE") && atoi(getenv("HELFEM_ACC_TILE")) == 128;
-  const bool band_update = !band_off && !acc128 && (force_sym0 >= 0 ? force_sym0 != 0 : trd_sym_min_tiles(ctx) == 0);
+  const bool band_update = tuning().trd_band_update && tuning().acc_tile != 128 && (tuning().trdf_sym >= 0 ? tuning().trdf_sym != 0 : tuning().trdf_sym_min == 0);
   if (fused) {
     std::vector<GemmTask> pt((size_t)npanel * nblk);
     for (int pi = 0; pi < npanel; pi++)
@@ -1313,41 +1325,11 @@ void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *
       }
     upload_cached(w.ptasks, w.h_ptasks, pt, s);
   }
-  // LDS-resident tail (k_trd_tail) from the first panel boundary where every trailing matrix has order <= TT_MAX
-  const int tail_max = trd_tail_order();
-  int j_tail = nmax;  // no tail
-  if (fused && tail_max > 0 && nmax >= 3) {
-    j_tail = std::max(0, ((nmax - tail_max + TB_NB - 1) / TB_NB) * TB_NB);
-    if (nmax - j_tail < 3) j_tail = nmax;
-  }
+  const int j_tail = trd_tail_start(nmax, fused);
   for (int j0 = 0; j0 <= nmax - 3 && j0 < j_tail; j0 += TB_NB) {
     if (fused) {
       const int jend = std::min(j0 + TB_NB, nmax - 2);
-      // symmetric sweep (lower tiles only) for the panels whose full grid would not fit the chip in one round
-      // (HELFEM_TRDF_SYM: 0 never, 1 always, default by size)
-      static const int force_sym = getenv("HELFEM_TRDF_SYM") ? atoi(getenv("HELFEM_TRDF_SYM")) : -1;
-      bool symm;
-      {
-        const int m0 = nmax - j0 - 1;
-        const long full = (long)((m0 + 1 + TF_T - 1) / TF_T) * std::max(1, (m0 + TF_T - 1) / TF_T) * nblk;
-        symm = (force_sym >= 0) ? (force_sym != 0) : (full > trd_sym_min_tiles(ctx));
-      }
-      for (int i = j0; i <= jend; i++) {
-        const int sweep = ((i < jend) ? 1 : 0) | (symm ? 16 : 0);  // the last launch of the panel only finishes column jend-1
-        const int m = nmax - i - 1;
-        const int nrt = (m + 1 + TF_T - 1) / TF_T, ncs = std::max(1, (m + TF_T - 1) / TF_T);
-        int grid = (sweep & 1) ? nrt * ncs : nrt;
-        if (symm && (sweep & 1)) {
-          const int delta = ((nmax & 1) == 0) ? ((i + 1) & 1) : 0;  // largest block; smaller blocks need no more tiles
-          const int nt = (m + 1 + TF_T - 1) / TF_T;                 // >= ceil((m + delta)/T) for either parity of n
-          grid = nt * (nt + 1) / 2;
-          (void)delta;
-        }
-        static const int force_nth = getenv("HELFEM_TRDF_NTH") ? atoi(getenv("HELFEM_TRDF_NTH")) : 0;  // A/B runs
-        const bool small_wg = (force_nth == 512);
-        if (small_wg) hipLaunchKernelGGL(k_trdf<512>, dim3(grid, nblk), dim3(512), 0, s, db, i, i - j0, sweep);
-        else hipLaunchKernelGGL(k_trdf<1024>, dim3(grid, nblk), dim3(1024), 0, s, db, i, i - j0, sweep);
-      }
+      for (int i = j0; i <= jend; i++) trdf_launch(s, db, nblk, nmax, i, j0, i - j0, i < jend);  // the last launch of the panel only finishes column jend-1
     } else {
     {
       int m = nmax - j0 - 1;
@@ -1369,8 +1351,7 @@ void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *
       const int mt = nmax - j0 - TB_NB;
       if (mt > 0) {
         const GemmTask *pt = w.ptasks.p + (size_t)(j0 / TB_NB) * nblk;
-        static const int acc_tile = getenv("HELFEM_ACC_TILE") ? atoi(getenv("HELFEM_ACC_TILE")) : 0;  // A/B runs: 64 or 128
-        gemm_tasklist_acc_dev(ctx, pt, nblk, mt, mt, acc_tile != 128);
+        gemm_tasklist_acc_dev(ctx, pt, nblk, mt, mt, tuning().acc_tile != 128);
       }
     }
     for (int k = 0; k < nblk; k++) {
@@ -1386,7 +1367,7 @@ void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *
       gemm_dev(ctx, false, true, mt, mt, ncols, -1.0, w.V[k].p + (size_t)n * TB_NB + j1, n, w.V[k].p + j1, n, 1.0, A22, n);
     }
   }
-  if (j_tail < nmax && tail_max == TR_MAX) {
+  if (j_tail < nmax && trd_tail_order() == TR_MAX) {
     hipLaunchKernelGGL(k_trd_tail_reg, dim3(nblk), dim3(TR_NTH), 0, s, db, j_tail);
   } else if (j_tail < nmax) {
     const size_t sht = (size_t)(TT_MAX * TT_LD + 2 * TT_MAX + TT_CG * TT_MAX + 32) * sizeof(double);
@@ -1415,49 +1396,20 @@ void trd_measure_gemv(hfg_ctx *ctx, double *ms, int64_t *launches) {
   int nmax = 0;
   for (int n : w.last_ns) nmax = std::max(nmax, n);
   hipStream_t s = ctx->stream;
-  // HELFEM_TRD_GRAPH=1 (measurement only): the same launches captured into a hipGraph on a private stream and replayed
-  // as ONE graph launch -- does the command processor chain dependent kernels faster than a stream of launches?
-  static const bool use_graph = getenv("HELFEM_TRD_GRAPH") && atoi(getenv("HELFEM_TRD_GRAPH")) != 0;
-  hipStream_t cap = nullptr;
-  if (use_graph) {
-    HFG_HIP_CHECK(hipStreamSynchronize(s));
-    HFG_HIP_CHECK(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-    HFG_HIP_CHECK(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
-    s = cap;
-  }
   const TrdBatch *db = w.desc.p;
   // k_trdb_gemv: v on a column chunk (at most 64 chunks per column) and on 129 rows, 4 x 128 partial sums
   size_t shb = (size_t)(std::max(64, (nmax + 63) / 64 + 1) + 136 + 4 * 128 + 8) * sizeof(double);
   hipEvent_t e0, e1;
   HFG_HIP_CHECK(hipEventCreate(&e0));
   HFG_HIP_CHECK(hipEventCreate(&e1));
-  if (!use_graph) HFG_HIP_CHECK(hipEventRecord(e0, s));
+  HFG_HIP_CHECK(hipEventRecord(e0, s));
   int count = 0;
-  int j_tail = nmax;  // the columns of the LDS-resident tail are not launches of this kernel
-  if (w.last_fused && trd_tail_order() > 0 && nmax >= 3) {
-    j_tail = std::max(0, ((nmax - trd_tail_order() + TB_NB - 1) / TB_NB) * TB_NB);
-    if (nmax - j_tail < 3) j_tail = nmax;
-  }
+  const int j_tail = trd_tail_start(nmax, w.last_fused);  // the columns of the tail are not launches of this kernel
   for (int i = 0; i <= nmax - 3 && i < j_tail; i++) {
     const int c = i % TB_NB;
     const int m = nmax - i - 1;
     if (w.last_fused) {
-      const int nrt = (m + 1 + TF_T - 1) / TF_T, ncs = std::max(1, (m + TF_T - 1) / TF_T);
-      const int cfix = getenv("HELFEM_TRDF_C") ? atoi(getenv("HELFEM_TRDF_C")) : c;
-      const int dbg = getenv("HELFEM_TRDF_DBG") ? atoi(getenv("HELFEM_TRDF_DBG")) : 0;
-      static const int force_nth = getenv("HELFEM_TRDF_NTH") ? atoi(getenv("HELFEM_TRDF_NTH")) : 0;
-      static const int force_sym = getenv("HELFEM_TRDF_SYM") ? atoi(getenv("HELFEM_TRDF_SYM")) : -1;
-      const bool small_wg = (force_nth == 512);
-      bool symm;
-      {
-        const int m0 = nmax - (i - c) - 1;  // the panel's first column decides, as in the factorisation
-        const long full = (long)((m0 + 1 + TF_T - 1) / TF_T) * std::max(1, (m0 + TF_T - 1) / TF_T) * nblk;
-        symm = (force_sym >= 0) ? (force_sym != 0) : (full > trd_sym_min_tiles(ctx));
-      }
-      const int grid = symm ? nrt * (nrt + 1) / 2 : nrt * ncs;
-      const int sw = 1 | ((dbg & 7) << 1) | (symm ? 16 : 0);
-      if (small_wg) hipLaunchKernelGGL(k_trdf<512>, dim3(grid, nblk), dim3(512), 0, s, db, i, cfix, sw);
-      else hipLaunchKernelGGL(k_trdf<1024>, dim3(grid, nblk), dim3(1024), 0, s, db, i, cfix, sw);
+      trdf_launch(s, db, nblk, nmax, i, i - c, tuning().trdf_c >= 0 ? tuning().trdf_c : c, true, tuning().trdf_dbg);
     } else {
       const int nrg = (m + 1 + 127) / 128;
       int ncs = std::max(1, std::min(64, (m + 63) / 64));
@@ -1465,31 +1417,15 @@ void trd_measure_gemv(hfg_ctx *ctx, double *ms, int64_t *launches) {
     }
     count++;
   }
-  if (use_graph) {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    HFG_HIP_CHECK(hipStreamEndCapture(cap, &graph));
-    HFG_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    HFG_HIP_CHECK(hipGraphLaunch(exec, cap));  // warm-up (uploads the graph)
-    HFG_HIP_CHECK(hipStreamSynchronize(cap));
-    HFG_HIP_CHECK(hipEventRecord(e0, cap));
-    HFG_HIP_CHECK(hipGraphLaunch(exec, cap));
-    HFG_HIP_CHECK(hipEventRecord(e1, cap));
-    HFG_HIP_CHECK(hipEventSynchronize(e1));
-    (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
-    (void)hipStreamDestroy(cap);
-  } else {
-    HFG_HIP_CHECK(hipEventRecord(e1, s));
-    HFG_HIP_CHECK(hipEventSynchronize(e1));
-  }
+  HFG_HIP_CHECK(hipEventRecord(e1, s));
+  HFG_HIP_CHECK(hipEventSynchronize(e1));
   float t = 0.f;
   HFG_HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   *ms = t;
   *launches = count;
-  if (w.last_fused && getenv("HELFEM_TRDF_DBG") && (atoi(getenv("HELFEM_TRDF_DBG")) & 4)) {
+  if (w.last_fused && (tuning().trdf_dbg & 4)) {
     const int n0 = w.last_ns[0];
     {
       std::vector<unsigned long long> wv((size_t)16 * n0);

@@ -599,7 +599,7 @@ void trdp_check_status(hfg_ctx *ctx) {
       total += n0s - t0;
       cnt++;
     }
-    if (getenv("HELFEM_TRDP_STAMPS") && atoi(getenv("HELFEM_TRDP_STAMPS")) >= 2 && n0 > 200) {
+    if (tuning().trdp_stamps >= 2 && n0 > 200) {
       fprintf(stderr, "k_trdp stamps, columns 100..160 (us): column | post-publish work | poll | element-wise | product+publish || thread 0 done polling at | lanes missing y, z, dot at the first check\n");
       for (int i = 100; i < 160; i++)
         fprintf(stderr, "  %4d  %.2f | %.2f | %.2f | %.2f | %.2f || %.2f | %llu %llu %llu\n", i, (double)(st[(size_t)(i + 1) * 8] - st[(size_t)i * 8]) * 0.01,
@@ -607,11 +607,11 @@ void trdp_check_status(hfg_ctx *ctx) {
                 (double)(st[(size_t)i * 8 + 1] - st[(size_t)i * 8]) * 0.01, (double)(st[(size_t)i * 8 + 2] - st[(size_t)i * 8 + 1]) * 0.01, (double)(st[(size_t)i * 8 + 5] - st[(size_t)i * 8 + 3]) * 0.01,
                 st[(size_t)i * 8 + 4] & 0xffff, (st[(size_t)i * 8 + 4] >> 16) & 0xffff, (st[(size_t)i * 8 + 4] >> 32) & 0xffff);
     }
-    if (getenv("HELFEM_TRDP_STAMPS_FILE")) {
+    if (!tuning().trdp_stamps_file.empty()) {
       // all workgroups, columns TP_WIN_0 .. TP_WIN_0 + TP_WIN_N: raw 100 MHz stamps (landed, element-wise done, published, poll start)
       std::vector<unsigned long long> win((size_t)TP_MAXG * TP_WIN_N * 4 + TP_MAXG);
       HFG_HIP_CHECK(hipMemcpy(win.data(), w.stamps.p + (size_t)8 * (w.last_nmax + 2), win.size() * 8, hipMemcpyDeviceToHost));
-      if (FILE *f = fopen(getenv("HELFEM_TRDP_STAMPS_FILE"), "w")) {
+      if (FILE *f = fopen(tuning().trdp_stamps_file.c_str(), "w")) {
         fprintf(f, "# grid %d R %d U %d first column %d columns %d; per line: workgroup column landed elementwise_done published poll_start\n", w.last_grid, w.last_R,
                 w.last_U, TP_WIN_0, TP_WIN_N);
         for (int g = 0; g < w.last_grid; g++)
@@ -660,8 +660,7 @@ static const int tp_rows_choices[] = {1, 2, 3, 4, 5, 6};
 static const int tp_widths[] = {2, 4, 6, 8, 10, 12, 14, 16, 17};
 /// column chunks per thread for matrices up to this order (0: beyond the register tiles)
 static int tp_columns_for(int nmax) {
-  static const int force = getenv("HELFEM_TRDP_U") ? atoi(getenv("HELFEM_TRDP_U")) : 0;  // measurement: a wider tile than needed
-  if (force && nmax <= force * TP_NCG) return force;
+  if (tuning().trdp_u && nmax <= tuning().trdp_u * TP_NCG) return tuning().trdp_u;  // measurement: a wider tile than needed
   for (int u : tp_widths)
     if (nmax <= u * TP_NCG) return u;
   return 0;
@@ -670,10 +669,8 @@ static int tp_columns_for(int nmax) {
 /// true when a batch with these orders sends a LARGE matrix through the chain of launches (order beyond the register
 /// tiles, or HELFEM_TRD selecting another variant): eig.hip then keeps the context's side stream out of the way
 bool tridiagonalize_takes_chain(int nblk, const int *ns) {
-  static const char *mode = getenv("HELFEM_TRD");
-  const bool persistent = !(mode && strcmp(mode, "persistent") != 0);
   for (int i = 0; i < nblk; i++)
-    if (ns[i] >= 1024 && (!persistent || tp_columns_for(ns[i]) == 0)) return true;
+    if (ns[i] >= 1024 && (tuning().trd_mode != TrdMode::persistent || tp_columns_for(ns[i]) == 0)) return true;
   return false;
 }
 
@@ -691,10 +688,8 @@ bool tridiagonalize_takes_chain(int nblk, const int *ns) {
 void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *const *A, double *const *d, double *const *e,
                                double *const *tau, std::vector<char> &done) {
   done.assign(nblk, 0);
-  static const char *mode = getenv("HELFEM_TRD");
-  if (mode && strcmp(mode, "persistent") != 0) return;
+  if (tuning().trd_mode != TrdMode::persistent) return;
   if (nblk < 1 || nblk > TP_MAXB) return;
-  static const int min_order = getenv("HELFEM_TRDP_MIN") ? atoi(getenv("HELFEM_TRDP_MIN")) : 256;
   TrdpWork *wp;
   auto it = g_trdp.find(ctx);
   if (it == g_trdp.end()) {
@@ -710,10 +705,8 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
     // the previous launches' status words were copied back on this stream; they are only READ when the stream says so
     if (hipStreamQuery(ctx->stream) == hipSuccess) trdp_check_status(ctx);
   }
-  static const int forceR = getenv("HELFEM_TRDP_R") ? atoi(getenv("HELFEM_TRDP_R")) : 0;
-  static const bool want_stamps = getenv("HELFEM_TRDP_STAMPS") && atoi(getenv("HELFEM_TRDP_STAMPS")) != 0;
-  static const bool phases = !(getenv("HELFEM_TRDP_PHASES") && atoi(getenv("HELFEM_TRDP_PHASES")) == 0);
-  static const int min_step = getenv("HELFEM_TRDP_STEP") ? std::max(1, atoi(getenv("HELFEM_TRDP_STEP"))) : 96;
+  const helfem::Tuning &tun = tuning();
+  const bool want_stamps = tun.trdp_stamps != 0;
   // ---- plan: largest matrices first; a matrix joins the current group while the group still fits ----
   struct Shape {
     int R = 0, U = 0, grid = 0;
@@ -724,7 +717,7 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
     const int U = tp_columns_for(nmax);
     if (U == 0) return false;
     for (int r : tp_rows_choices) {
-      if (forceR && r != forceR) continue;
+      if (tun.trdp_r && r != tun.trdp_r) continue;
       if (!trdp_pick(r, U, false)) continue;
       int grid = 0;
       bool ok = true;
@@ -744,7 +737,7 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
   };
   std::vector<int> order;
   for (int i = 0; i < nblk; i++)
-    if (ns[i] >= 3 && ns[i] >= min_order) order.push_back(i);
+    if (ns[i] >= 3 && ns[i] >= tun.trdp_min) order.push_back(i);
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return ns[x] > ns[y]; });
   // ---- launches (descriptors identical from one SCF iteration to the next: uploaded once).  Before every launch the
   // matrices still to be reduced are looked at again, largest trailing order first, and the launch takes every one of
@@ -787,11 +780,11 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
     }
     if (take.empty()) return;  // cannot happen: every matrix fitted alone at its full order
     const int nmax = orders[0];
-    // columns of this launch: until the largest trailing matrix fits the next narrower tile (at least min_step columns)
+    // columns of this launch: until the largest trailing matrix fits the next narrower tile (at least HELFEM_TRDP_STEP columns)
     int step = 0x3fffffff;
-    if (phases && !want_stamps)
+    if (tun.trdp_phases && !want_stamps)
       for (int q = (int)(sizeof(tp_widths) / sizeof(int)) - 1; q >= 0; q--)
-        if (tp_widths[q] < L.sh.U && nmax - tp_widths[q] * TP_NCG >= min_step) {
+        if (tp_widths[q] < L.sh.U && nmax - tp_widths[q] * TP_NCG >= tun.trdp_step) {
           step = nmax - tp_widths[q] * TP_NCG;
           break;
         }
@@ -845,14 +838,13 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
   w.ring.resize(ring_words);  // one region per launch: ONE poisoning memset in front of the first launch, one copy of the status words behind the last
   const size_t win_off = (size_t)8 * (nmax_all + 2);
   if (want_stamps) w.stamps.resize(win_off + (size_t)TP_MAXG * TP_WIN_N * 4 + TP_MAXG);
-  static const long long limit_ms = getenv("HELFEM_TRDP_LIMIT_MS") ? atoll(getenv("HELFEM_TRDP_LIMIT_MS")) : 200;
   for (size_t q = 0; q < descs.size(); q++) {
     TrdpDesc &D = descs[q];
     for (int b = 0; b < D.nblk; b++) D.xb[b] = w.ring.p + launches[q].ring_words + (size_t)D.xb[b];
     D.status = (int *)(w.ring.p + q);
     D.stamps = want_stamps ? w.stamps.p : nullptr;
     D.win_off = (long long)win_off;
-    D.spin_limit = limit_ms * 100000ll;  // 100 MHz wall clock
+    D.spin_limit = tun.trdp_limit_ms * 100000ll;  // 100 MHz wall clock
   }
   hipStream_t s = ctx->stream;
   upload_cached(w.desc, w.h_desc, descs, s);
@@ -879,9 +871,8 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
       if (nm.empty()) nm = "k_trdp<" + std::to_string(L.sh.R) + ", " + std::to_string(L.sh.U) + ">";
       ProfScope pk(ctx, "k_trdp");
       ProfScope ps(ctx, nm.c_str());
-      static const bool coop = !(getenv("HELFEM_TRDP_COOP") && atoi(getenv("HELFEM_TRDP_COOP")) == 0);  // A/B: plain launch
-      if (coop) err = hipLaunchCooperativeKernel((const void *)kern, dim3(L.sh.grid), dim3(TP_NT), args, 0, s);
-      else err = hipLaunchKernel((const void *)kern, dim3(L.sh.grid), dim3(TP_NT), args, 0, s);
+      if (tun.trdp_coop) err = hipLaunchCooperativeKernel((const void *)kern, dim3(L.sh.grid), dim3(TP_NT), args, 0, s);
+      else err = hipLaunchKernel((const void *)kern, dim3(L.sh.grid), dim3(TP_NT), args, 0, s);  // A/B: plain launch
     }
     if (err != hipSuccess) {
       (void)hipGetLastError();  // refused (grid not co-resident on this device)

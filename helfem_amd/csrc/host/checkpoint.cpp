@@ -1,4 +1,5 @@
 #include "checkpoint.h"
+#include "tuning.h"
 #include <dlfcn.h>
 #include <cstdint>
 #include <cstdlib>
@@ -47,7 +48,7 @@ H5 &h5() {
   static std::once_flag once;
   std::call_once(once, []() {
     std::vector<std::string> cand;
-    if (const char *e = getenv("HELFEM_HDF5_LIB")) cand.push_back(e);
+    if (const std::string e = tuning_live().hdf5_lib; !e.empty()) cand.push_back(e);
     for (const char *n : {"libhdf5.so", "libhdf5.so.103", "libhdf5.so.200", "libhdf5.so.310", "libhdf5_serial.so", "libhdf5_serial.so.103",
                           "/opt/conda/lib/libhdf5.so"})
       cand.push_back(n);

@@ -1,6 +1,7 @@
 // Tiny std::thread parallel-for used by the setup code (the reference uses OpenMP there,
 // e.g. basis.cpp:1175-1178); no dependency on an OpenMP runtime.
 #pragma once
+#include "tuning.h"
 #include <atomic>
 #include <cstdlib>
 #include <exception>
@@ -12,8 +13,8 @@
 namespace helfem {
 
 inline int host_threads() {
-  const char *e = getenv("HELFEM_NUM_THREADS");
-  if (e && atoi(e) > 0) return atoi(e);
+  const int forced = tuning_live().num_threads;  // (set by drivers after the library is loaded: read at every call)
+  if (forced > 0) return forced;
   unsigned n = std::thread::hardware_concurrency();
   if (n == 0) n = 1;
   if (n > 64) n = 64;

@@ -397,6 +397,10 @@ int hfg_profile_get(hfg_ctx *ctx, const char *name, double *ms, int64_t *launche
 /* the names seen since the last reset, separated by '\n' (besides the families above: one name per tile shape of the
  * persistent tridiagonalisation, "k_trdp<R, U>", and "k_trdp" for all its launches) */
 int hfg_profile_names(hfg_ctx *ctx, char *buf, size_t cap);
+/* the HELFEM_* environment switches of the library, one line per switch, fields separated by '\t': name, kind, default,
+ * current value in this process, "once" (read when the process first uses a switch) or "live" (read at every use),
+ * meaning.  Needs no device. */
+int hfg_tuning_table(char *buf, size_t cap);
 
 /* Atomic SCF, restricted closed shell or unrestricted (driver loop of src/atomic/main.cpp:760-1005); out as for hfg_scf_diatomic */
 int hfg_scf_atomic(hfg_ctx *ctx, int Z, int Q, int lmax, int mmax, int nelem, int nnodes, int nquad, double Rmax,

@@ -386,7 +386,7 @@ def test_device_tei_tables_at_the_bench_element_order(hf):
                               "launch_chain_full_sweep", "persistent_one_launch", "persistent_long_phases",
                               "backtransform_on_Z", "small_dc_gemm", "tiles_128", "tiles_64", "split_k_products"])
 def test_fallback_variants(native_libs, env):
-    """the earlier kernel variants stay selectable (environment, read once per process) and stay correct"""
+    """the earlier kernel variants stay selectable (environment, read once per process: helfem_amd.tuning_table() says which) and stay correct"""
     import os
     import subprocess
     import sys

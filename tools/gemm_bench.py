@@ -1,5 +1,5 @@
 """FP64 GEMM tile kernel alone: hfg_gemm_dev on device-resident operands, timed with the library's HIP-event brackets.
-   python tools/gemm_bench.py            (HELFEM_MFMA=16x16x4 for the other matrix instruction)"""
+   python tools/gemm_bench.py            (HELFEM_MFMA=4x4x4 for the other matrix instruction; the default is v_mfma_f64_16x16x4)"""
 import ctypes
 import os
 import sys
@@ -40,4 +40,4 @@ for (m, n, k, tA, tB) in shapes:
     ref = (Aop @ Bop).T
     err = float((C - ref).abs().max() / ref.abs().max())
     print("m=%d n=%d k=%d tA=%d tB=%d: %.3f ms  %.1f TFLOP/s  relerr %.1e  [%s]" % (m, n, k, tA, tB, ms / reps, 2.0 * m * n * k / (ms / reps) * 1e-9,
-                                                                              err, os.environ.get("HELFEM_MFMA", "4x4x4_4b")))
+                                                                              err, os.environ.get("HELFEM_MFMA", "16x16x4")))
