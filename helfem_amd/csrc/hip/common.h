@@ -156,8 +156,12 @@ struct GemmTask {
                  // 128-row tile are readable memory (their products land in rows of C that are not stored), bit 1 -- likewise
                  // the columns of op(B) from N up to the tile edge; lets partial edge tiles use the 16-byte loads.
                  // (Also fills the struct: task lists are compared bytewise, upload_cached.)
+  // column maps (gemm_tasklist64_map_dev only; op(A) = A, beta == 0): column k of A is A[:, amap[k]], column j of the
+  // product is stored at C[:, cmap[j]].  The merges of divide and conquer (dc.hip) read the non-deflated columns of Q
+  // and store every new eigenvector at its ranked place through them.
+  const int *amap = nullptr, *cmap = nullptr;
 };
-static_assert(sizeof(GemmTask) == 80, "GemmTask is compared bytewise: keep it free of padding");
+static_assert(sizeof(GemmTask) == 96, "GemmTask is compared bytewise: keep it free of padding");
 
 struct ProfScope {
   hfg_ctx *c;

@@ -31,6 +31,9 @@ constexpr int DC_MAXB = 8;
 
 struct DCNode {
   int blk, lo, mid, hi;
+  int par;       // depth of the node in its tree, modulo 2: the eigenvector buffer the node writes (see dc_wout)
+  int plo, phi;  // range of the parent (the node's own for a root)
+  int pad;
 };
 
 struct DCBatch {
@@ -44,7 +47,19 @@ struct DCBatch {
   double *rotc[DC_MAXB], *rots[DC_MAXB];
   int *src[DC_MAXB], *flag[DC_MAXB], *nd[DC_MAXB], *org[DC_MAXB], *roti[DC_MAXB], *rotj[DC_MAXB], *rank[DC_MAXB];
   int *ndpos[DC_MAXB];  // position of a non-deflated sorted slot in the nd list (written by k_dc_prepare for k_dc_rank)
+  int *acol[DC_MAXB], *ccol[DC_MAXB];  // column maps of the merge product: source column of nd entry c, ranked place of root c
 };
+
+// Which of the two (d, Q) buffer pairs a node reads and writes: 0 = (d, Qa), 1 = (d2, Qb).
+// Default path (pp = 1): a node of depth k writes pair k & 1 and reads its children's pair (k + 1) & 1, so the roots write
+// (d, Qa) = the caller's arrays and nothing is copied back; nodes of one launch (equal height) may differ in depth.
+// A node also zeroes, in its own columns, the rows of its parent's range outside its own: the parent's product reads
+// whole columns of the parent's square, and nothing else of the buffers is ever read, so they need not be cleared.
+// HELFEM_DC=levels (pp = 0): every node reads pair 0, k_dc_scatter writes pair 1 and k_dc_copyback copies it to pair 0.
+__device__ __forceinline__ int dc_win(const DCNode &nd, int pp) { return pp ? (nd.par ^ 1) : 0; }
+__device__ __forceinline__ int dc_wout(const DCNode &nd, int pp) { return pp ? nd.par : 1; }
+__device__ __forceinline__ double *dc_Q(const DCBatch &b, int blk, int w) { return w ? b.Qb[blk] : b.Qa[blk]; }
+__device__ __forceinline__ double *dc_d(const DCBatch &b, int blk, int w) { return w ? b.d2[blk] : b.d[blk]; }
 
 // ---- tear ------------------------------------------------------------------------------------------
 __global__ void k_dc_tear(DCBatch b, const DCNode *__restrict__ nodes, int nnodes, double *__restrict__ rho) {
@@ -59,7 +74,7 @@ __global__ void k_dc_tear(DCBatch b, const DCNode *__restrict__ nodes, int nnode
 
 // ---- leaves: implicit QL with eigenvectors, one wavefront per leaf -------------------------------------
 __global__ __launch_bounds__(64) void k_dc_leaf(DCBatch b, const DCNode *__restrict__ leaves, int nleaves,
-                                                int *__restrict__ status) {
+                                                int *__restrict__ status, int pp) {
   __shared__ double ds[DC_LEAF], es[DC_LEAF], zt[DC_LEAF][DC_LEAF + 1];
   int li = blockIdx.x;
   if (li >= nleaves) return;
@@ -135,9 +150,14 @@ __global__ __launch_bounds__(64) void k_dc_leaf(DCBatch b, const DCNode *__restr
     double v = ds[lane];
     int rk = 0;
     for (int j = 0; j < s; j++) rk += (ds[j] < v) || (ds[j] == v && j < lane);
-    d[lo + rk] = v;
-    double *Q = b.Qa[lf.blk];
-    for (int k = 0; k < s; k++) Q[(size_t)(lo + rk) * ld + lo + k] = zt[lane][k];
+    const int wl = pp ? lf.par : 0;  // a leaf writes where its parent reads
+    dc_d(b, lf.blk, wl)[lo + rk] = v;
+    double *Q = dc_Q(b, lf.blk, wl) + (size_t)(lo + rk) * ld;
+    for (int k = 0; k < s; k++) Q[lo + k] = zt[lane][k];
+    if (pp) {
+      for (int r = lf.plo; r < lo; r++) Q[r] = 0.0;
+      for (int r = lf.hi; r < lf.phi; r++) Q[r] = 0.0;
+    }
   }
 }
 
@@ -147,7 +167,7 @@ __global__ __launch_bounds__(256) void k_dc_prepare(DCBatch b, const DCNode *__r
                                                     const double *__restrict__ rho_all, int node0,
                                                     int *__restrict__ kcount, int *__restrict__ nrot,
                                                     double *__restrict__ rho_eff, GemmTask *__restrict__ tasks,
-                                                    double *__restrict__ gscratch, size_t gstride) {
+                                                    double *__restrict__ gscratch, size_t gstride, int pp) {
   // work arrays of the node: LDS, or -- for merges whose arrays exceed it (n > ~5000) -- a slice of a global buffer
   // (same code: a workgroup's global stores are visible to its own threads behind __syncthreads)
   extern __shared__ double lds_[];
@@ -168,8 +188,8 @@ __global__ __launch_bounds__(256) void k_dc_prepare(DCBatch b, const DCNode *__r
   __shared__ double red[8];
   __shared__ double tol_sh;
   __shared__ int k_sh;
-  const double *d = b.d[blk];
-  const double *Q = b.Qa[blk];
+  const double *d = dc_d(b, blk, dc_win(nd, pp));
+  const double *Q = dc_Q(b, blk, dc_win(nd, pp));
   const double rs = rho_all[ni];
   const double sgn = (rs >= 0.0) ? 1.0 : -1.0;
   const double rho = 2.0 * fabs(rs);
@@ -377,9 +397,16 @@ __global__ __launch_bounds__(256) void k_dc_prepare(DCBatch b, const DCNode *__r
     nrot[ni] = nr;
     rho_eff[ni] = rho;
     GemmTask t;
-    t.A = b.Qg[blk] + (size_t)lo * ld + lo;
+    if (pp) {  // non-deflated columns of the children's Q through acol, every root's vector to its ranked column through ccol
+      t.A = Q + lo;
+      t.C = dc_Q(b, blk, dc_wout(nd, pp)) + lo;
+      t.amap = b.acol[blk] + lo;
+      t.cmap = b.ccol[blk] + lo;
+    } else {
+      t.A = b.Qg[blk] + (size_t)lo * ld + lo;
+      t.C = b.Qn[blk] + (size_t)lo * ld + lo;
+    }
     t.B = b.U[blk] + (size_t)lo * ld + lo;
-    t.C = b.Qn[blk] + (size_t)lo * ld + lo;
     t.M = n;
     t.N = k;
     t.K = k;
@@ -426,6 +453,7 @@ __global__ __launch_bounds__(256) void k_dc_prepare(DCBatch b, const DCNode *__r
     int sidx = snd[c];
     b.ndpos[blk][lo + sidx] = c;
     b.nd[blk][lo + c] = sidx;
+    b.acol[blk][lo + c] = lo + ssrc[sidx];
     b.dnd[blk][lo + c] = sD[sidx];
     b.znd[blk][lo + c] = sz[sidx];
   }
@@ -433,7 +461,7 @@ __global__ __launch_bounds__(256) void k_dc_prepare(DCBatch b, const DCNode *__r
 
 // ---- step 2: Givens rotations of the deflation on the columns of Q -----------------------------------
 __global__ __launch_bounds__(256) void k_dc_rotate(DCBatch b, const DCNode *__restrict__ nodes, int node0,
-                                                   const int *__restrict__ nrot) {
+                                                   const int *__restrict__ nrot, int pp) {
   const int ni = node0 + blockIdx.y;
   const DCNode nd = nodes[ni];
   const int nr = nrot[ni];
@@ -446,7 +474,7 @@ __global__ __launch_bounds__(256) void k_dc_rotate(DCBatch b, const DCNode *__re
   __shared__ int scp[256], scj[256];
   __shared__ double sc[256], ss[256];
   const int *src = b.src[blk] + lo;
-  double *Q = b.Qa[blk] + lo + r;
+  double *Q = dc_Q(b, blk, dc_win(nd, pp)) + lo + r;
   for (int t0 = 0; t0 < nr; t0 += 256) {
     const int t = t0 + threadIdx.x;
     if (t < nr) {
@@ -565,11 +593,10 @@ __global__ __launch_bounds__(256) void k_dc_secular(DCBatch b, const DCNode *__r
 }
 
 // ---- step 4: Gu-Eisenstat z-hat, one wavefront per component ---------------------------------------------
-__global__ __launch_bounds__(256) void k_dc_zhat(DCBatch b, const DCNode *__restrict__ nodes, int node0,
-                                                 const int *__restrict__ kcount, const double *__restrict__ rho_eff) {
-  const int ni = node0 + blockIdx.y;
+__device__ __forceinline__ void dc_zhat_body(const DCBatch &b, const DCNode *__restrict__ nodes, int ni, int bx,
+                                             const int *__restrict__ kcount, const double *__restrict__ rho_eff) {
   const int k = kcount[ni];
-  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int j = bx * 4 + (threadIdx.x >> 6);
   if (j >= k) return;
   const int lane = threadIdx.x & 63;
   const DCNode nd = nodes[ni];
@@ -588,13 +615,16 @@ __global__ __launch_bounds__(256) void k_dc_zhat(DCBatch b, const DCNode *__rest
     b.zhat[blk][lo + j] = (b.znd[blk][lo + j] >= 0.0) ? zh : -zh;
   }
 }
+__global__ __launch_bounds__(256) void k_dc_zhat(DCBatch b, const DCNode *__restrict__ nodes, int node0,
+                                                 const int *__restrict__ kcount, const double *__restrict__ rho_eff) {
+  dc_zhat_body(b, nodes, node0 + blockIdx.y, blockIdx.x, kcount, rho_eff);
+}
 
 // ---- step 5: U(:,i) = zhat / (d - lam_i), normalised; one wavefront per column -----------------------------
-__global__ __launch_bounds__(256) void k_dc_U(DCBatch b, const DCNode *__restrict__ nodes, int node0,
-                                              const int *__restrict__ kcount) {
-  const int ni = node0 + blockIdx.y;
+__device__ __forceinline__ void dc_U_body(const DCBatch &b, const DCNode *__restrict__ nodes, int ni, int bx,
+                                          const int *__restrict__ kcount) {
   const int k = kcount[ni];
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int i = bx * 4 + (threadIdx.x >> 6);
   if (i >= k) return;
   const int lane = threadIdx.x & 63;
   const DCNode nd = nodes[ni];
@@ -610,6 +640,42 @@ __global__ __launch_bounds__(256) void k_dc_U(DCBatch b, const DCNode *__restric
   s = 1.0 / sqrt(wave_sum(s));
   double *Ucol = b.U[blk] + (size_t)(lo + i) * ld + lo;
   for (int j = lane; j < k; j += 64) Ucol[j] = zh[j] / ((d[j] - dorg) - mui) * s;
+}
+__global__ __launch_bounds__(256) void k_dc_U(DCBatch b, const DCNode *__restrict__ nodes, int node0,
+                                              const int *__restrict__ kcount) {
+  dc_U_body(b, nodes, node0 + blockIdx.y, blockIdx.x, kcount);
+}
+
+// Default path: U and, in the same launch, the columns the product does not write.  Workgroups [0, nU) of a node form U;
+// workgroup nU + g * nPx + q handles 256 rows of the output columns of the sorted slots [g DC_PSL, (g + 1) DC_PSL) over the
+// parent's row range: a deflated slot's (rotated) source column inside the node's rows, zeros outside them for every slot.
+// (One workgroup per slot launched 9188 x 3 workgroups at the top level of 3 x 1400, nearly all of which found a
+// non-deflated slot of a root -- nothing to write -- and left.)
+constexpr int DC_PSL = 8;
+__global__ __launch_bounds__(256) void k_dc_U_place(DCBatch b, const DCNode *__restrict__ nodes, int node0,
+                                                    const int *__restrict__ kcount, int nU, int nPx) {
+  const int ni = node0 + blockIdx.y;
+  if ((int)blockIdx.x < nU) {
+    dc_U_body(b, nodes, ni, blockIdx.x, kcount);
+    return;
+  }
+  const DCNode nd = nodes[ni];
+  const int q = blockIdx.x - nU, s0 = (q / nPx) * DC_PSL;
+  const int blk = nd.blk, lo = nd.lo, hi = nd.hi;
+  if (s0 >= hi - lo) return;
+  const int r = nd.plo + (q % nPx) * 256 + threadIdx.x;
+  if (r >= nd.phi) return;
+  const int ld = b.n[blk];
+  const bool inside = r >= lo && r < hi;
+  double *qout = dc_Q(b, blk, dc_wout(nd, 1));
+  const double *qin = dc_Q(b, blk, dc_win(nd, 1));
+  const int s1 = min(s0 + DC_PSL, hi - lo);
+  for (int s = s0; s < s1; s++) {  // (s, and with it rank, flag and src, are uniform over the workgroup)
+    const bool defl = b.flag[blk][lo + s] != 0;
+    if (inside && !defl) continue;
+    const double v = inside ? qin[(size_t)(lo + b.src[blk][lo + s]) * ld + r] : 0.0;
+    qout[(size_t)(lo + b.rank[blk][lo + s]) * ld + r] = v;
+  }
 }
 
 // ---- step 6: gather the non-deflated columns of Q ---------------------------------------------------------
@@ -631,24 +697,23 @@ __global__ void k_dc_gather(DCBatch b, const DCNode *__restrict__ nodes, int nod
 }
 
 // ---- step 8: final order of the node's eigenvalues --------------------------------------------------------
-__global__ __launch_bounds__(256) void k_dc_rank(DCBatch b, const DCNode *__restrict__ nodes, int node0,
-                                                 const int *__restrict__ kcount) {
+__device__ __forceinline__ void dc_rank_body(const DCBatch &b, const DCNode *__restrict__ nodes, int ni, int slice,
+                                             double *__restrict__ sh, int pp) {
   // grid (node, slice): every workgroup stages the node's n values in LDS, then ranks its own slice of 32 of them, eight
   // lanes per value (each counts over an eighth of the list, the counts are summed by DPP)
   // (one workgroup per node left the top merges, n ~ 1400, with three busy CUs for 250 us; one thread per value and 256
   // values per workgroup 104 us: every thread walked the whole list)
-  extern __shared__ double sh[];  // values[n]
-  const int ni = node0 + blockIdx.x;
+  // sh: values[n]
   const DCNode nd = nodes[ni];
   const int blk = nd.blk, lo = nd.lo, n = nd.hi - nd.lo;
-  if ((int)blockIdx.y * 32 >= n) return;
+  if (slice * 32 >= n) return;
   // value of sorted slot s: the new root if s is non-deflated (position ndpos[s] in the nd list), else the deflated Ds[s]
   const int *flag = b.flag[blk] + lo;
   for (int s = threadIdx.x; s < n; s += blockDim.x) {
     sh[s] = flag[s] ? b.Ds[blk][lo + s] : b.lam[blk][lo + b.ndpos[blk][lo + s]];
   }
   __syncthreads();
-  const int s = blockIdx.y * 32 + (threadIdx.x >> 3), part = threadIdx.x & 7;
+  const int s = slice * 32 + (threadIdx.x >> 3), part = threadIdx.x & 7;
   const int per = (n + 7) >> 3, j0 = part * per, j1 = min(n, j0 + per);
   const bool ok = s < n;
   const double v = ok ? sh[s] : 0.0;
@@ -672,8 +737,24 @@ __global__ __launch_bounds__(256) void k_dc_rank(DCBatch b, const DCNode *__rest
   rk += __builtin_amdgcn_update_dpp(0, rk, 0x141, 0xf, 0xf, true);  // the other quad of the eight (row_half_mirror)
   if (ok && part == 0) {
     b.rank[blk][lo + s] = rk;
-    b.d2[blk][lo + rk] = v;
+    dc_d(b, blk, dc_wout(nd, pp))[lo + rk] = v;
+    if (pp && !flag[s]) b.ccol[blk][lo + b.ndpos[blk][lo + s]] = lo + rk;
   }
+}
+__global__ __launch_bounds__(256) void k_dc_rank(DCBatch b, const DCNode *__restrict__ nodes, int node0,
+                                                 const int *__restrict__ kcount) {
+  extern __shared__ double sh[];
+  dc_rank_body(b, nodes, node0 + blockIdx.x, blockIdx.y, sh, 0);
+}
+// Default path: z-hat and the final order in one launch -- both need all roots of the node and nothing of each other.
+// Workgroups [0, nZ) of a node form z-hat, the others rank a slice of 32 values each.
+__global__ __launch_bounds__(256) void k_dc_zhat_rank(DCBatch b, const DCNode *__restrict__ nodes, int node0,
+                                                      const int *__restrict__ kcount, const double *__restrict__ rho_eff,
+                                                      int nZ) {
+  extern __shared__ double sh[];
+  const int ni = node0 + blockIdx.y;
+  if ((int)blockIdx.x < nZ) dc_zhat_body(b, nodes, ni, blockIdx.x, kcount, rho_eff);
+  else dc_rank_body(b, nodes, ni, blockIdx.x - nZ, sh, 1);
 }
 
 __global__ void k_dc_scatter(DCBatch b, const DCNode *__restrict__ nodes, int node0, const int *__restrict__ kcount) {
@@ -720,8 +801,10 @@ __global__ void k_dc_copyback(DCBatch b, const DCNode *__restrict__ nodes, int n
 
 // ---- batched FP64 MFMA GEMM over device-side task descriptors (C = A B, column-major) ----------------------------
 void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);  // gemm.hip
+void gemm_tasklist64_map_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
+// (honours the column maps of a task, GemmTask::amap / cmap, like k_dgemm_tasklist_map)
 __global__ __launch_bounds__(256) void k_dgemm_tasks(const GemmTask *__restrict__ tasks) {
   constexpr int BM = 64, BN = 64, BK = 16, PAD = 16;
   __shared__ double As[BK][BM + PAD];
@@ -745,7 +828,7 @@ __global__ __launch_bounds__(256) void k_dgemm_tasks(const GemmTask *__restrict_
       int e = tid + 256 * r;
       int m = e % BM, kk = e / BM;
       int gm = bm + m, gk = k0 + kk;
-      As[kk][m] = (gm < M && gk < K) ? t.A[(size_t)gk * t.lda + gm] : 0.0;
+      As[kk][m] = (gm < M && gk < K) ? t.A[(size_t)(t.amap ? t.amap[gk] : gk) * t.lda + gm] : 0.0;
       int k2 = e % BK, n2 = e / BK;
       int gn = bn + n2, gk2 = k0 + k2;
       Bs[k2][n2] = (gn < N && gk2 < K) ? t.B[(size_t)gn * t.ldb + gk2] : 0.0;
@@ -764,7 +847,7 @@ __global__ __launch_bounds__(256) void k_dgemm_tasks(const GemmTask *__restrict_
     for (int j = 0; j < 2; j++)
       for (int r = 0; r < 4; r++) {
         int gm = bm + wm + i * 16 + l15, gn = bn + wn + j * 16 + l4 + 4 * r;
-        if (gm < M && gn < N) t.C[(size_t)gn * t.ldc + gm] = acc[i][j][r];
+        if (gm < M && gn < N) t.C[(size_t)(t.cmap ? t.cmap[gn] : gn) * t.ldc + gm] = acc[i][j][r];
       }
 }
 
@@ -784,7 +867,7 @@ struct DCWork {
   DevBuf<double> prep_scratch;  // work arrays of k_dc_prepare for merges too large for LDS
   DevBuf<double> d2[DC_MAXB], Qb[DC_MAXB], U[DC_MAXB], Qg[DC_MAXB], Qn[DC_MAXB];
   DevBuf<double> vec[DC_MAXB];  // 9 double vectors of length n
-  DevBuf<int> ivec[DC_MAXB];    // 7 int vectors of length n
+  DevBuf<int> ivec[DC_MAXB];    // 10 int vectors of length n
   DevBuf<DCNode> nodes;
   DevBuf<double> rho, rho_eff;
   DevBuf<int> kcount, nrot, status;
@@ -793,6 +876,7 @@ struct DCWork {
   std::vector<DCNode> hnodes;
   std::vector<int> level_off;  // nodes of height h>=1 are hnodes[level_off[h-1] .. level_off[h])
   std::vector<int> level_maxn;
+  std::vector<int> level_maxp;  // largest parent range of the level's nodes
   int nleaves = 0;
 };
 static std::map<hfg_ctx *, DCWork *> g_dc;
@@ -804,11 +888,15 @@ void dc_release(hfg_ctx *ctx) {
   }
 }
 
-static int build_tree(int blk, int lo, int hi, std::vector<std::vector<DCNode> > &byheight) {
+static int build_tree(int blk, int lo, int hi, int depth, int plo, int phi, std::vector<std::vector<DCNode> > &byheight) {
   DCNode nd;
   nd.blk = blk;
   nd.lo = lo;
   nd.hi = hi;
+  nd.par = depth & 1;
+  nd.plo = plo;
+  nd.phi = phi;
+  nd.pad = 0;
   if (hi - lo <= DC_LEAF) {
     nd.mid = lo;
     if (byheight.empty()) byheight.resize(1);
@@ -817,7 +905,7 @@ static int build_tree(int blk, int lo, int hi, std::vector<std::vector<DCNode> >
   }
   int mid = lo + (hi - lo) / 2;
   nd.mid = mid;
-  int h = 1 + std::max(build_tree(blk, lo, mid, byheight), build_tree(blk, mid, hi, byheight));
+  int h = 1 + std::max(build_tree(blk, lo, mid, depth + 1, lo, hi, byheight), build_tree(blk, mid, hi, depth + 1, lo, hi, byheight));
   if ((int)byheight.size() <= h) byheight.resize(h + 1);
   byheight[h].push_back(nd);
   return h;
@@ -839,17 +927,22 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
   std::vector<int> key(ns, ns + nblk);
   if (key != w.key) {
     std::vector<std::vector<DCNode> > byh;
-    for (int b = 0; b < nblk; b++) build_tree(b, 0, ns[b], byh);
+    for (int b = 0; b < nblk; b++) build_tree(b, 0, ns[b], 0, 0, ns[b], byh);
     w.hnodes.clear();
     w.level_off.clear();
     w.level_maxn.clear();
+    w.level_maxp.clear();
     w.hnodes.insert(w.hnodes.end(), byh[0].begin(), byh[0].end());
     w.nleaves = (int)byh[0].size();
     for (size_t h = 1; h < byh.size(); h++) {
       w.level_off.push_back((int)w.hnodes.size());
-      int mx = 0;
-      for (auto &nd : byh[h]) mx = std::max(mx, nd.hi - nd.lo);
+      int mx = 0, mp = 0;
+      for (auto &nd : byh[h]) {
+        mx = std::max(mx, nd.hi - nd.lo);
+        mp = std::max(mp, nd.phi - nd.plo);
+      }
       w.level_maxn.push_back(mx);
+      w.level_maxp.push_back(mp);
       w.hnodes.insert(w.hnodes.end(), byh[h].begin(), byh[h].end());
     }
     w.level_off.push_back((int)w.hnodes.size());
@@ -866,6 +959,7 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
   }
   DCBatch b;
   int nmax = 0;
+  const int pp = tuning().dc_levels ? 0 : 1;
   for (int i = 0; i < nblk; i++) {
     int n = ns[i];
     nmax = std::max(nmax, n);
@@ -873,10 +967,12 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
     w.d2[i].resize(n);
     w.Qb[i].resize(nn);
     w.U[i].resize(nn);
-    w.Qg[i].resize(nn);
-    w.Qn[i].resize(nn);
+    if (!pp) {
+      w.Qg[i].resize(nn);
+      w.Qn[i].resize(nn);
+    }
     w.vec[i].resize((size_t)9 * n);
-    w.ivec[i].resize((size_t)8 * n);
+    w.ivec[i].resize((size_t)10 * n);
     b.n[i] = n;
     b.d[i] = d[i];
     b.d2[i] = w.d2[i].p;
@@ -905,14 +1001,16 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
     b.rotj[i] = iv + 5 * n;
     b.rank[i] = iv + 6 * n;
     b.ndpos[i] = iv + 7 * n;
-    HFG_HIP_CHECK(hipMemsetAsync(Z[i], 0, sizeof(double) * nn, s));
+    b.acol[i] = iv + 8 * n;
+    b.ccol[i] = iv + 9 * n;
+    if (!pp) HFG_HIP_CHECK(hipMemsetAsync(Z[i], 0, sizeof(double) * nn, s));
   }
   HFG_HIP_CHECK(hipMemsetAsync(w.status.p, 0, sizeof(int) * 4, s));
   const int ninternal = (int)w.hnodes.size() - w.nleaves;
   if (ninternal > 0)
     hipLaunchKernelGGL(k_dc_tear, dim3((ninternal + 255) / 256), dim3(256), 0, s, b, w.nodes.p + w.nleaves, ninternal,
                        w.rho.p + w.nleaves);
-  hipLaunchKernelGGL(k_dc_leaf, dim3(w.nleaves), dim3(64), 0, s, b, w.nodes.p, w.nleaves, w.status.p);
+  hipLaunchKernelGGL(k_dc_leaf, dim3(w.nleaves), dim3(64), 0, s, b, w.nodes.p, w.nleaves, w.status.p, pp);
   const int nlevels = (int)w.level_off.size() - 1;
   for (int h = 0; h < nlevels; h++) {
     const int node0 = w.level_off[h], nn = w.level_off[h + 1] - node0;
@@ -928,23 +1026,40 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
     } else if (shb > 64 * 1024)
       HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_dc_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
     hipLaunchKernelGGL(k_dc_prepare, dim3(nn), dim3(256), shb, s, b, w.nodes.p, w.rho.p, node0, w.kcount.p, w.nrot.p,
-                       w.rho_eff.p, w.tasks.p, gscr, gstride);
-    hipLaunchKernelGGL(k_dc_rotate, dim3((mx + 255) / 256, nn), dim3(256), 0, s, b, w.nodes.p, node0, w.nrot.p);
+                       w.rho_eff.p, w.tasks.p, gscr, gstride, pp);
+    hipLaunchKernelGGL(k_dc_rotate, dim3((mx + 255) / 256, nn), dim3(256), 0, s, b, w.nodes.p, node0, w.nrot.p, pp);
     hipLaunchKernelGGL(k_dc_secular, dim3((mx + 3) / 4, nn), dim3(256), 0, s, b, w.nodes.p, node0, w.kcount.p,
                        w.rho_eff.p);
+    size_t shr = (size_t)mx * sizeof(double);
+    if (pp) {
+      // six launches per level and one pass over Q: the order of the roots is known before the product, which then reads
+      // its A columns where they lie and stores every new vector at its ranked column of the other buffer
+      const int nZ = (mx + 3) / 4, nPx = (w.level_maxp[h] + 255) / 256;
+      if (shr > 64 * 1024)
+        HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_dc_zhat_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shr));
+      hipLaunchKernelGGL(k_dc_zhat_rank, dim3(nZ + (mx + 31) / 32, nn), dim3(256), shr, s, b, w.nodes.p, node0, w.kcount.p,
+                         w.rho_eff.p, nZ);
+      hipLaunchKernelGGL(k_dc_U_place, dim3(nZ + nPx * ((mx + DC_PSL - 1) / DC_PSL), nn), dim3(256), 0, s, b, w.nodes.p, node0, w.kcount.p, nZ,
+                         nPx);
+      // HELFEM_DC_GEMM=small: the first 64 x 64 kernel (it reads the same maps) as the checker of the mapped tile engine
+      if (tuning().dc_gemm_small)
+        hipLaunchKernelGGL(k_dgemm_tasks, dim3(((mx + 63) / 64) * ((mx + 63) / 64), nn), dim3(256), 0, s, w.tasks.p);
+      else
+        gemm_tasklist64_map_dev(ctx, w.tasks.p, nn, mx, mx);
+      continue;
+    }
     hipLaunchKernelGGL(k_dc_zhat, dim3((mx + 3) / 4, nn), dim3(256), 0, s, b, w.nodes.p, node0, w.kcount.p, w.rho_eff.p);
     hipLaunchKernelGGL(k_dc_U, dim3((mx + 3) / 4, nn), dim3(256), 0, s, b, w.nodes.p, node0, w.kcount.p);
     hipLaunchKernelGGL(k_dc_gather, dim3((mx + 255) / 256, mx, nn), dim3(256), 0, s, b, w.nodes.p, node0, w.kcount.p);
     // Q <- Q U of every node of the level: the tile engine of gemm.hip (16-byte staging loads, conflict-free LDS rows, two
     // workgroups per CU).  The small kernel below, which this call replaced, spent 68 % of its LDS cycles in bank
     // conflicts (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, profiles/r03_gemm_sq_counters_bench_step.txt): its B tile is
-    // read along k and stored transposed.  HELFEM_DC_GEMM=small keeps it as the checker.
+    // read along k and stored transposed.  HELFEM_DC_GEMM=small keeps it as the checker, on this path and on the default one.
     if (tuning().dc_gemm_small) {
       int tiles = ((mx + 63) / 64) * ((mx + 63) / 64);
       hipLaunchKernelGGL(k_dgemm_tasks, dim3(tiles, nn), dim3(256), 0, s, w.tasks.p);
     } else
       gemm_tasklist64_dev(ctx, w.tasks.p, nn, mx, mx);
-    size_t shr = (size_t)mx * sizeof(double);
     if (shr > 64 * 1024)
       HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_dc_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shr));
     hipLaunchKernelGGL(k_dc_rank, dim3(nn, (mx + 31) / 32), dim3(256), shr, s, b, w.nodes.p, node0, w.kcount.p);

@@ -1341,14 +1341,7 @@ void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs,
     eig_sym_batch(ctx, w, nb, ns.data(), Xptr);
     {
       ProfScope ps(ctx, "eig_backtransform");
-      {
-        ProfScope pp3(ctx, "eig_products");
-        const GemmTask *last = w.gtasks.p + (w.folded ? 3 : 2) * (size_t)nb;
-        if (w.tile64) gemm_tasklist64_dev(ctx, last, nb, nm, nm);
-        else if (w.split_full) gemm_tasklist_split2_dev(ctx, last, nb, nm, nm);  // the block slots were zeroed above
-        else if (tuning().gemm_rect) gemm_tasklist_rect_dev(ctx, last, nb, nm, nm);
-        else gemm_tasklist_dev(ctx, last, nb, nm, nm);
-      }
+      // the eigenvalues are final: their copy into the slots goes ahead of the last product, not behind it
       std::vector<const double *> csrc;
       std::vector<double *> cdst;
       std::vector<int> cn;
@@ -1360,6 +1353,14 @@ void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs,
         cn.push_back(ns[k]);
       }
       copy_slices(s, csrc, cdst, cn);
+      {
+        ProfScope pp3(ctx, "eig_products");
+        const GemmTask *last = w.gtasks.p + (w.folded ? 3 : 2) * (size_t)nb;
+        if (w.tile64) gemm_tasklist64_dev(ctx, last, nb, nm, nm);
+        else if (w.split_full) gemm_tasklist_split2_dev(ctx, last, nb, nm, nm);  // the block slots were zeroed above
+        else if (tuning().gemm_rect) gemm_tasklist_rect_dev(ctx, last, nb, nm, nm);
+        else gemm_tasklist_dev(ctx, last, nb, nm, nm);
+      }
     }
     check_status(ctx, w, nb);
   }

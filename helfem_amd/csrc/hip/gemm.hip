@@ -46,11 +46,14 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 // before the first store: interleaved "load, scale, store" through the bounds branches serialises 64 memory round
 // trips per thread, which made the rank-2NB trailing updates and the compact-WY updates of the eigensolver (K = 32
 // or 64: pure streaming of C) run at 1.2-1.6 TB/s.
-template <int BM, int BN, bool ACC = false, int MF = 1>
+// MAP: column maps (GemmTask::amap, cmap; op(A) = A): column k of A is read at A[:, amap[k]], column j of the product is
+// stored at C[:, cmap[j]]
+template <int BM, int BN, bool ACC = false, int MF = 1, bool MAP = false>
 __device__ __forceinline__ void dgemm_tile(int id, int transA, int transB, int M, int N, int K, double alpha,
                                            const double *__restrict__ A, int lda, const double *__restrict__ B, int ldb,
                                            double beta, double *__restrict__ C, int ldc, double (*As)[16][BM + 16],
-                                           double (*Bs)[16][BN + 16], int sym = 0, int kbeg = 0, int kend = -1, int over = 0) {
+                                           double (*Bs)[16][BN + 16], int sym = 0, int kbeg = 0, int kend = -1, int over = 0,
+                                           const int *__restrict__ amap = nullptr, const int *__restrict__ cmap = nullptr) {
   constexpr int BK = 16;
   constexpr int PAD = 16;
   constexpr int WM = BM / 2, WN = BN / 2;  // wave tile
@@ -148,12 +151,30 @@ __device__ __forceinline__ void dgemm_tile(int id, int transA, int transB, int M
   const int a_m = tid % BM, a_kv = tid / BM;               // kind K: row a_m, k pair a_kv + r * (256 / BM)
   const int b_nv = tid % (BN / 2), b_kc = tid / (BN / 2);
   const int b_n = tid % BN, b_kv = tid / BN;
-  const double *pA = transA ? A + (size_t)(bm + a_m) * lda + 2 * a_kv : A + (size_t)a_kc * lda + bm + 2 * a_mv;
+  const double *pA = MAP ? A + bm + 2 * a_mv : transA ? A + (size_t)(bm + a_m) * lda + 2 * a_kv : A + (size_t)a_kc * lda + bm + 2 * a_mv;
   const double *pB = transB ? B + (size_t)b_kc * ldb + bn + 2 * b_nv : B + (size_t)(bn + b_n) * ldb + 2 * b_kv;
   d2_t va[VA], vb[VB];
   auto load_tiles = [&](int k0) {
     const bool fullk = (k0 + BK <= K);
-    if (fastA && fullk) {
+    if constexpr (MAP) {
+      // the thread's columns of this k step through the map (a full step on the 16-byte path: every index is below K)
+      if (fastA && fullk) {
+#pragma unroll
+        for (int r = 0; r < VA; r++) va[r] = *reinterpret_cast<const d2_t *>(pA + (size_t)amap[k0 + a_kc + r * (512 / BM)] * lda);
+      } else {
+#pragma unroll
+        for (int r = 0; r < VA; r++) {
+          const int gm0 = bm + 2 * a_mv, gk = k0 + a_kc + r * (512 / BM);
+          d2_t v = (d2_t){0.0, 0.0};
+          if (gk < K) {
+            const double *col = A + (size_t)amap[gk] * lda;
+            if (gm0 < M) v.x = col[gm0];
+            if (gm0 + 1 < M) v.y = col[gm0 + 1];
+          }
+          va[r] = v;
+        }
+      }
+    } else if (fastA && fullk) {
       if (!transA) {
 #pragma unroll
         for (int r = 0; r < VA; r++) va[r] = *reinterpret_cast<const d2_t *>(pA + (size_t)(k0 + r * (512 / BM)) * lda);
@@ -321,7 +342,9 @@ __device__ __forceinline__ void dgemm_tile(int id, int transA, int transB, int M
       for (int r = 0; r < 4; r++) {
         int gm = bm + wm + i * 16 + l15, gn = bn + wn + j * 16 + l4 + 4 * r;
         if (gm < M && gn < N) {
-          size_t o = (size_t)gn * ldc + gm;
+          size_t o;
+          if constexpr (MAP) o = (size_t)cmap[gn] * ldc + gm;
+          else o = (size_t)gn * ldc + gm;
           double v = alpha * acc(i, j, r);
           if (splitk) {
             unsafeAtomicAdd(&C[o], v);
@@ -355,6 +378,19 @@ __global__ __launch_bounds__(256, 2) void k_dgemm_tasklist(const GemmTask *__res
   if ((int)blockIdx.x >= nt) return;
   dgemm_tile<BM, BN, ACC, MF>(blockIdx.x, t.tA, t.tB, t.M, t.N, t.K, t.alpha, t.A, t.lda, t.B, t.ldb, t.beta, t.C, t.ldc,
                               As, Bs, sym, 0, -1, t.over);
+}
+
+// the 64 x 64 tiles with the column maps of the tasks (products without transposes, beta == 0)
+template <int MF = 1>
+__global__ __launch_bounds__(256, 2) void k_dgemm_tasklist_map(const GemmTask *__restrict__ tasks) {
+  __shared__ __attribute__((aligned(16))) double As[2][16][64 + 16];
+  __shared__ __attribute__((aligned(16))) double Bs[2][16][64 + 16];
+  const GemmTask t = tasks[blockIdx.y];
+  if (t.M <= 0 || t.N <= 0) return;
+  const int nt = ((t.M + 63) / 64) * ((t.N + 63) / 64);
+  if ((int)blockIdx.x >= nt) return;
+  dgemm_tile<64, 64, false, MF, true>(blockIdx.x, 0, 0, t.M, t.N, t.K, t.alpha, t.A, t.lda, t.B, t.ldb, 0.0, t.C, t.ldc, As, Bs, 0,
+                                      0, -1, 0, t.amap, t.cmap);
 }
 
 // Task lists with an explicit workgroup list (task, tile), dealt out so that each XCD takes ONE contiguous eighth of the
@@ -465,6 +501,16 @@ void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int m
   const int tiles = ((maxM + 63) / 64) * ((maxN + 63) / 64);
   if (mfma4()) hipLaunchKernelGGL((k_dgemm_tasklist<64, 64, false, 0>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
   else hipLaunchKernelGGL((k_dgemm_tasklist<64, 64>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
+  HFG_HIP_CHECK(hipGetLastError());
+}
+
+/// the same for tasks with column maps (GemmTask::amap and cmap set in every active task)
+void gemm_tasklist64_map_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN) {
+  if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
+  ProfScope ps(ctx, "gemm");
+  const int tiles = ((maxM + 63) / 64) * ((maxN + 63) / 64);
+  if (mfma4()) hipLaunchKernelGGL((k_dgemm_tasklist_map<0>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
+  else hipLaunchKernelGGL((k_dgemm_tasklist_map<1>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
   HFG_HIP_CHECK(hipGetLastError());
 }
 

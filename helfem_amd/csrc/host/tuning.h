@@ -48,6 +48,7 @@ enum class TrdMode { persistent, chain, twokernel, unblocked };
   X(trdf_c, int, -1, "HELFEM_TRDF_C", false, "int", atoi(e), "measurement replay of k_trdf only: column-in-panel index forced for every launch (negative: each launch's own)") \
   X(tridiag_ql, bool, false, "HELFEM_TRIDIAG", false, "=ql", !strcmp(e, "ql"), "one-lane implicit QL for the tridiagonal problem instead of divide and conquer (checker)") \
   X(dc_gemm_small, bool, false, "HELFEM_DC_GEMM", false, "=small", !strcmp(e, "small"), "Q U of the divide-and-conquer merges by the first 64 x 64 kernel instead of the tile engine (checker)") \
+  X(dc_levels, bool, false, "HELFEM_DC", false, "=levels", !strcmp(e, "levels"), "divide-and-conquer merges with the gather, scatter and copy-back passes over Q and ten launches per level (checker of the column-mapped product)") \
   X(dc_dbg, bool, false, "HELFEM_DC_DBG", false, "present", true, "merge statistics of divide and conquer on stderr") \
   X(bt_column, bool, false, "HELFEM_BT", false, "=column", !strcmp(e, "column"), "back-transformation reflector by reflector instead of compact WY (checker)") \
   X(bt_fold, bool, true, "HELFEM_BT_FOLD", false, "off if 0", atoi(e) != 0, "X Q formed on the side stream beside divide and conquer; off: Z <- Q Z on the main stream behind it") \
