@@ -659,7 +659,7 @@ def lobatto_nodes(n):
     return x
 
 
-def xc_eval(func_id, rho, sigma=None, lapl=None, tau=None, nspin=1, thr=0.0):
+def xc_eval(func_id, rho, sigma=None, lapl=None, tau=None, nspin=1, thr=0.0, pars=None):
     """one functional at points, libxc's xc_mgga_exc_vxc layout (hfg_xc_eval; host only, no device): nspin 1 takes arrays of
     shape (np,), nspin 2 rho, lapl, tau of shape (np, 2) and sigma of shape (np, 3) (aa, ab, bb).  Returns a dict with exc
     (per particle) and vrho, vsigma, vlapl, vtau in the shapes of the inputs."""
@@ -676,11 +676,24 @@ def xc_eval(func_id, rho, sigma=None, lapl=None, tau=None, nspin=1, thr=0.0):
     out = {"exc": np.zeros(npt)}
     for k, src in (("vrho", "rho"), ("vsigma", "sigma"), ("vlapl", "lapl"), ("vtau", "tau")):
         out[k] = np.zeros(shp[src])
+    if pars is not None and len(pars):
+        pv = np.ascontiguousarray(pars, dtype=np.float64)
+        f = lib().hfg_xc_eval_ext
+        f.argtypes = [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [c_double_p] * 9 + [ctypes.c_double]
+        _check(f(int(func_id), _p(pv), len(pv), nspin, npt, _p(rho), _p(ins["sigma"]), _p(ins["lapl"]), _p(ins["tau"]),
+                 _p(out["exc"]), _p(out["vrho"]), _p(out["vsigma"]), _p(out["vlapl"]), _p(out["vtau"]), float(thr)))
+        return out
     f = lib().hfg_xc_eval
     f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [c_double_p] * 9 + [ctypes.c_double]
     _check(f(int(func_id), nspin, npt, _p(rho), _p(ins["sigma"]), _p(ins["lapl"]), _p(ins["tau"]), _p(out["exc"]),
              _p(out["vrho"]), _p(out["vsigma"]), _p(out["vlapl"]), _p(out["vtau"]), float(thr)))
     return out
+
+
+def xc_eval_ext(func_id, pars, rho, sigma=None, lapl=None, tau=None, nspin=1, thr=0.0):
+    """xc_eval with the external parameters of the functional for this call (hfg_xc_eval_ext): lda_x [alpha], gga_x_pbe
+    [kappa, mu], gga_c_pbe [beta, gamma, BB], gga_x_ityh / gga_x_sfat / gga_x_ityh_pbe / gga_x_sfat_pbe [omega]"""
+    return xc_eval(func_id, rho, sigma, lapl, tau, nspin, thr, pars=pars)
 
 
 def xc_func_ids(method):
@@ -707,6 +720,14 @@ def xc_exact_exchange(x_func):
     f.argtypes = [ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 3
     _check(f(int(x_func), ctypes.byref(o), ctypes.byref(a), ctypes.byref(b)))
     return o.value, a.value, b.value
+
+
+def xc_rs_kind(x_func):
+    """screened kernel of an exchange id (hfg_xc_rs_kind): 0 none, 1 Yukawa, 2 erfc -- the rs_kind of compute_rs_tei"""
+    f = lib().hfg_xc_rs_kind
+    f.argtypes = [ctypes.c_int]
+    f.restype = ctypes.c_int
+    return int(f(int(x_func)))
 
 
 def scf_set_iguess(iguess):

@@ -26,6 +26,9 @@ void model_potential_dev(hfg_ctx *ctx, hfg_basis *basis, int kind1, int Z1, doub
 void fock_release(hfg_dev_tables *t);
 void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double *sigma, const double *lapl, const double *tau,
                   double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau, double thr);
+void xc_eval_host_ext(int id, const double *pars, int npars, int nspin, size_t np, const double *rho, const double *sigma,
+                      const double *lapl, const double *tau, double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau,
+                      double thr);
 size_t fock_compact_size(hfg_basis *basis);
 void fock_compact_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dFc,
                       double *dScal, double thr);
@@ -837,6 +840,15 @@ int hfg_xc_eval(int func_id, int nspin, int64_t np, const double *rho, const dou
   HFG_CATCH
 }
 
+int hfg_xc_eval_ext(int func_id, const double *pars, int n_pars, int nspin, int64_t np, const double *rho, const double *sigma,
+                    const double *lapl, const double *tau, double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau,
+                    double thr) {
+  HFG_TRY
+  if (np < 0) throw std::logic_error("hfg_xc_eval_ext: negative point count\n");
+  xc_eval_host_ext(func_id, pars, n_pars, nspin, (size_t)np, rho, sigma, lapl, tau, exc, vrho, vsigma, vlapl, vtau, thr);
+  HFG_CATCH
+}
+
 int hfg_xc_func_ids(const char *method, int *x_func, int *c_func) {
   HFG_TRY
   if (!method || !x_func || !c_func) throw std::logic_error("hfg_xc_func_ids: null argument\n");
@@ -851,6 +863,12 @@ int hfg_xc_exact_exchange(int x_func, double *omega, double *alpha, double *beta
   if (!omega || !alpha || !beta) throw std::logic_error("hfg_xc_exact_exchange: null argument\n");
   helfem::range_separation(x_func, *omega, *alpha, *beta);
   HFG_CATCH
+}
+
+int hfg_xc_rs_kind(int x_func) {
+  bool erf, yuk;
+  helfem::is_range_separated(x_func, erf, yuk);
+  return yuk ? 1 : (erf ? 2 : 0);
 }
 
 int hfg_basis_radial_table(const hfg_basis *b, int which, int iel, double *out, int64_t *rows, int64_t *cols) {

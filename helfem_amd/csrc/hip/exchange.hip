@@ -278,7 +278,9 @@ void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, 
   hfg_dev_tables *t = rs ? basis->dev_rs : basis->dev;
   if (!t || !t->have_tei) throw std::logic_error("Primitive teis have not been computed!\n");
   if (basis->dev_device != ctx->device) throw std::logic_error("basis tables live on a different device\n");
-  ProfScope ps(ctx, "exchange");
+  // the screened builds of the range-separated hybrids are timed under names of their own, so that a profile shows which kernel
+  // a functional ran and what the second build of an iteration costs
+  ProfScope ps(ctx, !rs ? "exchange" : (t->rs_kind == 1 ? "exchange_yukawa" : "exchange_erfc"));
   // fast path for the low-rank densities of SCF runs (exchange_lr.hip); HELFEM_EXCHANGE=general forces the
   // general kernels below, which take any symmetric P
   if (!helfem::tuning_live().exchange_general && exchange_lowrank_dev(ctx, t, dP, dK, Lknown, rknown)) return;  // (read at every call)

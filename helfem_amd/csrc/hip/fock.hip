@@ -1359,8 +1359,8 @@ void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const do
 }
 
 /// External functional parameters for the following XC builds on this stream (NULL / 0: the functional's defaults).
-/// Supported: lda_x {alpha}, gga_x_pbe {kappa, mu}, gga_c_pbe {beta, gamma, BB} -- libxc's parameter lists; anything
-/// else throws (std::runtime_error, as libxc's "number of parameters" check does through the reference).
+/// Supported: lda_x {alpha}, gga_x_pbe {kappa, mu}, gga_c_pbe {beta, gamma, BB}, and {omega} of gga_x_ityh, gga_x_sfat,
+/// gga_x_ityh_pbe, gga_x_sfat_pbe -- libxc's parameter lists; anything else throws (std::runtime_error, as libxc's "number of parameters" check does through the reference).
 void set_xc_params(hfg_ctx *ctx, int x_func, const double *x_pars, int nx, int c_func, const double *c_pars, int nc) {
   xc::XCPar par = HFG_XCPAR_DEFAULTS;
   if (nx > 0 && !x_pars) throw std::runtime_error("Exchange functional parameters missing.\n");
@@ -1368,7 +1368,10 @@ void set_xc_params(hfg_ctx *ctx, int x_func, const double *x_pars, int nx, int c
   helfem::check_xc_params(x_func, nx, c_func, nc);
   if (nx > 0) {
     if (x_func == 1) par.x_alpha = x_pars[0];
-    else {
+    else if (xc::is_rsgga_x(x_func)) {
+      if (!(x_pars[0] > 0.0)) throw std::runtime_error("The range-separation constant omega must be positive.\n");
+      par.x_omega = x_pars[0];
+    } else {
       par.x_kappa = x_pars[0];
       par.x_mu = x_pars[1];
     }
@@ -1448,6 +1451,38 @@ void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double 
     out(vtau, 2 * i, vta);
     out(vtau, 2 * i + 1, vtb);
   }
+}
+
+/// xc_eval_host with external parameters for this call (hfg_xc_eval_ext): pars as set_xc_params takes them for the id as an
+/// exchange (lda_x, gga_x_pbe, the short-range GGA primitives) or correlation (gga_c_pbe) functional
+void xc_eval_host_ext(int id, const double *pars, int npars, int nspin, size_t np, const double *rho, const double *sigma,
+                      const double *lapl, const double *tau, double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau,
+                      double thr) {
+  if (npars > 0 && !pars) throw std::runtime_error("Functional parameters missing.\n");
+  xc::XCPar par = HFG_XCPAR_DEFAULTS;
+  if (npars > 0) {
+    if (id == 130) {
+      helfem::check_xc_params(0, 0, id, npars);
+      par.c_beta = pars[0];
+      par.c_gamma = pars[1];
+      par.c_BB = pars[2];
+    } else {
+      helfem::check_xc_params(id, npars, 0, 0);
+      if (id == 1) par.x_alpha = pars[0];
+      else if (xc::is_rsgga_x(id)) {
+        if (!(pars[0] > 0.0)) throw std::runtime_error("The range-separation constant omega must be positive.\n");
+        par.x_omega = pars[0];
+      } else {
+        par.x_kappa = pars[0];
+        par.x_mu = pars[1];
+      }
+    }
+  }
+  struct Reset {  // the defaults come back whatever happens
+    ~Reset() { xc::host_xcpar() = xc::XCPar HFG_XCPAR_DEFAULTS; }
+  } reset;
+  xc::host_xcpar() = par;
+  xc_eval_host(id, nspin, np, rho, sigma, lapl, tau, exc, vrho, vsigma, vlapl, vtau, thr);
 }
 
 void xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dH, double *dScal,

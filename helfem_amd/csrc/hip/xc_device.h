@@ -79,20 +79,25 @@ __host__ __device__ inline Dual derf(Dual a) {
 // dftgrid.cpp:405-410), in libxc's order: lda_x {alpha = 1}, gga_x_pbe {kappa = 0.8040, mu = beta pi^2/3},
 // gga_c_pbe {beta = 0.06672455060314922, gamma = (1 - ln 2)/pi^2, BB = 1}.  One constant-memory copy per translation
 // unit (this header is included by fock.hip only); set_xc_params() there fills it before the grid kernels are launched.
+// x_omega: the range-separation constant of the short-range GGA exchange primitives (gga_x_ityh, gga_x_sfat and their PBE
+// forms, libxc's {_omega}); negative: the functional's own default.
 struct XCPar {
-  double x_alpha, x_kappa, x_mu, c_beta, c_gamma, c_BB;
+  double x_alpha, x_kappa, x_mu, c_beta, c_gamma, c_BB, x_omega;
 };
 #define HFG_XCPAR_DEFAULTS \
-  { 1.0, 0.8040, 0.06672455060314922 * HFG_PI * HFG_PI / 3.0, 0.06672455060314922, (1.0 - 0.6931471805599453) / (HFG_PI * HFG_PI), 1.0 }
+  { 1.0, 0.8040, 0.06672455060314922 * HFG_PI * HFG_PI / 3.0, 0.06672455060314922, (1.0 - 0.6931471805599453) / (HFG_PI * HFG_PI), 1.0, -1.0 }
 static __constant__ XCPar c_xcpar = HFG_XCPAR_DEFAULTS;
-// the parameters as the point code reads them: the constant-memory copy on the device; the defaults in a host build of the
-// same code (hfg_xc_eval), which takes no external parameters
+// the parameters as the point code reads them: the constant-memory copy on the device; in a host build of the same code
+// (hfg_xc_eval, hfg_xc_eval_ext) a per-thread copy that holds the defaults unless hfg_xc_eval_ext has set it for its call
+inline XCPar &host_xcpar() {
+  static thread_local XCPar h = HFG_XCPAR_DEFAULTS;
+  return h;
+}
 __host__ __device__ inline const XCPar &xcpar() {
 #if defined(__HIP_DEVICE_COMPILE__)
   return c_xcpar;
 #else
-  static const XCPar h = HFG_XCPAR_DEFAULTS;
-  return h;
+  return host_xcpar();
 #endif
 }
 
@@ -242,14 +247,20 @@ __host__ __device__ inline Dual eps_gga_c_pbe(Dual rho, Dual sigma, double beta,
   return ec + H;
 }
 
+// gga_x_ityh_pbe / gga_x_sfat_pbe: the integer ids are libxc's as recalled, not confirmed against libxc itself;
+// the names are the interface
+#define HFG_ID_ITYH_PBE 623
+#define HFG_ID_SFAT_PBE 601
 __host__ __device__ inline bool is_gga(int id) {
   return id == 101 || id == 130 || id == 406 || id == 202 || id == 231 || id == 106 || id == 131 || id == 402 || id == 206 ||
-         id == 72 || id == 102 || id == 116 || id == 133 || id == 263 || id == 264 || id == 267;
+         id == 72 || id == 102 || id == 116 || id == 133 || id == 263 || id == 264 || id == 267 || id == 529 || id == 530 ||
+         id == HFG_ID_ITYH_PBE || id == HFG_ID_SFAT_PBE || id == 433 || id == 470 || id == 455 || id == 468 || id == 467;
 }
 __host__ __device__ inline bool is_supported(int id) {
   return id == 1 || id == 7 || id == 8 || id == 12 || id == 13 || id == 101 || id == 130 || id == 406 || id == 202 || id == 231 ||
          id == 546 || id == 641 || id == 178 || id == 106 || id == 131 || id == 402 || id == 206 || id == 72 || id == 102 || id == 116 ||
-         id == 133 || id == 263 || id == 264 || id == 267;
+         id == 133 || id == 263 || id == 264 || id == 267 || id == 529 || id == 530 || id == HFG_ID_ITYH_PBE ||
+         id == HFG_ID_SFAT_PBE || id == 433 || id == 470 || id == 455 || id == 468 || id == 467;
 }
 
 __host__ __device__ inline bool is_exchange(int id) {
@@ -911,7 +922,92 @@ __host__ __device__ inline T scan_eps_c(T n, T z, T sig, T tau) {
   return ec1 + scan_switch(alpha, 0.64, 1.5, 0.7) * (ec0 - ec1);
 }
 
-__host__ __device__ inline bool is_ext(int id) { return id == 263 || id == 264 || id == 267 || id == 102 || id == 116 || id == 133; }
+// ---------------------------------------------------------------------------------------------------------
+// Short-range GGA exchange of the range-separated GGA hybrids, in the construction of Iikura, Tsuneda, Yanai, Hirao (J. Chem.
+// Phys. 115, 3540 (2001); erfc kernel) and of Savin, Flad / Akinaga, Ten-no (Chem. Phys. Lett. 462, 348 (2008); Yukawa kernel,
+// used by Seth, Ziegler, J. Chem. Theory Comput. 8, 901 (2012)) for an enhancement factor F_x(s).  For an unpolarised density
+// (polarised by spin scaling, E_x[a,b] = (E_x[2a] + E_x[2b])/2):
+//   k_GGA = k_F / sqrt(F_x(s)),  k_F = (3 pi^2 rho)^{1/3},  a = omega / (2 k_GGA),  eps_x^sr = eps_x^LDA(rho) F_x(s) att(a)
+// with att = att_erf / att_yukawa of eps_lda_x_sr, to which this reduces for F_x = 1.  B88's F_x grows without bound in the
+// density tail (x / (6 asinh x)), so a is large there and the attenuation comes from its series branch.
+// Primitives (omega: libxc's default, or the external parameter x_omega): gga_x_ityh (529; B88, erfc, 0.2), gga_x_sfat (530;
+// B88, Yukawa, 0.44), gga_x_ityh_pbe (HFG_ID_ITYH_PBE; PBE, erfc, 0.2), gga_x_sfat_pbe (HFG_ID_SFAT_PBE; PBE, Yukawa, 0.44).
+// Hybrids, 1/r = [1 - alpha - beta erf(omega r)]/r + [alpha + beta erf(omega r)]/r (erfc; the Yukawa ones with exp(-omega r)
+// in place of erfc): DFT exchange (1 - alpha - beta) X + beta X^sr(omega); the drivers add (alpha + beta) K - beta K^sr.
+//   hyb_gga_xc_cam_b3lyp  (433; Yanai, Tew, Handy, Chem. Phys. Lett. 393, 51 (2004)): erfc, (0.19, 0.46, 0.33),
+//                          0.35 B88 + 0.46 ITYH-B88 + 0.19 lda_c_vwn + 0.81 gga_c_lyp
+//   hyb_gga_xc_camy_b3lyp (470; Seth, Ziegler): Yukawa, (0.19, 0.46, 0.34), 0.35 B88 + 0.46 SFAT-B88 + 0.19 lda_c_vwn + 0.81 gga_c_lyp
+//   hyb_gga_xc_camy_blyp  (455; Akinaga, Ten-no): Yukawa, (0.20, 0.80, 0.44), 0.80 SFAT-B88 + gga_c_lyp
+//   hyb_gga_xc_lcy_blyp   (468): Yukawa, (0, 1, 0.75), SFAT-B88 + gga_c_lyp
+//   hyb_gga_xc_lcy_pbe    (467): Yukawa, (0, 1, 0.75), SFAT-PBE + gga_c_pbe
+// Like the is_ext functionals these ids are evaluated by eval_add_ext / eval_add_ext_pol alone.
+// ---------------------------------------------------------------------------------------------------------
+/// B88's enhancement factor over eps_lda_x, F = 1 + (beta/Cx) t / (1 + 6 beta x asinh x) with t = x^2 of one spin channel
+__host__ __device__ inline Dual fx_b88(Dual rho, Dual sigma) {
+  const double beta = 0.0042, Cx = 0.9305257363491000;
+  Dual rs = 0.5 * rho;
+  Dual r43 = rs * dcbrt(rs);
+  Dual t = (0.25 * sigma) / (r43 * r43);
+  return 1.0 + (beta / Cx) * t / (1.0 + (6.0 * beta) * d_x_asinh_x(t));
+}
+__host__ __device__ inline Dual fx_pbe(Dual rho, Dual sigma, double kappa, double mu) {
+  Dual kf = dcbrt((3.0 * HFG_PI * HFG_PI) * rho);
+  Dual s2 = sigma / (4.0 * kf * kf * rho * rho);
+  return 1.0 + kappa - kappa / (1.0 + (mu / kappa) * s2);
+}
+__host__ __device__ inline bool is_rsgga_x(int id) { return id == 529 || id == 530 || id == HFG_ID_ITYH_PBE || id == HFG_ID_SFAT_PBE; }
+__host__ __device__ inline bool is_rsgga_hyb(int id) { return id == 433 || id == 470 || id == 455 || id == 468 || id == 467; }
+/// exchange part of a short-range GGA primitive or hybrid: eps_x^LDA F_x [wx + wsr att(a)].  Always inlined: as a device function
+/// of its own it would renumber the local labels of every kernel behind it in the module, and the kernels of the other
+/// functionals are kept identical to what they were, text included.
+__host__ __device__ __attribute__((always_inline)) inline Dual eps_rsgga_x(int id, Dual rho, Dual sigma) {
+  double wx = 0.0, wsr = 1.0, omega;
+  int kind = 1;
+  bool pbe = false;
+  switch (id) {
+    case 529: kind = 2; omega = 0.2; break;
+    case 530: omega = 0.44; break;
+    case HFG_ID_ITYH_PBE: kind = 2; pbe = true; omega = 0.2; break;
+    case HFG_ID_SFAT_PBE: pbe = true; omega = 0.44; break;
+    case 433: kind = 2; wx = 0.35; wsr = 0.46; omega = 0.33; break;
+    case 470: wx = 0.35; wsr = 0.46; omega = 0.34; break;
+    case 455: wsr = 0.80; omega = 0.44; break;
+    case 467: pbe = true; omega = 0.75; break;
+    default: omega = 0.75; break;  // 468
+  }
+  if (is_rsgga_x(id) && xcpar().x_omega >= 0.0) omega = xcpar().x_omega;
+  Dual F = pbe ? fx_pbe(rho, sigma, 0.8040, HFG_PBE_MU) : fx_b88(rho, sigma);
+  Dual kf = dcbrt((3.0 * HFG_PI * HFG_PI) * rho);
+  Dual a = (0.5 * omega) * dsqrt(F) / kf;
+  Dual Fatt;  // F_x att(a)
+  if (a.v > (kind == 1 ? 2.0 : 0.75)) {
+    // The series branch of att_erf / att_yukawa, as att(a) = u g(u) with u = 1/a^2 = 4 k_F^2 / (omega^2 F_x): the leading term of
+    // F_x att is 4 k_F^2 / (36 or 9 omega^2), free of F_x.  Taken as the product F_x * att(a), the sigma derivative would be the
+    // difference of two terms that cancel to 1/a^2 of their size, which is 1e-5 and less in the density tail.
+    Dual ua = (4.0 / (omega * omega)) * kf * kf;  // u F_x
+    Dual u = ua / F, g = mk(0.0);
+    if (kind == 1) {
+      Dual r = mk(1.0);
+      for (int k = 1; k <= 40; k++) {
+        g = g + r * (2.0 / ((2.0 * k + 1.0) * (k + 1.0) * (k + 2.0)));
+        r = -1.0 * r * u;
+      }
+    } else {
+      Dual r = mk(-0.25);
+      for (int k = 1; k <= 24; k++) {
+        g = g - r * (2.0 / ((2.0 * k + 1.0) * (k + 1.0) * (k + 2.0)));
+        r = r * u * (-0.25 / (k + 1.0));
+      }
+    }
+    Fatt = ua * g;
+  } else
+    Fatt = F * (kind == 1 ? att_yukawa(a) : att_erf(a));
+  return eps_lda_x(rho) * (wx * F + wsr * Fatt);
+}
+
+__host__ __device__ inline bool is_ext(int id) {
+  return id == 263 || id == 264 || id == 267 || id == 102 || id == 116 || id == 133 || is_rsgga_x(id) || is_rsgga_hyb(id);
+}
 __host__ __device__ inline double ext_pbe_kappa(int id) { return id == 102 ? 1.245 : 0.804; }
 __host__ __device__ inline double ext_pbe_mu(int id) { return id == 102 ? HFG_PBE_MU : 10.0 / 81.0; }
 
@@ -920,6 +1016,19 @@ __host__ __device__ inline double ext_pbe_mu(int id) { return id == 102 ? HFG_PB
 __host__ __device__ inline void eval_add_ext(int id, double rho, double sigma, double tau, bool live, double &exc, double &vrho,
                                              double &vsigma, double &vtau) {
   if (!live && is_exchange(id)) return;
+  if (is_rsgga_x(id) || is_rsgga_hyb(id)) {
+    if (!live && is_rsgga_x(id)) return;
+    Dual r = mk(rho, 1.0, 0.0), s = mk(sigma, 0.0, 1.0);
+    Dual e = live ? eps_rsgga_x(id, r, s) : mk(0.0);  // the hybrids keep their correlation part
+    if (id == 433 || id == 470) e = e + 0.19 * eps_lda_c_vwn(r) + 0.81 * eps_gga_c_lyp(r, s);
+    else if (id == 455 || id == 468) e = e + eps_gga_c_lyp(r, s);
+    else if (id == 467) e = e + eps_gga_c_pbe(r, s, 0.06672455060314922, HFG_PBE_GAMMA, 1.0);
+    Dual en = r * e;
+    exc += e.v;
+    vrho += en.dr;
+    vsigma += en.ds;
+    return;
+  }
   if (id == 102 || id == 116 || id == 133) {
     Dual r = mk(rho, 1.0, 0.0), s = mk(sigma, 0.0, 1.0);
     Dual e = id == 133 ? eps_gga_c_pbe(r, s, 0.046, HFG_PBE_GAMMA, 1.0) : eps_gga_x_pbe(r, s, ext_pbe_kappa(id), ext_pbe_mu(id));
@@ -945,6 +1054,53 @@ __host__ __device__ inline void eval_add_ext_pol(int id, double ra, double rb, d
                                                  double tb, bool live_a, bool live_b, double &exc, double &va, double &vb,
                                                  double &vsaa, double &vsab, double &vsbb, double &vta, double &vtb) {
   const double rt = ra + rb;
+  if (is_rsgga_x(id) || is_rsgga_hyb(id)) {  // exchange by spin scaling; the correlation of the hybrids from the basic evaluators
+    Dual na = mk(0.0), nb = mk(0.0);
+    if (live_a) {
+      Dual a = mk(2.0 * ra, 1.0, 0.0);
+      na = a * eps_rsgga_x(id, a, mk(4.0 * saa, 0.0, 1.0));
+    }
+    if (live_b) {
+      Dual b = mk(2.0 * rb, 1.0, 0.0);
+      nb = b * eps_rsgga_x(id, b, mk(4.0 * sbb, 0.0, 1.0));
+    }
+    exc += 0.5 * (na.v + nb.v) / rt;
+    va += na.dr;
+    vb += nb.dr;
+    vsaa += 2.0 * na.ds;
+    vsbb += 2.0 * nb.ds;
+    if (id == 467) {
+      T3 a = t3(ra, 1.0, 0.0, 0.0), b = t3(rb, 0.0, 1.0, 0.0), st = t3(saa + 2.0 * sab + sbb, 0.0, 0.0, 1.0);
+      T3 n = a + b;
+      T3 e = pol_eps_pbe_c(n, tcbrt((3.0 / (4.0 * HFG_PI)) / n), (a - b) / n, st, 0.06672455060314922, HFG_PBE_GAMMA, 1.0);
+      T3 en = n * e;
+      exc += e.v;
+      va += en.a;
+      vb += en.b;
+      vsaa += en.s;
+      vsab += 2.0 * en.s;
+      vsbb += en.s;
+    } else if (is_rsgga_hyb(id)) {
+      const bool b3 = id == 433 || id == 470;
+      double e_ = 0.0, a_ = 0.0, b_ = 0.0, x_ = 0.0, y_ = 0.0, z_ = 0.0;
+      eval_add_pol_basic(131, ra, rb, saa, sab, sbb, live_a, live_b, e_, a_, b_, x_, y_, z_);
+      const double wl = b3 ? 0.81 : 1.0;
+      exc += wl * e_;
+      va += wl * a_;
+      vb += wl * b_;
+      vsaa += wl * x_;
+      vsab += wl * y_;
+      vsbb += wl * z_;
+      if (b3) {
+        e_ = a_ = b_ = x_ = y_ = z_ = 0.0;
+        eval_add_pol_basic(7, ra, rb, saa, sab, sbb, live_a, live_b, e_, a_, b_, x_, y_, z_);
+        exc += 0.19 * e_;
+        va += 0.19 * a_;
+        vb += 0.19 * b_;
+      }
+    }
+    return;
+  }
   if (id == 102 || id == 116) {  // spin scaling, as gga_x_pbe in eval_add_pol_basic
     Dual na = mk(0.0), nb = mk(0.0);
     if (live_a) {

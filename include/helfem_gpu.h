@@ -176,7 +176,12 @@ int hfg_rs_exchange(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *K);
  * the caller adds 0.5 K - 0.25 K_erfc(omega = 1/3)), 206 mgga_x_br89 and 72 mgga_c_cs (these two depend on the density
  * Laplacian: atomic bases only, a diatomic basis fails with "Laplacian not implemented!"), 263 mgga_x_scan, 267 mgga_c_scan,
  * 264 hyb_mgga_x_scan0 (DFT part: 0.75 mgga_x_scan; the caller adds 0.25 K), 102 gga_x_pbe_r (revPBE), 116 gga_x_pbe_sol,
- * 133 gga_c_pbe_sol; <=0 none.  The spin-polarised
+ * 133 gga_c_pbe_sol; the short-range GGA exchange primitives 529 gga_x_ityh (B88, erfc, omega = 0.2), 530 gga_x_sfat (B88,
+ * Yukawa, omega = 0.44), 623 gga_x_ityh_pbe, 601 gga_x_sfat_pbe (the same with PBE's enhancement factor; these two integer ids
+ * are not confirmed against libxc, the names are the interface), and the DFT parts of the range-separated GGA hybrids 433
+ * hyb_gga_xc_cam_b3lyp, 470 hyb_gga_xc_camy_b3lyp, 455 hyb_gga_xc_camy_blyp, 468 hyb_gga_xc_lcy_blyp, 467 hyb_gga_xc_lcy_pbe
+ * (the caller adds alpha K + beta K_screened of hfg_xc_exact_exchange, the screened kernel being that of hfg_xc_rs_kind);
+ * <=0 none.  The spin-polarised
  * entry takes the same ids. */
 int hfg_xc_fock(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *P, double *H, double *Exc,
                 double *Nel, double *Ekin, double dens_thr);
@@ -186,8 +191,9 @@ int hfg_xc_fock_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, cons
                     double *Ha, double *Hb, double *Exc, double *Nel, double *Ekin, double dens_thr);
 /* The same with the reference's full argument list (dftgrid.h:179/181): x_pars / c_pars are the external functional
  * parameters of --x_pars / --c_pars (xc_func_set_ext_params in the reference, dftgrid.cpp:405-410).  Supported: gga_x_pbe
- * (kappa, mu), gga_c_pbe (beta, gamma, B), lda_x (alpha); NULL / 0 keeps the functional's defaults; any other
- * combination is refused with an error rather than ignored. */
+ * (kappa, mu), gga_c_pbe (beta, gamma, B), lda_x (alpha), and (omega > 0) of gga_x_ityh, gga_x_sfat, gga_x_ityh_pbe,
+ * gga_x_sfat_pbe; NULL / 0 keeps the functional's defaults; any other combination is refused with an error rather than
+ * ignored. */
 int hfg_xc_fock_ext(hfg_ctx *ctx, hfg_basis *basis, int x_func, const double *x_pars, int n_x_pars, int c_func,
                     const double *c_pars, int n_c_pars, const double *P, double *H, double *Exc, double *Nel, double *Ekin,
                     double dens_thr);
@@ -201,12 +207,21 @@ int hfg_xc_fock_pol_ext(hfg_ctx *ctx, hfg_basis *basis, int x_func, const double
  * zero, NULL outputs are skipped; functionals without sigma / tau / lapl dependence return zero for those potentials. */
 int hfg_xc_eval(int func_id, int nspin, int64_t np, const double *rho, const double *sigma, const double *lapl, const double *tau,
                 double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau, double dens_thr);
+/* hfg_xc_eval with external parameters of the one functional for this call: pars / n_pars as hfg_xc_fock_ext takes them for
+ * that id (lda_x, gga_x_pbe, gga_c_pbe, omega of the short-range GGA primitives); NULL / 0 is hfg_xc_eval. */
+int hfg_xc_eval_ext(int func_id, const double *pars, int n_pars, int nspin, int64_t np, const double *rho, const double *sigma,
+                    const double *lapl, const double *tau, double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau,
+                    double dens_thr);
 /* --method parsing of the drivers (dftfuncs.cpp:64-118): "x-c" names or numeric ids -> libxc ids; and id -> name */
 int hfg_xc_func_ids(const char *method, int *x_func, int *c_func);
 const char *hfg_xc_func_name(int func_id);
 /* Exact exchange the drivers add for an exchange id (range_separation, dftfuncs.cpp:505): K = alpha K[1/r12] + beta K[screened
- * kernel of range omega]; 1 for HF, 0.25 for hyb_gga_xc_pbeh and hyb_mgga_x_scan0, 0 for the pure functionals */
+ * kernel of range omega]; 1 for HF, 0.25 for hyb_gga_xc_pbeh and hyb_mgga_x_scan0, 0 for the pure functionals; for a CAM
+ * hybrid with 1/r = [1 - a - b s(r)]/r + [a + b s(r)]/r: alpha = a + b, beta = -b (hyb_gga_xc_cam_b3lyp: 0.33, 0.65, -0.46) */
 int hfg_xc_exact_exchange(int x_func, double *omega, double *alpha, double *beta);
+/* The screened kernel of an exchange id (is_range_separated, dftfuncs.cpp:464): 0 none, 1 Yukawa exp(-omega r)/r, 2
+ * erfc(omega r)/r -- the rs_kind hfg_compute_rs_tei needs for the beta term of hfg_xc_exact_exchange */
+int hfg_xc_rs_kind(int x_func);
 /* Radial tables of an atomic basis at the quadrature points of element iel (nquad x Nprim(iel), column-major): which 0 =
  * B/r (RadialBasis::get_bf), 1 = d/dr (B/r) (get_df), 2 = d^2/dr^2 (B/r) (get_lf), 3 = the radial coordinates
  * (nquad x 1).  out = NULL returns the shape only. */
@@ -389,7 +404,8 @@ int hfg_chk_read_diatomic_basis(hfg_chk *chk, int lpad, hfg_basis **basis);
 /* ---- measurement --------------------------------------------------------------------------- */
 /* When enabled, every kernel family is bracketed by hipEvents on the context's stream; the
  * accumulated device time (ms) and launch count per family can be read back after a synchronize.
- * names: "coulomb", "xc", "exchange", "eig_reduce", "eig_tridiag", "eig_tridiag_solve",
+ * names: "coulomb", "xc", "exchange" (the full-range build; "exchange_yukawa" / "exchange_erfc": the screened build of
+ * hfg_rs_exchange and of the range-separated hybrids), "eig_reduce", "eig_tridiag", "eig_tridiag_solve",
  * "eig_backtransform", "gemm", "density", "scatter". */
 int hfg_profile_enable(hfg_ctx *ctx, int on);
 int hfg_profile_reset(hfg_ctx *ctx);
