@@ -47,6 +47,43 @@ class hfg_atomic_desc(ctypes.Structure):
                 ("nang", ctypes.c_int)]
 
 
+class hfg_atomic_desc_ex(ctypes.Structure):
+    _fields_ = [("base", hfg_atomic_desc), ("finitenuc", ctypes.c_int), ("Rrms", ctypes.c_double), ("zeroder", ctypes.c_int),
+                ("Zl", ctypes.c_int), ("Zr", ctypes.c_int), ("Rmid", ctypes.c_double)]
+
+
+class hfg_scf_options(ctypes.Structure):
+    """hfg_scf_options of include/helfem_gpu.h, field by field"""
+    _fields_ = [("program", ctypes.c_int), ("Z1", ctypes.c_int), ("Z2", ctypes.c_int), ("Rbond", ctypes.c_double),
+                ("nela", ctypes.c_int), ("nelb", ctypes.c_int), ("Q", ctypes.c_int), ("M", ctypes.c_int),
+                ("lmmax", ctypes.c_int * 16), ("nlm", ctypes.c_int), ("lmax", ctypes.c_int), ("mmax", ctypes.c_int),
+                ("lpad", ctypes.c_int), ("Rmax", ctypes.c_double), ("grid", ctypes.c_int), ("zexp", ctypes.c_double),
+                ("nelem", ctypes.c_int), ("nnodes", ctypes.c_int), ("nquad", ctypes.c_int), ("maxit", ctypes.c_int),
+                ("convthr", ctypes.c_double), ("diag", ctypes.c_int), ("method", ctypes.c_char * 128), ("ldft", ctypes.c_int),
+                ("mdft", ctypes.c_int), ("dftthr", ctypes.c_double), ("restricted", ctypes.c_int), ("symmetry", ctypes.c_int),
+                ("primbas", ctypes.c_int), ("diiseps", ctypes.c_double), ("diisthr", ctypes.c_double), ("diisorder", ctypes.c_int),
+                ("iguess", ctypes.c_int), ("x_pars", ctypes.c_void_p), ("n_x_pars", ctypes.c_int), ("c_pars", ctypes.c_void_p),
+                ("n_c_pars", ctypes.c_int), ("maverage", ctypes.c_int), ("dampfock", ctypes.c_double), ("dampthr", ctypes.c_double),
+                ("save", ctypes.c_char * 512), ("load", ctypes.c_char * 512), ("Ez", ctypes.c_double), ("Qzz", ctypes.c_double),
+                ("Bz", ctypes.c_double), ("finitenuc", ctypes.c_int), ("readocc", ctypes.c_int), ("occs", ctypes.c_void_p),
+                ("occ_rows", ctypes.c_int), ("occ_cols", ctypes.c_int), ("perturb", ctypes.c_double), ("iconf", ctypes.c_int),
+                ("zeroder", ctypes.c_int), ("verbose", ctypes.c_int)]
+
+
+class hfg_scf_result(ctypes.Structure):
+    _fields_ = [("Etot", ctypes.c_double), ("Ekin", ctypes.c_double), ("Epot", ctypes.c_double), ("Enucr", ctypes.c_double),
+                ("Ecoul", ctypes.c_double), ("Exx", ctypes.c_double), ("Exc", ctypes.c_double), ("iterations", ctypes.c_int),
+                ("converged", ctypes.c_int), ("nela", ctypes.c_int), ("nelb", ctypes.c_int), ("Nbf", ctypes.c_int64),
+                ("tJ", ctypes.c_double), ("tK", ctypes.c_double), ("tXC", ctypes.c_double), ("tdiag", ctypes.c_double)]
+
+
+class hfg_scf_atomic_extras(ctypes.Structure):
+    _fields_ = [("Rrms", ctypes.c_double), ("conf_N", ctypes.c_int), ("conf_R", ctypes.c_double),
+                ("conf_barrier", ctypes.c_double), ("shift_conf", ctypes.c_double), ("add_conf", ctypes.c_int),
+                ("Zl", ctypes.c_int), ("Zr", ctypes.c_int), ("Rmid", ctypes.c_double), ("nelem0", ctypes.c_int),
+                ("grid0", ctypes.c_int), ("zexp0", ctypes.c_double), ("Econf", ctypes.c_double)]
+
+
 def lib():
     """Load the native library (fails loudly if it has not been built)."""
     global _lib
@@ -87,6 +124,14 @@ def lib():
         L.hfg_lobatto_nodes.restype = None
         L.hfg_lobatto_nodes.argtypes = [ctypes.c_int, c_double_p]
         L.hfg_radial_grid.argtypes = [ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p]
+        L.hfg_basis_confinement.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, c_double_p]
+        L.hfg_atomic_grid.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_double, ctypes.c_int, ctypes.c_double, c_double_p, c_int_p]
+        L.hfg_scf_options_check_ex.argtypes = [ctypes.POINTER(hfg_scf_options), ctypes.POINTER(hfg_scf_atomic_extras)]
+        L.hfg_scf_run_ex.argtypes = [ctypes.c_void_p, ctypes.POINTER(hfg_scf_options), ctypes.POINTER(hfg_scf_atomic_extras),
+                                     ctypes.POINTER(hfg_scf_result), c_double_p, c_double_p]
         L.hfg_ctx_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p]
         L.hfg_xc_fock.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
                                   c_double_p, c_double_p, c_double_p, ctypes.c_double]
@@ -378,17 +423,35 @@ def angular_basis(lmax, mmax):
     return list(lv[:n.value]), list(mv[:n.value])
 
 
-class AtomicTwoDBasis(TwoDBasis):
-    """atomic::basis::TwoDBasis (point nucleus) — setup on the host, coulomb/exchange on the GPU."""
+def atomic_grid(nelem, Rmax=40.0, igrid=4, zexp=2.0, finitenuc=0, Rrms=0.0, nelem0=0, igrid0=4, zexp0=2.0, Z=0, Zl=0, Zr=0,
+                Rmid=0.0, add_conf=False, shift_conf=0.0):
+    """atomic::basis::form_grid (src/atomic/basis.cpp:119-172): element boundaries of the atomic program"""
+    cap = int(nelem) + 3 * int(nelem0) + 4
+    b = np.zeros(cap)
+    n = ctypes.c_int(cap)
+    _check(lib().hfg_atomic_grid(int(finitenuc), float(Rrms), int(nelem), float(Rmax), int(igrid), float(zexp), int(nelem0),
+                                 int(igrid0), float(zexp0), int(Z), int(Zl), int(Zr), float(Rmid), 1 if add_conf else 0,
+                                 float(shift_conf), _p(b), ctypes.byref(n)))
+    return b[:n.value].copy()
 
-    def __init__(self, Z, nnodes, nquad, bval, lval, mval, ctx=None):
+
+class AtomicTwoDBasis(TwoDBasis):
+    """atomic::basis::TwoDBasis — setup on the host, coulomb/exchange on the GPU.  finitenuc / Rrms: nuclear model of the
+    central charge (1 Gaussian, 2 uniform sphere, 3 hollow sphere); zeroder: zero derivative at the last grid point; Zl, Zr:
+    point charges at z = -Rmid, +Rmid (on an element boundary)."""
+
+    def __init__(self, Z, nnodes, nquad, bval, lval, mval, ctx=None, finitenuc=0, Rrms=0.0, zeroder=False, Zl=0, Zr=0, Rmid=0.0):
         self._bval = np.ascontiguousarray(bval, dtype=np.float64)
         self._lval = (ctypes.c_int * len(lval))(*lval)
         self._mval = (ctypes.c_int * len(mval))(*mval)
         d = hfg_atomic_desc(int(Z), 4, int(nnodes), int(nquad), _p(self._bval), len(self._bval), self._lval,
                             self._mval, len(lval))
         h = ctypes.c_void_p()
-        _check(lib().hfg_atomic_basis_create(ctypes.byref(d), ctypes.byref(h)))
+        if finitenuc or zeroder or Zl or Zr:
+            dx = hfg_atomic_desc_ex(d, int(finitenuc), float(Rrms), 1 if zeroder else 0, int(Zl), int(Zr), float(Rmid))
+            _check(lib().hfg_atomic_basis_create_ex(ctypes.byref(dx), ctypes.byref(h)))
+        else:
+            _check(lib().hfg_atomic_basis_create(ctypes.byref(d), ctypes.byref(h)))
         self.h = h
         self.ctx = ctx
         self.lval, self.mval = list(lval), list(mval)
@@ -396,6 +459,12 @@ class AtomicTwoDBasis(TwoDBasis):
         dims = [ctypes.c_int64() for _ in range(5)]
         _check(lib().hfg_basis_dims(self.h, *[ctypes.byref(x) for x in dims]))
         self._Nbf, self._Ndummy, self._Nrad, self._Nang, self._Nel = [x.value for x in dims]
+
+    def confinement(self, iconf, N=0, R=0.0, V=0.0, shift=0.0):
+        """TwoDBasis::confinement(N, R, iconf, V, shift) (src/atomic/TwoDBasis.cpp:480)"""
+        out = np.zeros((self._Nbf, self._Nbf), order="F")
+        _check(lib().hfg_basis_confinement(self.h, int(iconf), int(N), float(R), float(V), float(shift), _p(out)))
+        return out
 
     ATOMIC_TABLES = {"prim_tei": 0, "prim_ktei": 4, "disjoint_L": 8, "disjoint_m1L": 10, "disjoint_iL": 12, "disjoint_kL": 13,
                      "rs_tei": 14, "rs_ktei": 15}
@@ -759,6 +828,42 @@ def scf_diatomic(Z1, Z2, Rbond, lmmax, nelem, nnodes, method, nquad=0, Rmax=40.0
     r["converged"] = (out[7] - int(out[7])) > 0.25
     r["tJ"], r["tK"], r["tXC"], r["tdiag"] = out[8:12]
     return r
+
+
+def scf_run_atomic(Z, lmax, mmax, nelem, nnodes, method="HF", ctx=None, check_only=False, E=None, C=None, extras=None, **kw):
+    """One run of the atomic program through hfg_scf_run_ex.  extras: dict of hfg_scf_atomic_extras fields (Rrms, conf_N, conf_R,
+    conf_barrier, shift_conf, add_conf, Zl, Zr, Rmid, nelem0, grid0, zexp0), None for hfg_scf_run's behaviour; kw: fields of
+    hfg_scf_options (finitenuc, iconf, zeroder, symmetry, save, load, ...).  Returns a dict of the result fields plus Econf.
+    check_only: hfg_scf_options_check_ex alone (no device)."""
+    o = hfg_scf_options()
+    _check(lib().hfg_scf_options_default(ctypes.byref(o), 1))
+    o.Z1, o.lmax, o.mmax, o.nelem, o.nnodes = int(Z), int(lmax), int(mmax), int(nelem), int(nnodes)
+    o.method = method.encode()
+    o.verbose = 0
+    o.save = b""
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError("hfg_scf_options has no field %s" % k)
+        setattr(o, k, v.encode() if isinstance(v, str) else v)
+    x = None
+    if extras is not None:
+        x = hfg_scf_atomic_extras()
+        _check(lib().hfg_scf_atomic_extras_default(ctypes.byref(x)))
+        for k, v in extras.items():
+            if not hasattr(x, k):
+                raise TypeError("hfg_scf_atomic_extras has no field %s" % k)
+            setattr(x, k, v)
+    xp = ctypes.byref(x) if x is not None else None
+    if check_only:
+        _check(lib().hfg_scf_options_check_ex(ctypes.byref(o), xp))
+        return None
+    ctx = ctx or default_context()
+    r = hfg_scf_result()
+    _check(lib().hfg_scf_run_ex(ctx.h, ctypes.byref(o), xp, ctypes.byref(r), _p(E) if E is not None else None,
+                                _p(C) if C is not None else None))
+    out = dict((f[0], getattr(r, f[0])) for f in hfg_scf_result._fields_)
+    out["Econf"] = x.Econf if x is not None else 0.0
+    return out
 
 
 def scf_set_occupations(occs=None, readocc=-1):

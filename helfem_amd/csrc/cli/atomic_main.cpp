@@ -77,9 +77,23 @@ int main(int argc, char **argv) {
     hfg_scf_options_default(&o, 1);
     o.Z1 = hfg_get_Z(parser.str("Z").c_str());
     if (o.Z1 < 0) fail(hfg_last_error());
-    if (hfg_get_Z(parser.str("Zl").c_str()) != 0 || hfg_get_Z(parser.str("Zr").c_str()) != 0 || parser.real("Rmid") != 0.0 ||
-        parser.integer("nelem0") != 0)
-      fail("Off-center nuclei (--Zl --Zr --Rmid --nelem0) are not supported by this build.\n");
+    hfg_scf_atomic_extras x;
+    hfg_scf_atomic_extras_default(&x);
+    x.Zl = hfg_get_Z(parser.str("Zl").c_str());
+    if (x.Zl < 0) fail(hfg_last_error());
+    x.Zr = hfg_get_Z(parser.str("Zr").c_str());
+    if (x.Zr < 0) fail(hfg_last_error());
+    x.Rmid = parser.real("Rmid");
+    if (parser.boolean("angstrom")) x.Rmid *= ANGSTROMINBOHR;  // atomic/main.cpp:223-226
+    x.nelem0 = parser.integer("nelem0");
+    x.grid0 = parser.integer("grid0");
+    x.zexp0 = parser.real("zexp0");
+    x.Rrms = parser.real("Rrms");
+    x.conf_N = parser.integer("conf_N");
+    x.conf_R = parser.real("conf_R");
+    x.conf_barrier = parser.real("conf_barrier");
+    x.shift_conf = parser.real("shift_conf");
+    x.add_conf = parser.boolean("add_conf") ? 1 : 0;
     o.nela = parser.integer("nela");
     o.nelb = parser.integer("nelb");
     o.Q = parser.integer("Q");
@@ -148,11 +162,11 @@ int main(int argc, char **argv) {
     printf("Nuclear charge is %i\n", o.Z1);
     fflush(stdout);
 
-    if (hfg_scf_options_check(&o)) fail(hfg_last_error());
+    if (hfg_scf_options_check_ex(&o, &x)) fail(hfg_last_error());
     hfg_ctx *ctx = nullptr;
     if (hfg_ctx_create(&ctx, parser.integer("device"), nullptr)) fail(hfg_last_error());
     hfg_scf_result r;
-    int rc = hfg_scf_run(ctx, &o, &r, nullptr, nullptr);
+    int rc = hfg_scf_run_ex(ctx, &o, &x, &r, nullptr, nullptr);
     if (rc) {
       std::string msg = hfg_last_error();
       hfg_ctx_destroy(ctx);

@@ -7,7 +7,6 @@
 #include <cstring>
 #include <sstream>
 
-#define ANGSTROMINBOHR 1.8897261254578281  // src/general/constants.h
 
 static void fail(const std::string &msg) {
   fprintf(stderr, "%s", msg.c_str());

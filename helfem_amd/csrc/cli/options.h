@@ -10,6 +10,8 @@
 #include <string>
 #include <vector>
 
+#define ANGSTROMINBOHR 1.8897261254578281  // src/general/constants.h
+
 namespace cli {
 
 /// arma::imat::load(raw_ascii): whitespace-separated integers, one row per line, equal row lengths

@@ -6,6 +6,7 @@
 #include "../host/dftfuncs.h"
 #include "tables.h"
 #include <cstring>
+#include <memory>
 #include <mutex>
 
 namespace hfg {
@@ -278,6 +279,42 @@ int hfg_atomic_basis_create(const hfg_atomic_desc *d, hfg_basis **out) {
   b->ab = helfem::atomic::TwoDBasis(d->Z, d->nnodes, d->nquad, helfem::Vec(d->bval, d->bval + d->nbval),
                                     helfem::IVec(d->lval, d->lval + d->nang), helfem::IVec(d->mval, d->mval + d->nang));
   *out = b;
+  HFG_CATCH
+}
+
+static int copy_out(const helfem::Mat &M, double *out);
+
+int hfg_atomic_basis_create_ex(const hfg_atomic_desc_ex *dx, hfg_basis **out) {
+  HFG_TRY
+  const hfg_atomic_desc *d = &dx->base;
+  if (d->primbas != 4) throw std::logic_error("Unsupported primitive basis.\n");
+  if (dx->finitenuc != 0 && (dx->Zl != 0 || dx->Zr != 0))
+    throw std::logic_error("Off-center nuclei not supported in finite nucleus mode!\n");
+  std::unique_ptr<hfg_basis> b(new hfg_basis());
+  b->kind = 1;
+  b->ab = helfem::atomic::TwoDBasis(d->Z, dx->finitenuc, dx->Rrms, dx->zeroder != 0, d->nnodes, d->nquad,
+                                    helfem::Vec(d->bval, d->bval + d->nbval), helfem::IVec(d->lval, d->lval + d->nang),
+                                    helfem::IVec(d->mval, d->mval + d->nang), dx->Zl, dx->Zr, dx->Rmid);
+  *out = b.release();
+  HFG_CATCH
+}
+
+int hfg_basis_confinement(const hfg_basis *b, int iconf, int N, double R, double V, double shift, double *out) {
+  HFG_TRY
+  if (!b->kind) throw std::logic_error("Confinement potentials belong to the atomic program.\n");
+  copy_out(b->ab.confinement(N, R, iconf, V, shift), out);
+  HFG_CATCH
+}
+
+int hfg_atomic_grid(int finitenuc, double Rrms, int nelem, double Rmax, int grid, double zexp, int nelem0, int grid0,
+                    double zexp0, int Z, int Zl, int Zr, double Rmid, int add_conf, double shift_conf, double *bval, int *n) {
+  HFG_TRY
+  helfem::Vec g = helfem::atomic::form_grid(finitenuc, Rrms, nelem, Rmax, grid, zexp, nelem0, grid0, zexp0, Z, Zl, Zr, Rmid,
+                                            add_conf != 0, shift_conf, false);
+  const int cap = *n;
+  *n = (int)g.size();
+  if ((int)g.size() > cap) throw std::logic_error("hfg_atomic_grid: output capacity too small");
+  for (size_t i = 0; i < g.size(); i++) bval[i] = g[i];
   HFG_CATCH
 }
 

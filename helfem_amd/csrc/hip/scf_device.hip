@@ -469,6 +469,8 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
 
   DevSCF d(ctx);
   hipStream_t s = d.s;
+  DevBuf<double> Vconf;  // confinement potential of the atomic program (part of H0); Econf = tr(P Vconf)
+  const int econf_slot = 8 + 3 * std::max(1, opt.diisorder);  // past the DIIS inner products
   {
     Mat S = hb->kind ? hb->ab.overlap() : hb->b.overlap();
     Mat T = hb->kind ? hb->ab.kinetic() : hb->b.kinetic();
@@ -479,6 +481,10 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
     d.up(d.T, T);
     d.up(d.V, V);
     Mat H0 = T + V;
+    if (opt.Vconf) {
+      H0 = H0 + *opt.Vconf;
+      d.up(Vconf, *opt.Vconf);
+    }
     d.up(d.H0, H0);
   }
   const size_t N = d.N, NN = d.NN;
@@ -598,8 +604,13 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
       model_potential_dev(ctx, hb, Za ? 3 : 0, Za, 0.0, 0.0, Zb ? 3 : 0, Zb, 0.0, 0.0, d.T1.p);
     d.axpby(1.0, d.T.p, 1.0, d.T1.p, NN);  // T1 = T + V_model
     Hg = d.T1.p;
-  } else if (verbose)
-    printf("Guess orbitals from core Hamiltonian\n");
+  } else {
+    if (verbose) printf("Guess orbitals from core Hamiltonian\n");
+    if (opt.Hcore_guess) {
+      d.up(d.T1, *opt.Hcore_guess);
+      Hg = d.T1.p;
+    }
+  }
   // forced occupations on the device: S C by one product, the symmetry weights of all orbitals by one small kernel per
   // occupied symmetry, the order on the host from the weights and the energies (the reference's rule), one gather
   DevBuf<double> FdB;  // the beta spin's extrapolated Fock matrix (the alpha one lives in d.T1)
@@ -745,6 +756,7 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
     d.dot(d.P.p, d.T.p, NN, 0);
     d.dot(d.P.p, d.V.p, NN, 1);
     d.dot(d.P.p, d.J.p, NN, 2);
+    if (opt.Vconf) d.dot(d.P.p, Vconf.p, NN, econf_slot);
     if (anyK) {
       d.dot(d.Pa.p, d.Ka.p, NN, 3);
       if (!restr) d.dot(d.Pb.p, d.Kb.p, NN, 4);
@@ -865,6 +877,10 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
         printf("Error in integrated number of electrons % e\n", sc[1] - nel);
       }
     }
+    if (opt.Vconf) {
+      HFG_HIP_CHECK(hipMemcpyAsync(&res.Econf, d.res.p + econf_slot, sizeof(double), hipMemcpyDeviceToHost, s));
+      HFG_HIP_CHECK(hipStreamSynchronize(s));
+    }
     res.Ekin = d.hres[0];
     res.Epot = d.hres[1];
     res.Ecoul = 0.5 * d.hres[2];
@@ -875,7 +891,7 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
       printf("Coulomb energy %.10e % .6f\n", res.Ecoul, res.tJ);
       if (anyK) printf("Exchange energy %.10e % .6f\n", res.Exx, res.tK);
     }
-    res.Etot = res.Ekin + res.Epot + res.Ecoul + res.Exx + res.Exc + res.Enucr;
+    res.Etot = res.Ekin + res.Epot + res.Ecoul + res.Exx + res.Exc + res.Enucr + res.Econf;
     const double dE = res.Etot - Eold;
     mixer.push(res.Etot, diiserr);
     for (int k = 0; k < nh0; k++) {
@@ -966,6 +982,7 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
     down("T", d.T.p, N, N);
     down("Vnuc", d.V.p, N, N);
     down("H0", d.H0.p, N, N);
+    if (opt.Vconf) res.mats["Vconf"] = *opt.Vconf;
     down("Sinvh", d.Sinvh.p, N, N);
     down("P", d.P.p, N, N);
     down("Pa", d.Pa.p, N, N);
@@ -989,6 +1006,7 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
     printf("%-21s energy: % .16f\n", "Coulomb", res.Ecoul);
     printf("%-21s energy: % .16f\n", "Exact exchange", res.Exx);
     printf("%-21s energy: % .16f\n", "Exchange-correlation", res.Exc);
+    if (opt.Vconf) printf("%-21s energy: % .16f\n", "Confinement potential", res.Econf);
     printf("%-21s energy: % .16f\n", "Total", res.Etot);
     printf("%-21s energy: % .16f\n", "Virial ratio", -res.Etot / res.Ekin);
   }

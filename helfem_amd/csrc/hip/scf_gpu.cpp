@@ -169,20 +169,13 @@ helfem::scf::Result run_diatomic_device(hfg_ctx *ctx, const helfem::scf::Options
 }
 
 helfem::scf::Result run_atomic_device(hfg_ctx *ctx, const helfem::scf::AtomicOptions &a) {
-  const helfem::scf::Options &opt = a.common;
-  int nel = a.Z - a.Q;
-  if (nel <= 0) throw std::logic_error("No electrons.\n");
-  int Nquad = opt.nquad;
-  if (Nquad == 0) Nquad = 5 * opt.nnodes;
-  else if (Nquad < 2 * opt.nnodes) throw std::logic_error("Insufficient radial quadrature.\n");
-  helfem::IVec lval, mval;
-  helfem::atomic::angular_basis(a.lmax, a.mmax, lval, mval);
-  helfem::Vec bval = helfem::get_grid(opt.Rmax, opt.nelem, opt.igrid, opt.zexp);
+  helfem::scf::AtomicSetup su = helfem::scf::atomic_setup(a);
+  const helfem::scf::Options &opt = su.common;
   hfg_basis *hb = new hfg_basis();
   helfem::scf::Result r;
   try {
     hb->kind = 1;
-    hb->ab = helfem::atomic::TwoDBasis(a.Z, opt.nnodes, Nquad, bval, lval, mval);
+    hb->ab = su.basis;
     if (opt.verbose)
       printf("Basis set consists of %i angular shells composed of %i radial functions, totaling %i basis functions\n",
              (int)hb->ab.Nang(), (int)hb->ab.Nrad(), (int)hb->ab.Nbf());
@@ -197,7 +190,7 @@ helfem::scf::Result run_atomic_device(hfg_ctx *ctx, const helfem::scf::AtomicOpt
       ldft = mdft = 0;
     std::vector<std::vector<std::vector<size_t> > > avg;
     if (a.maverage) avg = helfem::scf::atomic_average_groups(hb->ab);
-    r = hfg::scf_device_loop(ctx, hb, opt, nel, 0.0, opt.symmetry, hb->ab.get_sym_idx(opt.symmetry), ldft, mdft, avg);
+    r = hfg::scf_device_loop(ctx, hb, opt, su.nel, su.Enucr, su.symm, hb->ab.get_sym_idx(su.symm), ldft, mdft, avg);
   } catch (...) {
     hfg_basis_destroy(hb);
     throw;
@@ -456,7 +449,8 @@ int hfg_scf_options_default(hfg_scf_options *o, int program) {
 
 namespace hfg {
 // what the reference's drivers leave in their checkpoint (diatomic/main.cpp:236-537, 790-963), in its HDF5 layout
-void write_checkpoint(const hfg_scf_options &p, const helfem::scf::Options &o, const helfem::scf::Result &r) {
+void write_checkpoint(const hfg_scf_options &p, const helfem::scf::Options &o, const helfem::scf::Result &r,
+                      const helfem::scf::AtomicOptions *a = nullptr, bool extended = false) {
   helfem::Checkpoint chk(p.save, true);
   chk.write("nela", r.nela);
   chk.write("nelb", r.nelb);
@@ -467,6 +461,8 @@ void write_checkpoint(const hfg_scf_options &p, const helfem::scf::Options &o, c
     const double Rhalf = 0.5 * o.Rbond;
     helfem::Vec bval = helfem::get_grid(helfem::arcosh(o.Rmax / Rhalf), o.nelem, o.igrid, o.zexp);
     chk.write(helfem::diatomic::TwoDBasis(o.Z1, o.Z2, Rhalf, o.nnodes, Nquad, bval, lval, mval, o.lpad));
+  } else if (a && a->extended()) {
+    chk.write(helfem::scf::atomic_setup(*a, true).basis);
   } else {
     helfem::IVec lval, mval;
     helfem::atomic::angular_basis(p.lmax, p.mmax, lval, mval);
@@ -477,6 +473,12 @@ void write_checkpoint(const hfg_scf_options &p, const helfem::scf::Options &o, c
     auto it = r.mats.find(name);
     if (it != r.mats.end()) chk.write(name, it->second);
   }
+  if (p.program == 1 && a && extended) {  // atomic/main.cpp:468, 478: the nuclear attraction matrix under "Vuc", and Vconf
+    auto it = r.mats.find("Vnuc");
+    if (it != r.mats.end()) chk.write("Vuc", it->second);
+    it = r.mats.find("Vconf");
+    chk.write("Vconf", it != r.mats.end() ? it->second : helfem::Mat(r.Nbf, r.Nbf));
+  }
   chk.write("Ekin", r.Ekin);
   chk.write("Epot", r.Epot);
   chk.write("Eefield", 0.0);
@@ -484,6 +486,7 @@ void write_checkpoint(const hfg_scf_options &p, const helfem::scf::Options &o, c
   chk.write("Ecoul", r.Ecoul);
   chk.write("Exx", r.Exx);
   chk.write("Exc", r.Exc);
+  if (p.program == 1 && a && extended) chk.write("Econf", r.Econf);
   chk.write("Etot", r.Etot);
   chk.write("Ea", r.E);
   chk.write("Eb", r.Eb.empty() ? r.E : r.Eb);
@@ -491,17 +494,19 @@ void write_checkpoint(const hfg_scf_options &p, const helfem::scf::Options &o, c
 }
 }  // namespace hfg
 
-static void check_options(const hfg_scf_options &p) {
+// x: the atomic program's extras (hfg_scf_run_ex), with which finite nuclei, confinement and --zeroder are in scope
+static void check_options(const hfg_scf_options &p, const hfg_scf_atomic_extras *x = nullptr) {
     // features outside the hot-path scope: refuse loudly rather than compute something else
+  if (x && p.program != 1) throw std::logic_error("hfg_scf_atomic_extras belongs to the atomic program (program = 1).\n");
   if (p.Ez != 0.0 || p.Qzz != 0.0 || p.Bz != 0.0) throw std::logic_error("External electric / magnetic fields are not supported by this build.\n");
-  if (p.finitenuc != 0) throw std::logic_error("Finite nuclear models are not supported by this build.\n");
+  if (p.finitenuc != 0 && !x) throw std::logic_error("Finite nuclear models are not supported by this build.\n");
   if (p.readocc != 0 && (!p.occs || p.occ_rows <= 0 || p.occ_cols < 3))
     throw std::logic_error(p.program == 0 ? "Must have at least three columns in occupation data.\n"
                                           : "Must have three columns in occupation data to use axial symmetry.\n");
   if (p.perturb != 0.0) throw std::logic_error("Random perturbation of the guess (--perturb) is not supported by this build.\n");
   if (p.primbas != 4) throw std::logic_error("Only the LIP primitive basis (--primbas 4) is supported by this build.\n");
-  if (p.iconf != 0) throw std::logic_error("Confinement potentials (--iconf) are not supported by this build.\n");
-  if (p.zeroder != 0) throw std::logic_error("--zeroder is not supported by this build.\n");
+  if (p.iconf != 0 && !x) throw std::logic_error("Confinement potentials (--iconf) are not supported by this build.\n");
+  if (p.zeroder != 0 && !x) throw std::logic_error("--zeroder is not supported by this build.\n");
   if (p.iguess == 2) throw std::logic_error("Unsupported guess (SAP needs the reference's tabulated potentials)\n");
   if (p.iguess == 1) throw std::logic_error("Unsupported guess (GSZ needs the reference's per-element parameters)\n");
   if (p.iguess != 0 && p.iguess != 3) throw std::logic_error("Unsupported guess\n");
@@ -521,7 +526,7 @@ static void check_options(const hfg_scf_options &p) {
     throw std::logic_error("Laplacian not implemented!\n");  // diatomic dftgrid.cpp:115-116
   helfem::check_xc_params(x_func, p.n_x_pars, c_func, p.n_c_pars);  // before the device: the refusal of set_xc_params
   int nela = p.nela, nelb = p.nelb, Q = p.Q, M = p.M > 0 ? p.M : 1;
-  helfem::scf::parse_nela_nelb(nela, nelb, Q, M, p.program == 0 ? p.Z1 + p.Z2 : p.Z1);
+  helfem::scf::parse_nela_nelb(nela, nelb, Q, M, p.program == 0 ? p.Z1 + p.Z2 : p.Z1 + (x ? x->Zl + x->Zr : 0));
   if (nela + nelb <= 0) throw std::logic_error("No electrons.\n");
   if (p.readocc) {  // diatomic/main.cpp:369-380
     int sa = 0, sb = 0;
@@ -538,11 +543,98 @@ static void check_options(const hfg_scf_options &p) {
   }
 }
 
+// the extras of an atomic run in the driver's own options
+static void apply_extras(const hfg_scf_options &p, const hfg_scf_atomic_extras &x, helfem::scf::AtomicOptions &a) {
+  a.finitenuc = p.finitenuc;
+  a.Rrms = x.Rrms;
+  a.zeroder = p.zeroder != 0;
+  a.Zl = x.Zl;
+  a.Zr = x.Zr;
+  a.Rhalf = x.Rmid;
+  a.nelem0 = x.nelem0;
+  a.igrid0 = x.grid0;
+  a.zexp0 = x.zexp0;
+  a.iconf = p.iconf;
+  a.conf_N = x.conf_N;
+  a.conf_R = x.conf_R;
+  a.conf_barrier = x.conf_barrier;
+  a.shift_conf = x.shift_conf;
+  a.add_conf = x.add_conf != 0;
+}
+
+// hfg_scf_options (and the atomic extras) in the drivers' own options: one mapping for the check and for the run
+static void map_options(const hfg_scf_options &p, const hfg_scf_atomic_extras *x, helfem::scf::AtomicOptions &a) {
+  helfem::scf::Options &o = a.common;
+  o.nela = p.nela;
+  o.nelb = p.nelb;
+  o.Q = p.Q;
+  o.multiplicity = p.M > 0 ? p.M : 1;
+  o.restricted = p.restricted;
+  o.lpad = p.lpad;
+  o.Rmax = p.Rmax;
+  o.igrid = p.grid;
+  o.zexp = p.zexp;
+  o.nelem = p.nelem;
+  o.nnodes = p.nnodes;
+  o.nquad = p.nquad;
+  o.maxit = p.maxit;
+  o.convthr = p.convthr;
+  o.diag = p.diag != 0;
+  o.method = p.method;
+  helfem::parse_xc_func(o.x_func, o.c_func, o.method);
+  helfem::range_separation(o.x_func, o.omega, o.kfrac, o.kshort);
+  {
+    bool erf, yuk;
+    helfem::is_range_separated(o.x_func, erf, yuk);
+    o.rs_kind = yuk ? 1 : (erf ? 2 : 0);
+  }
+  o.ldft = p.ldft;
+  o.mdft = p.mdft;
+  o.dftthr = p.dftthr;
+  o.symmetry = p.symmetry;
+  o.diiseps = p.diiseps;
+  o.diisthr = p.diisthr;
+  o.diisorder = p.diisorder;
+  o.iguess = p.iguess;
+  o.readocc = p.readocc;
+  if (p.readocc)
+    for (int r = 0; r < p.occ_rows; r++) o.occs.push_back(std::vector<int>(p.occs + (size_t)r * p.occ_cols, p.occs + (size_t)(r + 1) * p.occ_cols));
+  o.dampfock = p.program ? p.dampfock : 1.0;
+  o.dampthr = p.dampthr;
+  o.verbose = p.verbose != 0;
+  if (p.program) {
+    a.Z = p.Z1;
+    a.Q = p.Q;
+    a.lmax = p.lmax;
+    a.mmax = p.mmax;
+    a.maverage = p.maverage != 0;
+    if (x) apply_extras(p, *x, a);
+  }
+}
+
+int hfg_scf_atomic_extras_default(hfg_scf_atomic_extras *x) {
+  if (!x) return 1;
+  memset(x, 0, sizeof(*x));
+  x->add_conf = 1;
+  x->grid0 = 4;
+  x->zexp0 = 2.0;
+  return 0;
+}
+
 /* validates an options structure the way hfg_scf_run does before it touches the device (usable without a GPU) */
-int hfg_scf_options_check(const hfg_scf_options *opt) {
+int hfg_scf_options_check(const hfg_scf_options *opt) { return hfg_scf_options_check_ex(opt, nullptr); }
+
+int hfg_scf_options_check_ex(const hfg_scf_options *opt, const hfg_scf_atomic_extras *extras) {
   try {
     if (!opt) throw std::logic_error("hfg_scf_options_check: null argument\n");
-    check_options(*opt);
+    check_options(*opt, extras);
+    if (extras) {  // the grid, the basis and the confinement matrix carry the refusals of the reference's set-up
+      helfem::scf::AtomicOptions a;
+      map_options(*opt, extras, a);
+      a.common.verbose = false;
+      helfem::scf::AtomicSetup su = helfem::scf::atomic_setup(a);
+      su.basis.nuclear();  // the remaining refusals of the set-up: unknown nuclear models
+    }
   } catch (const std::logic_error &e) {
     hfg::set_error(e.what());
     return 1;
@@ -557,50 +649,19 @@ int hfg_scf_options_check(const hfg_scf_options *opt) {
 }
 
 int hfg_scf_run(hfg_ctx *ctx, const hfg_scf_options *in, hfg_scf_result *res, double *E, double *C) {
+  return hfg_scf_run_ex(ctx, in, nullptr, res, E, C);
+}
+
+int hfg_scf_run_ex(hfg_ctx *ctx, const hfg_scf_options *in, hfg_scf_atomic_extras *extras, hfg_scf_result *res, double *E,
+                   double *C) {
   try {
     if (!ctx || !in || !res) throw std::logic_error("hfg_scf_run: null argument\n");
     const hfg_scf_options &p = *in;
-    check_options(p);
+    check_options(p, extras);
 
     helfem::scf::AtomicOptions a;
     helfem::scf::Options &o = a.common;
-    o.nela = p.nela;
-    o.nelb = p.nelb;
-    o.Q = p.Q;
-    o.multiplicity = p.M > 0 ? p.M : 1;
-    o.restricted = p.restricted;
-    o.lpad = p.lpad;
-    o.Rmax = p.Rmax;
-    o.igrid = p.grid;
-    o.zexp = p.zexp;
-    o.nelem = p.nelem;
-    o.nnodes = p.nnodes;
-    o.nquad = p.nquad;
-    o.maxit = p.maxit;
-    o.convthr = p.convthr;
-    o.diag = p.diag != 0;
-    o.method = p.method;
-    helfem::parse_xc_func(o.x_func, o.c_func, o.method);
-    helfem::range_separation(o.x_func, o.omega, o.kfrac, o.kshort);
-    {
-      bool erf, yuk;
-      helfem::is_range_separated(o.x_func, erf, yuk);
-      o.rs_kind = yuk ? 1 : (erf ? 2 : 0);
-    }
-    o.ldft = p.ldft;
-    o.mdft = p.mdft;
-    o.dftthr = p.dftthr;
-    o.symmetry = p.symmetry;
-    o.diiseps = p.diiseps;
-    o.diisthr = p.diisthr;
-    o.diisorder = p.diisorder;
-    o.iguess = p.iguess;
-    o.readocc = p.readocc;
-    if (p.readocc)
-      for (int r = 0; r < p.occ_rows; r++) o.occs.push_back(std::vector<int>(p.occs + (size_t)r * p.occ_cols, p.occs + (size_t)(r + 1) * p.occ_cols));
-    o.dampfock = p.program ? p.dampfock : 1.0;
-    o.dampthr = p.dampthr;
-    o.verbose = p.verbose != 0;
+    map_options(p, extras, a);
     o.keep_matrices = p.save[0] != 0;
     if (o.keep_matrices) {
       std::string why;
@@ -642,11 +703,6 @@ int hfg_scf_run(hfg_ctx *ctx, const hfg_scf_options *in, hfg_scf_result *res, do
       } else
         r = run_diatomic_device(ctx, o);
     } else {
-      a.Z = p.Z1;
-      a.Q = p.Q;
-      a.lmax = p.lmax;
-      a.mmax = p.mmax;
-      a.maverage = p.maverage != 0;
       if (host_driver()) {
         GPUBackend be(ctx);
         r = helfem::scf::run_atomic(a, be);
@@ -671,7 +727,8 @@ int hfg_scf_run(hfg_ctx *ctx, const hfg_scf_options *in, hfg_scf_result *res, do
     res->tdiag = r.tdiag;
     if (E && r.E.size()) memcpy(E, r.E.data(), sizeof(double) * r.E.size());
     if (C && r.C.n_elem()) memcpy(C, r.C.memptr(), sizeof(double) * r.C.n_elem());
-    if (p.save[0]) hfg::write_checkpoint(p, o, r);
+    if (extras) extras->Econf = r.Econf;
+    if (p.save[0]) hfg::write_checkpoint(p, o, r, p.program == 1 ? &a : nullptr, extras != nullptr);
   } catch (const std::logic_error &e) {
     hfg::set_error(e.what());
     return 1;

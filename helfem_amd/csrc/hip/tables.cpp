@@ -101,6 +101,9 @@ BasisView view_of(const hfg_basis *basis, bool rs = false) {
     v.E = (int)b->Nel();
     v.p = (int)b->max_Nprim();
     v.R = v.E * (v.p - 1);  // "dummy" radial count: function 0 (dropped at the nucleus) + the Nrad real ones
+    if (b->zeroder)
+      throw std::logic_error("A basis with zero derivative at Rmax (zeroder) keeps a radial function the device tables have no slot for: "
+                             "its host matrices are available, the device path is not supported by this build.\n");
     if ((int)b->Nrad() != v.R - 1) throw std::logic_error("unexpected atomic radial basis size");
     v.nq = b->nquad();
     v.N = (int)b->Nbf();

@@ -31,6 +31,195 @@ TwoDBasis::TwoDBasis(int Z_, int nnodes_, int n_quad, const Vec &bval, const IVe
   chebyshev_rule(n_quad, xq, wq);
 }
 
+TwoDBasis::TwoDBasis(int Z_, int finitenuc_, double Rrms_, bool zeroder_, int nnodes_, int n_quad, const Vec &bval,
+                     const IVec &lval_, const IVec &mval_, int Zl_, int Zr_, double Rhalf_)
+    : TwoDBasis(Z_, nnodes_, n_quad, bval, lval_, mval_) {
+  finitenuc = finitenuc_;
+  Rrms = Rrms_;
+  zeroder = zeroder_;
+  Zl = Zl_;
+  Zr = Zr_;
+  Rhalf = Rhalf_;
+  if (finitenuc != POINT_NUCLEUS && finitenuc != REGULARIZED_NUCLEUS) nuclear_model(finitenuc, Z, Rrms);  // refuses unknown models here
+  if (zeroder) fem = FEMBasis(fem.poly, bval, true, false);
+}
+
+// Regularized nucleus (Gygi, J. Chem. Theory Comput. 19, 1300 (2023)): the potential whose exact 1s state of a unit charge is
+// phi(r) = exp(h(r)) / sqrt(pi), h(r) = -r erf(a r) - b exp(-a^2 r^2); b makes phi normalised.  From (-1/2 Lap + V) phi =
+// -phi/2:  V = -1/2 + (h'' + h'^2)/2 + h'/r, and for a charge Z, V_Z(r) = Z^2 V(Z r).
+namespace {
+struct Regularized {
+  double a = 1.0, b = 0.0;
+  // erf(a r)/r, by its series where the quotient would lose digits
+  double erf_over_r(double r) const {
+    const double x = a * r;
+    if (x < 1e-2) {
+      const double x2 = x * x;
+      return a * M_2_SQRTPI * (1.0 + x2 * (-1.0 / 3.0 + x2 * (1.0 / 10.0 + x2 * (-1.0 / 42.0 + x2 / 216.0))));
+    }
+    return std::erf(x) / r;
+  }
+  double h(double r) const { return -r * std::erf(a * r) - b * std::exp(-a * a * r * r); }
+  double V(double r) const {
+    const double g = std::exp(-a * a * r * r), c = a * M_2_SQRTPI;
+    const double h1_over_r = -erf_over_r(r) - c * g + 2.0 * a * a * b * g;
+    const double h1 = h1_over_r * r;
+    const double h2 = -2.0 * c * g + 2.0 * c * a * a * r * r * g + 2.0 * a * a * b * g - 4.0 * a * a * a * a * b * r * r * g;
+    return -0.5 + 0.5 * (h2 + h1 * h1) + h1_over_r;
+  }
+  // 4 int r^2 exp(2 h) dr - 1 on panels that resolve both the Gaussian core (1/a) and the exponential tail
+  double norm_defect(double bb, const Vec &x, const Vec &w) {
+    b = bb;
+    const double core = 8.0 / a;
+    double sum = 0.0;
+    for (int part = 0; part < 2; part++) {
+      const int npanel = 64;
+      const double lo = part ? core : 0.0, len = (part ? 60.0 : core) / npanel;
+      for (int ip = 0; ip < npanel; ip++)
+        for (size_t q = 0; q < x.size(); q++) {
+          const double r = lo + (ip + 0.5 + 0.5 * x[q]) * len;
+          sum += 0.5 * len * w[q] * r * r * std::exp(2.0 * h(r));
+        }
+    }
+    return 4.0 * sum - 1.0;
+  }
+  explicit Regularized(double a_) : a(a_) {
+    if (!(a > 0.0)) throw std::logic_error("The regularized nucleus needs a positive parameter a (--Rrms).\n");
+    Vec x, w;
+    chebyshev_rule(40, x, w);
+    double lo = -40.0, hi = 40.0;  // the defect falls monotonically with b
+    for (int it = 0; it < 200 && hi - lo > 1e-15 * std::max(1.0, std::fabs(lo)); it++) {
+      const double mid = 0.5 * (lo + hi);
+      (norm_defect(mid, x, w) > 0.0 ? lo : hi) = mid;
+    }
+    b = 0.5 * (lo + hi);
+  }
+};
+}  // namespace
+
+std::function<double(double)> nuclear_model(int model, int Z, double Rrms, bool verbose) {
+  switch (model) {
+    case POINT_NUCLEUS:
+      if (verbose) printf("Getting point nucleus with Z=%i\n", Z);
+      return [Z](double r) { return -Z / r; };
+    case GAUSSIAN_NUCLEUS: {
+      if (verbose) printf("Getting Gaussian nucleus with Z=%i Rrms=%e\n", Z, Rrms);
+      // -Z erf(mu r)/r with mu = sqrt(3/2)/Rrms (Visscher and Dyall 1997, eq. 11); series below the radius where its
+      // first neglected term reaches the rounding error
+      const double mu = std::sqrt(1.5) / Rrms;
+      const double Rcut = std::pow(42.0 * 2.220446049250313e-16, 1.0 / 6.0) / mu;
+      return [Z, mu, Rcut](double r) {
+        if (r <= Rcut) {
+          const double x2 = (mu * r) * (mu * r);
+          return -Z * M_2_SQRTPI * mu * (1.0 + (-1.0 / 3.0 + (1.0 / 10.0 - x2 / 42.0) * x2) * x2);
+        }
+        return -Z * std::erf(mu * r) / r;
+      };
+    }
+    case SPHERICAL_NUCLEUS: {
+      if (verbose) printf("Getting uniformly charged spherical nucleus with Z=%i Rrms=%e\n", Z, Rrms);
+      const double R0 = std::sqrt(5.0 / 3.0) * Rrms;  // ibid. eqs. 4, 7
+      return [Z, R0](double r) { return (r >= R0) ? -Z / r : -Z / (2.0 * R0) * (3.0 - (r / R0) * (r / R0)); };
+    }
+    case HOLLOW_NUCLEUS:
+      if (verbose) printf("Getting hollow spherical nucleus with Z=%i Rrms=%e\n", Z, Rrms);
+      return [Z, Rrms](double r) { return (r >= Rrms) ? -Z / r : -Z / Rrms; };
+    case REGULARIZED_NUCLEUS: {
+      if (verbose) printf("Getting regularized nucleus with Z=%i a=%e\n", Z, Rrms);
+      Regularized unit(Rrms);
+      if (verbose) printf("a = %.15e yields b = %.15e\n", unit.a, unit.b);
+      return [Z, unit](double r) { return (double)Z * Z * unit.V(Z * r); };
+    }
+    case NOSUCH_NUCLEUS: throw std::logic_error("No such nucleus!\n");
+  }
+  throw std::logic_error("Unrecognized model\n");
+}
+
+// a segment that starts from zero, laid after the end of the grid so far
+static void append_segment(Vec &grid, const Vec &segment) {
+  if (segment.empty()) return;
+  if (segment[0] != 0.0) throw std::logic_error("grid segment doesn't start from zero");
+  if (grid.empty()) {
+    grid = segment;
+    return;
+  }
+  const double origin = grid.back();
+  for (size_t i = 1; i < segment.size(); i++) grid.push_back(segment[i] + origin);
+}
+
+// arma::vec::print(header): one value per line in the cell layout arma_ostream picks from the magnitudes
+static void print_vec(const char *header, const Vec &v) {
+  printf("%s\n", header);
+  bool sci = false, wide = false;
+  for (double x : v) {
+    if (!std::isfinite(x)) continue;
+    const double a = std::fabs(x);
+    if (a >= 100.0 || (a > 0.0 && a <= 1e-4)) sci = true;
+    if (a >= 10.0) wide = true;
+  }
+  const int width = sci ? 13 : (wide ? 10 : 9);
+  for (double x : v) {
+    if (x == 0.0) printf("%*s\n", width, "0");
+    else if (sci) printf("%*.4e\n", width, x);
+    else printf("%*.4f\n", width, x);
+  }
+}
+
+Vec form_grid(int model, double Rrms, int Nelem, double Rmax, int igrid, double zexp, int Nelem0, int igrid0, double zexp0,
+              int Z, int Zl, int Zr, double Rhalf, bool add_el, double shift_conf, bool verbose) {
+  Vec grid;
+  if (model != POINT_NUCLEUS && model != REGULARIZED_NUCLEUS) {
+    if (verbose) printf("Finite-nucleus grid\n");
+    if (Zl != 0 || Zr != 0) throw std::logic_error("Off-center nuclei not supported in finite nucleus mode!\n");
+    double rnuc;
+    if (model == HOLLOW_NUCLEUS) rnuc = Rrms;
+    else if (model == SPHERICAL_NUCLEUS) rnuc = std::sqrt(5.0 / 3.0) * Rrms;
+    else if (model == GAUSSIAN_NUCLEUS) rnuc = 3 * Rrms;
+    else throw std::logic_error("Nuclear grid not handled!\n");
+    if (Nelem0) {
+      // the nuclear segment twice (to rnuc and on to 2 rnuc), then an electronic segment of length Rmax - rnuc
+      const Vec inside = get_grid(rnuc, Nelem0, igrid0, zexp0);
+      append_segment(grid, inside);
+      append_segment(grid, inside);
+      append_segment(grid, get_grid(Rmax - rnuc, Nelem, igrid, zexp));
+    } else
+      grid = get_grid(Rmax, Nelem, igrid, zexp);
+  } else if (Zl != 0 || Zr != 0) {
+    if (verbose) printf("Off-center grid\n");
+    // a boundary where the pull of the central charge and of the larger off-centre one balance (only with a central
+    // charge), one on the off-centre nuclei, then out to Rmax; the segment that ends on the nuclei is mirrored so that its
+    // small elements lie next to them
+    const int Zoff = std::max(Zl, Zr);
+    const bool central = (Z != 0), offcentre = (Zoff != 0);
+    const double split = Z * Rhalf / (Z + Zoff);
+    if (verbose) {
+      printf("b0 = %e, b0used = %i\n", split, (int)central);
+      printf("b1 = %e, b1used = %i\n", Rhalf, (int)offcentre);
+      printf("b2 = %e\n", Rmax);
+    }
+    if (central) append_segment(grid, get_grid(split, Nelem0, igrid, zexp));
+    if (offcentre) {
+      const double len = Rhalf - split;
+      const Vec g = get_grid(len, Nelem0, igrid, zexp);
+      Vec mirrored(g.size());
+      for (size_t i = 0; i < g.size(); i++) mirrored[i] = len - g[g.size() - 1 - i];
+      mirrored.front() = 0.0;
+      mirrored.back() = len;
+      append_segment(grid, mirrored);
+    }
+    append_segment(grid, get_grid(Rmax - Rhalf, Nelem, igrid, zexp));
+  } else {
+    if (verbose) printf("Normal grid\n");
+    grid = get_grid(Rmax, Nelem, igrid, zexp);
+  }
+  if (add_el && std::find(grid.begin(), grid.end(), shift_conf) == grid.end()) {
+    grid.push_back(shift_conf);
+    std::sort(grid.begin(), grid.end());
+  }
+  if (verbose) print_vec("Grid", grid);
+  return grid;
+}
+
 int TwoDBasis::N_L() const { return 2 * *std::max_element(lval.begin(), lval.end()) + 1; }
 int TwoDBasis::Mmax() const {
   return *std::max_element(mval.begin(), mval.end()) - *std::min_element(mval.begin(), mval.end());
@@ -275,9 +464,99 @@ Mat TwoDBasis::kinetic() const {
   return place_diag(*this, rad);
 }
 
-Mat TwoDBasis::nuclear() const {
+Mat TwoDBasis::nuclear_point() const {
   Mat Vrad = assemble_radial(*this, [this](size_t iel) { return radial_integral(-1, iel); });
   return place_diag(*this, std::vector<Mat>(Nang(), (-(double)Z) * Vrad));
+}
+
+Mat TwoDBasis::nuclear_offcenter(size_t iel, int L) const {
+  // 1/|r - R| = sum_L 4 pi/(2L+1) r_<^L / r_>^(L+1) Y_L0(r) Y_L0(R), Y_L0 on the z axis = sqrt((2L+1)/(4 pi)): an element
+  // beyond the nucleus sees Rhalf^L r^(-L-1), one inside it r^L Rhalf^(-L-1); the nucleus must sit on a boundary
+  const double c = -std::sqrt(4.0 * M_PI / (2 * L + 1));
+  if (fem.element_begin(iel) >= Rhalf) return (c * std::pow(Rhalf, (double)L)) * radial_integral(-L - 1, iel);
+  if (fem.element_end(iel) <= Rhalf) return (c * std::pow(Rhalf, -(double)L - 1.0)) * radial_integral(L, iel);
+  throw std::logic_error("Nucleus placed within element!\n");
+}
+
+Mat TwoDBasis::nuclear() const {
+  if (finitenuc != POINT_NUCLEUS) {
+    const std::function<double(double)> pot = nuclear_model(finitenuc, Z, Rrms);
+    Mat Vrad = assemble_radial(*this, [&](size_t iel) { return fem.matrix_element(iel, 0, 0, xq, wq, pot); });
+    return place_diag(*this, std::vector<Mat>(Nang(), Vrad));
+  }
+  Mat V = nuclear_point();
+  if (Zl != 0 || Zr != 0) {
+    const size_t R = Nrad();
+    const int Lmax = 2 * *std::max_element(lval.begin(), lval.end());
+    std::vector<Mat> Vaux((size_t)Lmax + 1);
+    for (int L = 0; L <= Lmax; L++) Vaux[L] = assemble_radial(*this, [&](size_t iel) { return nuclear_offcenter(iel, L); });
+    for (size_t ia = 0; ia < Nang(); ia++)
+      for (size_t ja = 0; ja < Nang(); ja++) {
+        if (mval[ia] != mval[ja]) continue;
+        const int li = lval[ia], lj = lval[ja];
+        for (int L = std::abs(li - lj); L <= li + lj; L++) {
+          const double cpl = gaunt_coefficient(li, mval[ia], L, 0, lj, mval[ja]);
+          if (cpl == 0.0) continue;
+          const double f = cpl * ((L % 2 ? -1.0 : 1.0) * Zl + Zr);
+          for (size_t j = 0; j < R; j++)
+            for (size_t i = 0; i < R; i++) V(ia * R + i, ja * R + j) += f * Vaux[L](i, j);
+        }
+      }
+  }
+  return V;
+}
+
+Mat TwoDBasis::confinement(int N, double r_0, int iconf, double V, double shift, bool verbose) const {
+  if (iconf == 0) return Mat(Nbf(), Nbf());
+  const int sign = (r_0 < 0) ? -1 : 1;  // the sign of r_0 selects an attractive or a repulsive potential
+  r_0 = std::fabs(r_0);
+  const double r_c = *std::max_element(fem.bval.begin(), fem.bval.end());
+  Mat Orad = assemble_radial(*this, [&](size_t iel) -> Mat {
+    if (iconf == 1) {
+      if (verbose) printf("Polynomial confinement, r_0 = %e N = %i shift = %e \n", r_0, N, shift);
+      if (N < 0 && shift != 0.0) throw std::logic_error("Cannot have a divergent potential with a shift!\n");
+      // int (B_i/r)(B_j/r) (r - shift)^(N+2) dr beyond the shift (RadialBasis.cpp:361-369)
+      Mat bf = get_bf(iel);
+      Vec r = get_r(iel), w = get_wrad(iel);
+      Mat wbf(bf);
+      for (size_t q = 0; q < bf.n_rows; q++) {
+        const double wp = (r[q] < shift) ? 0.0 : w[q] * std::pow(r[q] - shift, N + 2);
+        for (size_t j = 0; j < bf.n_cols; j++) wbf(q, j) *= wp;
+      }
+      return (sign * std::pow(r_0, -(double)std::abs(N))) * matmul(wbf, true, bf, false);
+    } else if (iconf == 2) {
+      if (verbose) printf("Exponential confinement, r_0 = %e N = %i shift = %e \n", r_0, N, shift);
+      if (N < 0) throw std::logic_error("Exponential confinement potential does not make sense with negative N!\n");
+      if (N == 0) throw std::logic_error("Exponential confinement potential requires N >= 1!");
+      // N! [exp(x) - sum_{k<N} x^k/k!], x = (r - shift)/r_0: the exponential without its first N Taylor terms
+      return fem.matrix_element(iel, 0, 0, xq, wq, [=](double r) {
+        if (r < shift) return 0.0;
+        const double x = (r - shift) / r_0;
+        double term = 1.0, partial = 0.0, Nfactorial = 1.0;  // term = x^k / k!
+        for (int k = 0; k < N; k++) {
+          partial += term;
+          term *= x / (k + 1);
+          Nfactorial *= k + 1;
+        }
+        return Nfactorial * (std::exp(x) - partial);
+      });
+    } else if (iconf == 3) {
+      if (V < 0) throw std::logic_error("Cannot have attractive barrier!\n");
+      if (verbose) printf("Barrier confinement, V = %e shift = %e \n", V, shift);
+      return fem.matrix_element(iel, 0, 0, xq, wq, [=](double r) { return (r < shift) ? 0.0 : V; });
+    } else if (iconf == 4) {
+      if (verbose) printf("Junquera-type confinement, r_0 = %e N = %i V = %e shift = %e \n", r_0, N, V, shift);
+      if (N <= 0) throw std::logic_error("Junquera confinement potential requires N >= 1!");
+      if (V <= 0) throw std::logic_error("Cannot have attractive Junquera potential!\n");
+      // V0 exp(-(r_c - r_i)/(r - r_i)) / (r_c - r)^N with r_c the last grid point (Junquera et al. 2001)
+      return fem.matrix_element(iel, 0, 0, xq, wq, [=](double r) {
+        if (r < shift) return 0.0;
+        return V * std::exp(-(r_c - shift) / (r - shift)) / std::pow(r_c - r, N);
+      });
+    }
+    throw std::logic_error("Case not implemented!\n");
+  });
+  return place_diag(*this, std::vector<Mat>(Nang(), Orad));
 }
 
 // quadrature::twoe_inner_integral + twoe_integral / yukawa_integral (libhelfem/src/quadrature.cpp:22-169) for a kernel

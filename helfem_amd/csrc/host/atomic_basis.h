@@ -7,8 +7,10 @@
 // Range-separated exchange tables: :741-778 compute_yukawa, :780-815 compute_erfc with RadialBasis.cpp:201-209
 // bessel_il/kl_integral, :491 yukawa_integral, :502-558 erfc_integral and libhelfem/src/quadrature.cpp:128-222.
 //
-// Point nucleus at the origin only (finite nuclei, off-centre charges, confinement are outside this round's scope
-// and rejected by the driver).
+// One-electron Hamiltonian beyond the point nucleus at the origin: finite nuclear models (src/general/model_potential.cpp
+// get_nuclear_model, TwoDBasis.cpp:378-384), off-centre point charges on the z axis (TwoDBasis.cpp:405-452,
+// RadialBasis.cpp:464-476), confinement potentials (RadialBasis.cpp:361-455) and the radial grids that go with them
+// (src/atomic/basis.cpp:34-172).
 //
 // B(r)/r near the origin: the reference switches to a Taylor series of order nprim-1 below a numerically
 // chosen cutoff (RadialBasis.cpp:59-133, 575-631).  For LIPs whose first function is dropped, B_i(r)/r is a
@@ -33,9 +35,32 @@ Mat twoe_integral(double rmin, double rmax, const Vec &xq, const Vec &wq, const 
 /// (quadrature::yukawa_integral, libhelfem/src/quadrature.cpp:128-169)
 Mat yukawa_integral(double rmin, double rmax, const Vec &xq, const Vec &wq, const LIPBasis &poly, int L, double lambda);
 
+/// modelpotential::nuclear_model_t (src/general/model_potential.h:16-23), the values of --finitenuc
+enum NuclearModel {
+  POINT_NUCLEUS = 0,
+  GAUSSIAN_NUCLEUS = 1,
+  SPHERICAL_NUCLEUS = 2,
+  HOLLOW_NUCLEUS = 3,
+  REGULARIZED_NUCLEUS = 4,
+  NOSUCH_NUCLEUS = 5
+};
+/// V(r) of a nucleus of charge Z: Gaussian, uniformly charged sphere and hollow sphere of rms radius Rrms, or the regularized
+/// nucleus with parameter a = Rrms (modelpotential::get_nuclear_model); throws its texts for the other numbers
+std::function<double(double)> nuclear_model(int model, int Z, double Rrms, bool verbose = false);
+/// atomic::basis::form_grid (src/atomic/basis.cpp:119-172): finite-nucleus grid (Nelem0 elements up to the nuclear
+/// radius), off-centre grid (a boundary at Rhalf, Nelem0 elements inside) or the normal one, plus the boundary at
+/// shift_conf when add_el is set and it is not there yet; verbose prints what the reference prints
+Vec form_grid(int model, double Rrms, int Nelem, double Rmax, int igrid, double zexp, int Nelem0, int igrid0, double zexp0,
+              int Z, int Zl, int Zr, double Rhalf, bool add_el, double shift_conf, bool verbose);
+
 struct TwoDBasis {
   int Z = 0;
   int nnodes = 0;
+  int finitenuc = POINT_NUCLEUS;  // nuclear model of the central charge and its rms radius
+  double Rrms = 0.0;
+  bool zeroder = false;  // zero derivative instead of zero value at the last grid point: the last function is kept
+  int Zl = 0, Zr = 0;    // point charges at z = -Rhalf and z = +Rhalf
+  double Rhalf = 0.0;
   FEMBasis fem;
   Vec xq, wq;
   IVec lval, mval;
@@ -56,6 +81,9 @@ struct TwoDBasis {
 
   TwoDBasis() {}
   TwoDBasis(int Z, int nnodes, int n_quad, const Vec &bval, const IVec &lval, const IVec &mval);
+  /// the reference's full constructor (TwoDBasis.cpp:38-58)
+  TwoDBasis(int Z, int finitenuc, double Rrms, bool zeroder, int nnodes, int n_quad, const Vec &bval, const IVec &lval,
+            const IVec &mval, int Zl, int Zr, double Rhalf);
 
   size_t Nel() const { return fem.nelem(); }
   size_t Nrad() const { return fem.nbf(); }
@@ -98,6 +126,13 @@ struct TwoDBasis {
   Mat overlap() const;
   Mat kinetic() const;
   Mat nuclear() const;
+  /// the point-nucleus attraction of the central charge alone (the core guess, atomic/main.cpp:616)
+  Mat nuclear_point() const;
+  /// RadialBasis::nuclear_offcenter: radial part of the L-th multipole of a unit charge at distance Rhalf, element iel
+  Mat nuclear_offcenter(size_t iel, int L) const;
+  /// TwoDBasis::confinement (TwoDBasis.cpp:480-506) with RadialBasis::confinement_potential (RadialBasis.cpp:412-455):
+  /// iconf 1 polynomial, 2 exponential, 3 barrier, 4 Junquera et al.; verbose prints the reference's line per element
+  Mat confinement(int N, double r_0, int iconf, double V, double shift_pot, bool verbose = false) const;
   /// TwoDBasis::model_potential (src/atomic/TwoDBasis.cpp:458): int B_i B_j V(r) dr on every shell's diagonal block
   Mat model_potential(const ModelPotential &pot) const;
   void compute_tei(bool exchange);

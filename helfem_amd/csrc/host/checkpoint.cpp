@@ -276,16 +276,16 @@ void Checkpoint::write(const diatomic::TwoDBasis &basis) {
 void Checkpoint::write(const atomic::TwoDBasis &basis) {
   write("HelFEM_ID", 1);
   write("Z", basis.Z);
-  write("Zl", 0);
-  write("Zr", 0);
-  write("Rhalf", 0.0);
+  write("Zl", basis.Zl);
+  write("Zr", basis.Zr);
+  write("Rhalf", basis.Rhalf);
   write("bval", basis.fem.bval);
-  write("finitenuc", 0);
-  write("Rrms", 0.0);
+  write("finitenuc", basis.finitenuc);
+  write("Rrms", basis.Rrms);
   write("n_quad", (int)basis.xq.size());
   write("poly_id", 4);
   write("poly_nnodes", basis.nnodes);
-  write_bool("zeroder", false);
+  write_bool("zeroder", basis.zeroder);
   write("taylor_order", -1);
   write("lval", basis.lval);
   write("mval", basis.mval);
@@ -334,6 +334,14 @@ void Checkpoint::read(const std::string &name, int &v) const {
   if (a.Dread(d.d, a.native_int, 0, 0, 0, &v) < 0) throw std::runtime_error("Checkpoint: reading " + name + " failed\n");
 }
 
+bool Checkpoint::read_bool(const std::string &name) const {
+  const H5 &a = need();
+  Dataset d(a, file_, name);
+  unsigned int buf = 0;  // as write_bool: wide enough for either form of hbool_t
+  if (a.Dread(d.d, a.native_hbool, 0, 0, 0, &buf) < 0) throw std::runtime_error("Checkpoint: reading " + name + " failed\n");
+  return (buf & 0xffu) != 0;
+}
+
 diatomic::TwoDBasis Checkpoint::read_diatomic_basis(int lpad) const {
   int id = 0;
   read("HelFEM_ID", id);
@@ -359,7 +367,9 @@ atomic::TwoDBasis Checkpoint::read_atomic_basis() const {
   int id = 0;
   read("HelFEM_ID", id);
   if (id != 1) throw std::logic_error("Checkpoint does not correspond to an atomic calculation!\n");
-  int Z, nq, pid, nn, finitenuc = 0;
+  int Z, nq, pid, nn, finitenuc = 0, Zl = 0, Zr = 0;
+  double Rrms = 0.0, Rhalf = 0.0;
+  bool zeroder = false;
   Vec bval;
   IVec lval, mval;
   read("Z", Z);
@@ -370,9 +380,13 @@ atomic::TwoDBasis Checkpoint::read_atomic_basis() const {
   read("lval", lval);
   read("mval", mval);
   if (exist("finitenuc")) read("finitenuc", finitenuc);
+  if (exist("Rrms")) read("Rrms", Rrms);
+  if (exist("Zl")) read("Zl", Zl);
+  if (exist("Zr")) read("Zr", Zr);
+  if (exist("Rhalf")) read("Rhalf", Rhalf);
+  if (exist("zeroder")) zeroder = read_bool("zeroder");
   if (pid != 4) throw std::logic_error("Only the LIP primitive basis (poly_id 4) is supported by this build.\n");
-  if (finitenuc != 0) throw std::logic_error("Finite nuclear models are not supported by this build.\n");
-  return atomic::TwoDBasis(Z, nn, nq, bval, lval, mval);
+  return atomic::TwoDBasis(Z, finitenuc, Rrms, zeroder, nn, nq, bval, lval, mval, Zl, Zr, Rhalf);
 }
 
 }  // namespace helfem

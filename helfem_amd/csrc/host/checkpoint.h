@@ -33,6 +33,7 @@ class Checkpoint {
   void write(const std::string &name, double v);
   void write(const std::string &name, int v);
   void write_bool(const std::string &name, bool v);
+  bool read_bool(const std::string &name) const;
   void write(const diatomic::TwoDBasis &basis);
   void write(const atomic::TwoDBasis &basis);
 

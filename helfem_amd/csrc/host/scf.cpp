@@ -342,6 +342,7 @@ Result scf_loop(const Options &opt, Backend &be, Problem &pb, Result res) {
   const Mat &S = pb.S, &T = pb.T, &Vnuc = pb.Vnuc;
   const std::vector<std::vector<size_t> > &dsym = pb.dsym;
   Mat H0(T + Vnuc);
+  if (opt.Vconf) H0 = H0 + *opt.Vconf;
   double t0 = wall();
   Mat Sinvh(be.Sinvh(S, !opt.diag, dsym));
   if (verbose) printf("Half-inverse formed in %.6f\n", wall() - t0);
@@ -353,7 +354,7 @@ Result scf_loop(const Options &opt, Backend &be, Problem &pb, Result res) {
   Vec Ea, Eb;
   Mat Ca, Cb;
   bool prepared = false;
-  Mat Hguess(H0);
+  Mat Hguess(opt.Hcore_guess ? *opt.Hcore_guess : H0);
   if (opt.have_guess) {
     // orbitals of a previous run, nothing to evaluate
   } else if (opt.iguess != 0) {
@@ -407,6 +408,7 @@ Result scf_loop(const Options &opt, Backend &be, Problem &pb, Result res) {
     }
     res.Ekin = trace_prod(P, T);
     res.Epot = trace_prod(P, Vnuc);
+    if (opt.Vconf) res.Econf = trace_prod(P, *opt.Vconf);
 
     t0 = wall();
     Mat J(be.coulomb(P));
@@ -473,7 +475,7 @@ Result scf_loop(const Options &opt, Backend &be, Problem &pb, Result res) {
       last.XCa = XCa;
       last.XCb = restr ? XCa : XCb;
     }
-    res.Etot = res.Ekin + res.Epot + res.Ecoul + res.Exx + res.Exc + res.Enucr;
+    res.Etot = res.Ekin + res.Epot + res.Ecoul + res.Exx + res.Exc + res.Enucr + res.Econf;
     double dE = res.Etot - Eold;
     if (verbose) {
       printf("Total energy is % .10f\n", res.Etot);
@@ -586,6 +588,7 @@ Result scf_loop(const Options &opt, Backend &be, Problem &pb, Result res) {
     m["T"] = T;
     m["Vnuc"] = Vnuc;
     m["H0"] = H0;
+    if (opt.Vconf) m["Vconf"] = *opt.Vconf;
     m["Sinvh"] = Sinvh;
     m["P"] = P;
     m["Pa"] = last.Pa;
@@ -607,6 +610,7 @@ Result scf_loop(const Options &opt, Backend &be, Problem &pb, Result res) {
     printf("%-21s energy: % .16f\n", "Coulomb", res.Ecoul);
     printf("%-21s energy: % .16f\n", "Exact exchange", res.Exx);
     printf("%-21s energy: % .16f\n", "Exchange-correlation", res.Exc);
+    if (opt.Vconf) printf("%-21s energy: % .16f\n", "Confinement potential", res.Econf);
     printf("%-21s energy: % .16f\n", "Total", res.Etot);
     printf("%-21s energy: % .16f\n", "Virial ratio", -res.Etot / res.Ekin);
   }
@@ -715,28 +719,71 @@ std::vector<std::vector<std::vector<size_t> > > atomic_average_groups(const atom
   return grp;
 }
 
-Result run_atomic(const AtomicOptions &aopt, Backend &be) {
-  const Options &opt = aopt.common;
-  Result res;
-  const bool verbose = opt.verbose;
-  Problem pb;
-  int nel = aopt.Z - aopt.Q;
-  if (nel <= 0) throw std::logic_error("No electrons.\n");
-
+AtomicSetup atomic_setup(const AtomicOptions &a, bool basis_only) {
+  AtomicSetup su;
+  su.common = a.common;
+  Options &opt = su.common;
+  const bool verbose = opt.verbose && !basis_only;
+  su.nel = a.Z + a.Zl + a.Zr - a.Q;
+  if (su.nel <= 0) throw std::logic_error("No electrons.\n");
   // atomic/main.cpp:245-251
   int Nquad = opt.nquad;
   if (Nquad == 0) Nquad = 5 * opt.nnodes;
   else if (Nquad < 2 * opt.nnodes) throw std::logic_error("Insufficient radial quadrature.\n");
-
   IVec lval, mval;
-  atomic::angular_basis(aopt.lmax, aopt.mmax, lval, mval);
-  Vec bval = get_grid(opt.Rmax, opt.nelem, opt.igrid, opt.zexp);
-  atomic::TwoDBasis basis(aopt.Z, opt.nnodes, Nquad, bval, lval, mval);
+  atomic::angular_basis(a.lmax, a.mmax, lval, mval);
+  su.symm = opt.symmetry;
+  if (!a.extended()) {
+    su.basis = atomic::TwoDBasis(a.Z, opt.nnodes, Nquad, get_grid(opt.Rmax, opt.nelem, opt.igrid, opt.zexp), lval, mval);
+    return su;
+  }
+  if (a.zeroder)
+    throw std::logic_error("--zeroder: SCF runs with zero derivative at Rmax are not supported by this build (the device tables have "
+                           "no slot for the radial function it keeps; the basis and its one-electron matrices are available through "
+                           "hfg_atomic_basis_create_ex).\n");
+  if ((a.Zl != 0 || a.Zr != 0) && !(a.Rhalf > 0.0)) throw std::logic_error("Off-center nuclei need a positive --Rmid.\n");
+  if ((a.Zl != 0 || a.Zr != 0) && a.nelem0 <= 0) throw std::logic_error("Off-center nuclei need --nelem0.\n");
+  if (a.finitenuc != 0 && !(a.Rrms > 0.0)) throw std::logic_error("Finite nuclear models need a positive --Rrms.\n");
+  Vec bval = atomic::form_grid(a.finitenuc, a.Rrms, opt.nelem, opt.Rmax, opt.igrid, opt.zexp, a.nelem0, a.igrid0, a.zexp0, a.Z,
+                               a.Zl, a.Zr, a.Rhalf, a.add_conf, a.shift_conf, verbose);
+  su.basis = atomic::TwoDBasis(a.Z, a.finitenuc, a.Rrms, a.zeroder, opt.nnodes, Nquad, bval, lval, mval, a.Zl, a.Zr, a.Rhalf);
+  su.Enucr = (a.Rhalf > 0) ? a.Z * (a.Zl + a.Zr) / a.Rhalf + a.Zl * a.Zr / (2 * a.Rhalf) : 0.0;
+  if (verbose) {
+    printf("Central nuclear charge is %i\n", a.Z);
+    printf("Left- and right-hand nuclear charges are %i and %i at distance % .3f from center\n", a.Zl, a.Zr, a.Rhalf);
+    printf("Nuclear repulsion energy is %e\n", su.Enucr);
+  }
+  if (su.symm == 2 && (a.Zl != 0 || a.Zr != 0)) {
+    // off-centre charges couple l: (l, m) blocks would project that coupling out of the Fock matrix
+    if (verbose) printf("Warning - asked for full orbital symmetry in presence of off-center nuclei. Relaxing restriction.\n");
+    su.symm = 1;
+  }
+  if (basis_only) return su;
+  if (a.iconf) {
+    if (verbose) printf("Computing confinement potential\n");
+    opt.Vconf = std::make_shared<Mat>(su.basis.confinement(a.conf_N, a.conf_R, a.iconf, a.conf_barrier, a.shift_conf, verbose));
+  }
+  if (opt.iguess == 3 && a.Z == 0)
+    throw std::logic_error("The Thomas-Fermi guess (--iguess 3) screens the central charge only and there is none: use --iguess 0\n");
+  // the reference's core guess is T + the central point nucleus, whatever else H0 holds (atomic/main.cpp:616, 642)
+  if (opt.iguess == 0) opt.Hcore_guess = std::make_shared<Mat>(su.basis.kinetic() + su.basis.nuclear_point());
+  return su;
+}
+
+Result run_atomic(const AtomicOptions &aopt, Backend &be) {
+  AtomicSetup su = atomic_setup(aopt);
+  const Options &opt = su.common;
+  Result res;
+  const bool verbose = opt.verbose;
+  Problem pb;
+  const int nel = su.nel;
+  atomic::TwoDBasis &basis = su.basis;
+
   res.Nbf = basis.Nbf();
   if (verbose)
     printf("Basis set consists of %i angular shells composed of %i radial functions, totaling %i basis functions\n",
            (int)basis.Nang(), (int)basis.Nrad(), (int)basis.Nbf());
-  res.Enucr = 0.0;
+  res.Enucr = su.Enucr;
 
   const bool dft = (opt.x_func > 0 || opt.c_func > 0);
   int ldft = opt.ldft, mdft = opt.mdft;
@@ -746,7 +793,7 @@ Result run_atomic(const AtomicOptions &aopt, Backend &be) {
     if (mdft == 0) mdft = 4 * aopt.mmax + 5;
     if (mdft < 2 * aopt.mmax) throw std::logic_error("Increase mdft to guarantee accuracy of quadrature!\n");
   }
-  pb.symm = opt.symmetry;
+  pb.symm = su.symm;
   pb.dsym = basis.get_sym_idx(pb.symm);
   if (aopt.maverage) pb.avg_idx = atomic_average_groups(basis);
   pb.nel = nel;

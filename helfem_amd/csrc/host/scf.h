@@ -96,12 +96,16 @@ struct Options {
   Vec guessEa, guessEb;
   std::shared_ptr<diatomic::TwoDBasis> guess_basis;
   std::shared_ptr<atomic::TwoDBasis> guess_basis_atomic;
+  // atomic program: confinement potential matrix, part of H0 (atomic/main.cpp:473-494), Econf = tr(P Vconf); and the
+  // Hamiltonian of the core guess when it is not H0 (T + the central point nucleus, atomic/main.cpp:616, 642)
+  std::shared_ptr<Mat> Vconf, Hcore_guess;
   bool keep_matrices = false;  // fill Result::mats with what the reference's drivers write to their checkpoint
   bool verbose = true;
 };
 
 struct Result {
   double Ekin = 0, Epot = 0, Enucr = 0, Ecoul = 0, Exx = 0, Exc = 0, Etot = 0;
+  double Econf = 0;  // tr(P Vconf), part of Etot
   int iterations = 0;
   bool converged = false;
   double tJ = 0, tK = 0, tXC = 0, tdiag = 0;  // seconds of the last iteration
@@ -122,7 +126,31 @@ struct AtomicOptions {
   int Z = 2, Q = 0;
   int lmax = 0, mmax = 0;
   bool maverage = false;  // --maverage: average the Fock matrices over m for every l (scf::fock_symmetry_average)
+  // --finitenuc --Rrms --zeroder, --Zl --Zr --Rmid (bohr) --nelem0 --grid0 --zexp0, --iconf --conf_N --conf_R --conf_barrier
+  // --shift_conf --add_conf (atomic/main.cpp:160-194, 258-264)
+  int finitenuc = 0;
+  double Rrms = 0.0;
+  bool zeroder = false;
+  int Zl = 0, Zr = 0;
+  double Rhalf = 0.0;
+  int nelem0 = 0, igrid0 = 4;
+  double zexp0 = 2.0;
+  int iconf = 0, conf_N = 0;
+  double conf_R = 0.0, conf_barrier = 0.0, shift_conf = 0.0;
+  bool add_conf = false;
+  bool extended() const { return finitenuc != 0 || zeroder || Zl != 0 || Zr != 0 || iconf != 0 || add_conf; }
 };
+
+/// the set-up of the atomic program that both drivers share (atomic/main.cpp:228-300, 463-494): grid, basis, nuclear
+/// repulsion, the symmetry an off-centre run can keep, and in `common` the confinement matrix and the core-guess Hamiltonian
+struct AtomicSetup {
+  atomic::TwoDBasis basis;
+  double Enucr = 0.0;
+  int nel = 0, symm = 1;
+  Options common;
+};
+/// basis_only: quietly, without the confinement matrix and the guess Hamiltonian (what a checkpoint stores)
+AtomicSetup atomic_setup(const AtomicOptions &opt, bool basis_only = false);
 
 /// scf::parse_nela_nelb (src/general/scf_helpers.cpp:558-603): occupations from the charge state and the multiplicity, or
 /// charge and multiplicity from explicit occupations; Ztot = total nuclear charge.  Throws std::runtime_error like the

@@ -82,7 +82,7 @@ int hfg_diatomic_basis_create(const hfg_diatomic_desc *desc, hfg_basis **basis);
 
 /* Constructor arguments of helfem::atomic::basis::TwoDBasis (src/atomic/TwoDBasis.cpp:38-76) for the
  * point-nucleus case the atomic driver builds at src/atomic/main.cpp:268-273 (finitenuc = 0, no off-centre
- * charges, zeroder = 0).  The handle is used with every hfg_basis_* / hfg_coulomb / hfg_exchange / hfg_xc_fock
+ * charges, zeroder = 0; hfg_atomic_basis_create_ex takes the rest).  The handle is used with every hfg_basis_* / hfg_coulomb / hfg_exchange / hfg_xc_fock
  * entry below exactly like a diatomic one (replacing TwoDBasis::coulomb / exchange, TwoDBasis.cpp:817/957,
  * and atomic::dftgrid::DFTGrid::eval_Fxc, src/atomic/dftgrid.cpp:810). */
 typedef struct {
@@ -97,6 +97,32 @@ typedef struct {
   int nang;
 } hfg_atomic_desc;
 int hfg_atomic_basis_create(const hfg_atomic_desc *desc, hfg_basis **basis);
+/* The remaining constructor arguments of atomic::basis::TwoDBasis (TwoDBasis.cpp:38): finitenuc = nuclear model of the
+ * central charge (modelpotential::nuclear_model_t: 0 point, 1 Gaussian, 2 uniformly charged sphere, 3 hollow sphere with
+ * rms radius Rrms; 4 regularized nucleus with a = Rrms), zeroder = zero derivative instead of zero value at
+ * the last grid point (the last radial function is kept: Nbf grows by Nang; host matrices only, hfg_basis_upload and the SCF
+ * drivers refuse such a basis because the device tables have no slot for that function), and point charges Zl at z = -Rmid, Zr at
+ * z = +Rmid, which must lie on an element boundary.  hfg_basis_nuclear then returns the full nuclear attraction matrix
+ * (TwoDBasis::nuclear, TwoDBasis.cpp:378-456), which couples l for off-centre charges. */
+typedef struct {
+  hfg_atomic_desc base;
+  int finitenuc;
+  double Rrms;
+  int zeroder;
+  int Zl, Zr;
+  double Rmid;
+} hfg_atomic_desc_ex;
+int hfg_atomic_basis_create_ex(const hfg_atomic_desc_ex *desc, hfg_basis **basis);
+/* TwoDBasis::confinement(N, R, iconf, V, shift) (TwoDBasis.cpp:480, RadialBasis::confinement_potential,
+ * RadialBasis.cpp:412-455): iconf 1 polynomial sign(R) ((r - shift)/|R|)^N, 2 exponential, 3 barrier of height V beyond
+ * shift, 4 Junquera et al. with r_c = the last grid point; iconf 0 gives zeros.  Atomic bases only; out is Nbf x Nbf. */
+int hfg_basis_confinement(const hfg_basis *basis, int iconf, int N, double R, double V, double shift, double *out);
+/* atomic::basis::form_grid (src/atomic/basis.cpp:119-172): the element boundaries of the atomic program for a finite
+ * nucleus (nelem0 elements up to the nuclear radius, twice, then nelem elements), for off-centre charges (a boundary at
+ * Rmid with nelem0 elements inside it per segment) or neither (hfg_radial_grid), plus a boundary at shift_conf when add_conf
+ * is set and none is there.  n in: capacity of bval, out: number of boundaries. */
+int hfg_atomic_grid(int finitenuc, double Rrms, int nelem, double Rmax, int grid, double zexp, int nelem0, int grid0,
+                    double zexp0, int Z, int Zl, int Zr, double Rmid, int add_conf, double shift_conf, double *bval, int *n);
 /* atomic::basis::angular_basis (src/atomic/basis.cpp:174): shell list for --lmax/--mmax */
 int hfg_angular_basis(int lmax, int mmax, int *lval, int *mval, int *nang /* in: capacity, out: count */);
 int hfg_basis_destroy(hfg_basis *basis);
@@ -374,6 +400,30 @@ int hfg_scf_set_occupations(int readocc, int nrows, int ncols, const int *rows);
 int hfg_scf_options_check(const hfg_scf_options *opt);
 /* runs the calculation on ctx's device; E / C (alpha orbital energies Nbf, orbitals Nbf x Nbf) may be NULL */
 int hfg_scf_run(hfg_ctx *ctx, const hfg_scf_options *opt, hfg_scf_result *res, double *E, double *C);
+/* The atomic program's flags that hfg_scf_options carries no value for (atomic/main.cpp:64-66, 104, 113-118, 160-194).
+ * With them hfg_scf_options::finitenuc and iconf take effect (zeroder is refused with a text that says why); Rmid is in bohr.  Econf is an output: tr(P Vconf),
+ * the "Confinement potential" line of the energy table, which is part of Etot (atomic/main.cpp:748, 858). */
+typedef struct hfg_scf_atomic_extras {
+  double Rrms;               /* --Rrms */
+  int conf_N;                /* --conf_N */
+  double conf_R;             /* --conf_R */
+  double conf_barrier;       /* --conf_barrier */
+  double shift_conf;         /* --shift_conf */
+  int add_conf;              /* --add_conf = 1 */
+  int Zl, Zr;                /* --Zl --Zr */
+  double Rmid;               /* --Rmid */
+  int nelem0;                /* --nelem0 */
+  int grid0;                 /* --grid0 = 4 */
+  double zexp0;              /* --zexp0 = 2 */
+  double Econf;              /* out */
+} hfg_scf_atomic_extras;
+int hfg_scf_atomic_extras_default(hfg_scf_atomic_extras *extras);
+/* hfg_scf_options_check for an atomic run with extras (NULL: exactly hfg_scf_options_check): the combination, the grid and
+ * the one-electron matrices are formed on the host, so every refusal of the run short of the device comes out here */
+int hfg_scf_options_check_ex(const hfg_scf_options *opt, const hfg_scf_atomic_extras *extras);
+/* hfg_scf_run with the extras (NULL: exactly hfg_scf_run, with its refusals); opt->program must be 1 when extras is given */
+int hfg_scf_run_ex(hfg_ctx *ctx, const hfg_scf_options *opt, hfg_scf_atomic_extras *extras, hfg_scf_result *res, double *E,
+                   double *C);
 /* scf::parse_xc_params (src/general/scf_helpers.cpp): one number per line of a text file; n in: capacity, out: count */
 int hfg_parse_xc_params(const char *path, double *pars, int *n);
 /* element symbol or number -> nuclear charge (get_Z of src/general/elements.h as the drivers use it); < 0: unknown */
