@@ -2,6 +2,8 @@
 
   helfem_amd/lib/libhelfem_amd.so   product: host setup code + HIP kernels + C ABI (hipcc, gfx950)
   oracle/liboracle.so               test-only CPU checker (g++)
+  tests/gpu_probe/libtwostage_probe.so      test-only: the two-stage tridiagonalisation (hipcc, links the product library)
+  tests/gpu_probe/libgemm_engine_probe.so   test-only: the GEMM launchers behind one entry point (likewise)
   oracle/_ref/libref_legendre.so    the one buildable piece of the reference (only if /root/reference exists)
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the CPU-only container too.
@@ -118,11 +120,10 @@ def build_adapter_test(verbose=True):
     return exe
 
 
-def build_probe(verbose=True):
-    """tests/gpu_probe/libtwostage_probe.so: the two-stage tridiagonalisation of round 2 (measured slower than the product
-    path, kept as a probe with its test), linked against the product library for the GEMM task lists"""
-    src = os.path.join(ROOT, "tests", "gpu_probe", "two_stage.hip")
-    out = os.path.join(ROOT, "tests", "gpu_probe", "libtwostage_probe.so")
+def _build_probe_lib(srcname, outname, verbose):
+    """one probe library tests/gpu_probe/<outname> from tests/gpu_probe/<srcname>, linked against the product library"""
+    src = os.path.join(ROOT, "tests", "gpu_probe", srcname)
+    out = os.path.join(ROOT, "tests", "gpu_probe", outname)
     lib = os.path.join(LIBDIR, "libhelfem_amd.so")
     if _newer(src, out, tuple(_headers()) + (lib,)):
         hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -132,6 +133,18 @@ def build_probe(verbose=True):
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
     return out
+
+
+def build_probe(verbose=True):
+    """tests/gpu_probe/libtwostage_probe.so: the two-stage tridiagonalisation of round 2 (measured slower than the product
+    path, kept as a probe with its test), linked against the product library for the GEMM task lists"""
+    return _build_probe_lib("two_stage.hip", "libtwostage_probe.so", verbose)
+
+
+def build_gemm_probe(verbose=True):
+    """tests/gpu_probe/libgemm_engine_probe.so: the launchers of the GEMM tile engine (hip/gemm.hip) behind one C entry
+    point, for tests/test_gpu_gemm_engine.py"""
+    return _build_probe_lib("gemm_engine.hip", "libgemm_engine_probe.so", verbose)
 
 
 def build_oracle(verbose=True):
@@ -146,4 +159,5 @@ def build_oracle(verbose=True):
 if __name__ == "__main__":
     build_product(force="--force" in sys.argv)
     build_probe()
+    build_gemm_probe()
     build_oracle()

@@ -1069,7 +1069,13 @@ int hfg_gemm(hfg_ctx *ctx, int tA, int tB, int64_t m, int64_t n, int64_t k, cons
   size_t na = (size_t)lda * (tA ? m : k), nb = (size_t)ldb * (tB ? k : n);
   double *dA = st.up(A, na), *dB = st.up(B, nb), *dC = st.alloc((size_t)ldc * n);
   gemm_dev(ctx, tA != 0, tB != 0, (int)m, (int)n, (int)k, 1.0, dA, (int)lda, dB, (int)ldb, 0.0, dC, (int)ldc);
-  st.down(C, dC, (size_t)ldc * n);
+  if (ldc == m) {
+    st.down(C, dC, (size_t)ldc * n);
+  } else if (m > 0 && n > 0) {
+    // the m x n part only: rows m..ldc-1 of the caller's C are not this call's to write (dC holds nothing there)
+    HFG_HIP_CHECK(hipMemcpy2DAsync(C, (size_t)ldc * sizeof(double), dC, (size_t)ldc * sizeof(double), (size_t)m * sizeof(double),
+                                   (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  }
   st.sync();
   HFG_CATCH
 }

@@ -499,8 +499,11 @@ void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int m
   if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
   ProfScope ps(ctx, "gemm");
   const int tiles = ((maxM + 63) / 64) * ((maxN + 63) / 64);
-  if (mfma4()) hipLaunchKernelGGL((k_dgemm_tasklist<64, 64, false, 0>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
-  else hipLaunchKernelGGL((k_dgemm_tasklist<64, 64>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
+  for (int t0 = 0; t0 < ntasks; t0 += 65535) {  // (the grid's second dimension ends at 65535)
+    const int nt = std::min(65535, ntasks - t0);
+    if (mfma4()) hipLaunchKernelGGL((k_dgemm_tasklist<64, 64, false, 0>), dim3(tiles, nt), dim3(256), 0, ctx->stream, dtasks + t0);
+    else hipLaunchKernelGGL((k_dgemm_tasklist<64, 64>), dim3(tiles, nt), dim3(256), 0, ctx->stream, dtasks + t0);
+  }
   HFG_HIP_CHECK(hipGetLastError());
 }
 

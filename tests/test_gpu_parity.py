@@ -25,7 +25,10 @@ def test_gemm_all_transposes(hf):
                 assert np.max(np.abs(C - ref)) < 1e-12 * k, (m, n, k, tA, tB)
 
 
-def test_gemm_large_tile_path(hf):
+def test_gemm_large_product(hf):
+    """3000 x 200 x 2900 through hfg_gemm.  Written for the 128 x 128 kernel, which it no longer reaches: 24 x 23 = 552 large
+    tiles fill two rounds of the 512 slots of a 256-CU part to 54 % only, so gemm_prefers_128 sends the product to
+    k_dgemm<64, 64> (47 x 46 tiles).  The large-tile kernels are tested in tests/test_gpu_gemm_engine.py."""
     rng = np.random.RandomState(1)
     A = rng.uniform(-1, 1, size=(3000, 200))
     B = rng.uniform(-1, 1, size=(200, 2900))
