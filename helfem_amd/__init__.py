@@ -791,6 +791,20 @@ def xc_exact_exchange(x_func):
     return o.value, a.value, b.value
 
 
+def xc_func_table():
+    """the functionals of the native library (hfg_xc_func_table; no device needed): a list of dicts, one per functional, with
+    id, name, role ("x", "c", "xc"), the inputs it needs (grad, tau, lapl), ext (0, or which branch of the EXT instantiation
+    evaluates it), skip_dead (left out as a whole where a spin channel is below the threshold), what the drivers add as exact
+    exchange (kfrac, kshort, omega, rs_kind), its external parameters (npar, pars: a tuple of names) and a remark"""
+    buf = ctypes.create_string_buffer(1 << 16)
+    _check(lib().hfg_xc_func_table(buf, ctypes.c_size_t(len(buf))))
+    keys = ("id", "name", "role", "grad", "tau", "lapl", "ext", "skip_dead", "kfrac", "kshort", "omega", "rs_kind", "npar", "pars", "remark")
+    conv = dict(id=int, grad=lambda v: v == "1", tau=lambda v: v == "1", lapl=lambda v: v == "1", ext=int, skip_dead=lambda v: v == "1",
+                kfrac=float, kshort=float, omega=float, rs_kind=int, npar=int, pars=lambda v: tuple(v.split(",")) if v else ())
+    rows = [dict(zip(keys, line.split("\t"))) for line in buf.value.decode().split("\n") if line]
+    return [{k: conv.get(k, str)(v) for k, v in row.items()} for row in rows]
+
+
 def xc_rs_kind(x_func):
     """screened kernel of an exchange id (hfg_xc_rs_kind): 0 none, 1 Yukawa, 2 erfc -- the rs_kind of compute_rs_tei"""
     f = lib().hfg_xc_rs_kind

@@ -902,10 +902,14 @@ int hfg_xc_exact_exchange(int x_func, double *omega, double *alpha, double *beta
   HFG_CATCH
 }
 
-int hfg_xc_rs_kind(int x_func) {
-  bool erf, yuk;
-  helfem::is_range_separated(x_func, erf, yuk);
-  return yuk ? 1 : (erf ? 2 : 0);
+int hfg_xc_rs_kind(int x_func) { return helfem::rs_kind(x_func); }
+
+int hfg_xc_func_table(char *buf, size_t cap) {
+  HFG_TRY
+  const std::string all = helfem::xc_func_table();
+  if (cap == 0 || all.size() + 1 > cap) throw std::logic_error("hfg_xc_func_table: buffer too small");
+  memcpy(buf, all.c_str(), all.size() + 1);
+  HFG_CATCH
 }
 
 int hfg_basis_radial_table(const hfg_basis *b, int which, int iel, double *out, int64_t *rows, int64_t *cols) {
@@ -963,18 +967,21 @@ int hfg_xc_fock_pol(hfg_ctx *ctx, hfg_basis *b, int x_func, int c_func, const do
   *Ekin = sc[2];
   HFG_CATCH
 }
+namespace {
+struct XCParReset {  // the functionals' default parameters come back whatever happens
+  hfg_ctx *c;
+  ~XCParReset() {
+    try {
+      set_xc_params(c, 0, nullptr, 0, 0, nullptr, 0);
+    } catch (...) {
+    }
+  }
+};
+}  // namespace
 int hfg_xc_fock_ext(hfg_ctx *ctx, hfg_basis *b, int x_func, const double *x_pars, int n_x_pars, int c_func, const double *c_pars,
                     int n_c_pars, const double *P, double *H, double *Exc, double *Nel, double *Ekin, double thr) {
   HFG_TRY
-  struct Reset {  // the defaults come back whatever happens
-    hfg_ctx *c;
-    ~Reset() {
-      try {
-        set_xc_params(c, 0, nullptr, 0, 0, nullptr, 0);
-      } catch (...) {
-      }
-    }
-  } reset{ctx};
+  XCParReset reset{ctx};
   set_xc_params(ctx, x_func, x_pars, n_x_pars, c_func, c_pars, n_c_pars);
   int rc = hfg_xc_fock(ctx, b, x_func, c_func, P, H, Exc, Nel, Ekin, thr);
   if (rc) return rc;
@@ -984,15 +991,7 @@ int hfg_xc_fock_pol_ext(hfg_ctx *ctx, hfg_basis *b, int x_func, const double *x_
                         const double *c_pars, int n_c_pars, const double *Pa, const double *Pb, double *Ha, double *Hb, double *Exc,
                         double *Nel, double *Ekin, double thr) {
   HFG_TRY
-  struct Reset {
-    hfg_ctx *c;
-    ~Reset() {
-      try {
-        set_xc_params(c, 0, nullptr, 0, 0, nullptr, 0);
-      } catch (...) {
-      }
-    }
-  } reset{ctx};
+  XCParReset reset{ctx};
   set_xc_params(ctx, x_func, x_pars, n_x_pars, c_func, c_pars, n_c_pars);
   int rc = hfg_xc_fock_pol(ctx, b, x_func, c_func, Pa, Pb, Ha, Hb, Exc, Nel, Ekin, thr);
   if (rc) return rc;

@@ -21,6 +21,7 @@
 #include "tables.h"
 #include "xc_device.h"
 #include "../host/dftfuncs.h"
+#include <cstring>
 
 namespace hfg {
 
@@ -530,18 +531,8 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
     if (rho >= thr && rho > 0.0) {
       const bool live = 0.5 * rho >= thr;  // the spin channels of the exchange sum carry rho/2 each
       const double lapl = 2.0 * (2.0 * tau + lap);
-      if (x_func > 0) {
-        if (EXT && xc::is_ext(x_func)) xc::eval_add_ext(x_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
-        else if (xc::is_mgga_lapl(x_func)) xc::eval_add_mgga_lapl(x_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
-        else if (xc::is_mgga(x_func)) xc::eval_add_mgga(x_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
-        else xc::eval_add(x_func, rho, sigma, live, exc, vrho, vsig);
-      }
-      if (c_func > 0) {
-        if (EXT && xc::is_ext(c_func)) xc::eval_add_ext(c_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
-        else if (xc::is_mgga_lapl(c_func)) xc::eval_add_mgga_lapl(c_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
-        else if (xc::is_mgga(c_func)) xc::eval_add_mgga(c_func, rho, sigma, tau, live, exc, vrho, vsig, vtau);
-        else xc::eval_add(c_func, rho, sigma, live, exc, vrho, vsig);
-      }
+      if (x_func > 0) HFG_XC_EVAL_POINT(EXT, x_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
+      if (c_func > 0) HFG_XC_EVAL_POINT(EXT, c_func, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap);
       if (!isfinite(vlap)) vlap = 0.0;  // check_xc, dftgrid.cpp:336-339
     }
     nel += w * rho;
@@ -723,13 +714,8 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
       for (int f = 0; f < 2; f++) {
         const int id = f ? c_func : x_func;
         if (id <= 0) continue;
-        if (EXT && xc::is_ext(id))
-          xc::eval_add_ext_pol(id, ra, rb, saa, sab, sbb, tau[0], tau[1], rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa, vsab, vsbb, vta, vtb);
-        else if (xc::is_mgga_lapl(id))
-          xc::eval_add_mgga_lapl_pol(id, ra, rb, saa, sab, sbb, tau[0], tau[1], la, lb, rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa,
-                                     vsab, vsbb, vta, vtb, vla, vlb);
-        else if (xc::is_mgga(id)) xc::eval_add_mgga_pol(id, ra, rb, saa, sab, sbb, tau[0], tau[1], rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa, vsab, vsbb, vta, vtb);
-        else xc::eval_add_pol(id, ra, rb, saa, sab, sbb, rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa, vsab, vsbb);
+        HFG_XC_EVAL_POINT_POL(EXT, id, ra, rb, saa, sab, sbb, tau[0], tau[1], la, lb, rho[0] >= thr, rho[1] >= thr, exc, va, vb, vsaa, vsab,
+                                vsbb, vta, vtb, vla, vlb);
       }
       if (!isfinite(vla)) vla = 0.0;  // check_xc, dftgrid.cpp:336-339
       if (!isfinite(vlb)) vlb = 0.0;
@@ -1291,96 +1277,138 @@ void coulomb_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dJ) {
   HFG_HIP_CHECK(hipGetLastError());
 }
 
-void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPc, double *dHc, double *dScal,
-                double thr) {
-  hfg_dev_tables *t = tables_of(ctx, basis);
+// What one XC build computes and launches, decided once from the rows of its two functionals (host/xc_funcs.h)
+struct XCPlan {
+  int do_grad, do_tau, do_lapl;  // the inputs beside rho that the density stage forms and the Fock stage consumes
+  bool ext;                      // the EXT instantiation of the grid kernel
+  double thr;                    // density threshold
+  int maxgrp;                    // largest m group of the angular basis
+  size_t NQ, AA, nv;             // radial points, angular pairs, entries of one V / Fo plane
+};
+static XCPlan xc_plan(const hfg_dev_tables *t, int x_func, int c_func, double thr) {
   if (!t->have_xc) throw std::runtime_error("XC grid tables were not uploaded (hfg_basis_upload with ldft,mdft > 0)\n");
+  auto either = [&](bool (*is)(int)) { return (x_func > 0 && is(x_func)) || (c_func > 0 && is(c_func)); };
   if ((x_func > 0 && !xc::is_supported(x_func)) || (c_func > 0 && !xc::is_supported(c_func)))
     throw std::runtime_error("Functional not found!");
-  FockAux &a = aux_for(ctx, basis);
-  const int A = t->A, E = t->E, p = t->p, nq = t->nq, G = t->G, nth = t->ntheta, nphi = t->nphi;
-  const size_t NQ = (size_t)E * nq, AA = (size_t)A * A;
-  int do_grad = ((x_func > 0 && xc::is_gga(x_func)) || (c_func > 0 && xc::is_gga(c_func))) ? 1 : 0;
+  XCPlan pl;
+  pl.do_grad = either(xc::is_gga);
   // Laplacian-dependent meta-GGAs (the atomic program only; both available ones need tau as well)
-  const int do_lapl = ((x_func > 0 && xc::is_mgga_lapl(x_func)) || (c_func > 0 && xc::is_mgga_lapl(c_func))) ? 1 : 0;
-  if (do_lapl && t->geom != 1) throw std::logic_error("Laplacian not implemented!\n");  // diatomic dftgrid.cpp:115-116, 209-210
-  int do_tau = ((x_func > 0 && xc::is_mgga(x_func)) || (c_func > 0 && xc::is_mgga(c_func)) || do_lapl) ? 1 : 0;
+  pl.do_lapl = either(xc::is_mgga_lapl);
+  if (pl.do_lapl && t->geom != 1) throw std::logic_error("Laplacian not implemented!\n");  // diatomic dftgrid.cpp:115-116, 209-210
+  pl.do_tau = either(xc::is_mgga) || pl.do_lapl;
+  pl.ext = either(xc::is_ext);
   // meta-GGAs: a floor under the density threshold.  Below 1e-50 the tau-dependent expressions overflow (tau_unif ~ n^(5/3),
   // p ~ sigma / n^(8/3)) and return NaN where the point carries nothing; libxc keeps such points out with its own tau and
   // sigma thresholds, --dftthr 0 would switch the density threshold off.  Far-field densities of an SCF density are
   // rounding noise of the eigensolver at that level (tests/test_gpu_fullsize.py::test_fullsize_xc_without_density_threshold).
-  if (do_tau) thr = std::max(thr, 1e-40);
-  a.D0.resize(NQ * AA);
-  a.D1.resize(NQ * AA);
-  a.GA.resize(NQ * AA);
-  a.GB.resize(NQ * AA);
-  if (do_tau) {
-    a.D2.resize(NQ * AA);
-    a.GC.resize(NQ * AA);
-  }
-  if (do_lapl) {
-    a.D3.resize(NQ * AA);
-    a.GL.resize(NQ * AA);
-  }
-  const size_t nv = NQ * G * G * nth;
-  a.V.resize((do_lapl ? 6 : 5) * nv);
-  a.Fo.resize((do_lapl ? 6 : 5) * nv);
-  a.partial.resize(3 * NQ);
-  int maxgrp = 0;
-  for (int g = 0; g < G; g++) maxgrp = std::max(maxgrp, t->h_grp_off[g + 1] - t->h_grp_off[g]);
+  pl.thr = pl.do_tau ? std::max(thr, 1e-40) : thr;
+  pl.maxgrp = 0;
+  for (int g = 0; g < t->G; g++) pl.maxgrp = std::max(pl.maxgrp, t->h_grp_off[g + 1] - t->h_grp_off[g]);
+  pl.NQ = (size_t)t->E * t->nq;
+  pl.AA = (size_t)t->A * t->A;
+  pl.nv = pl.NQ * t->G * t->G * t->ntheta;
+  return pl;
+}
 
-  hipLaunchKernelGGL(k_xc_density_radial, dim3(A * A, E), dim3(256), xc_density_radial_lds(p, nq, do_lapl),
-                     ctx->stream, dPc, t->rad_B.p, t->rad_dB.p, (const double *)t->rad_L.p, A, E, p, nq, do_grad, do_tau, do_lapl,
+// work arrays of one XC build; planes: how many V and Fo hold in all, as the grid kernel indexes them
+static void xc_buffers(FockAux &a, const XCPlan &pl, int planes) {
+  a.D0.resize(pl.NQ * pl.AA);
+  a.D1.resize(pl.NQ * pl.AA);
+  a.GA.resize(pl.NQ * pl.AA);
+  a.GB.resize(pl.NQ * pl.AA);
+  if (pl.do_tau) {
+    a.D2.resize(pl.NQ * pl.AA);
+    a.GC.resize(pl.NQ * pl.AA);
+  }
+  if (pl.do_lapl) {
+    a.D3.resize(pl.NQ * pl.AA);
+    a.GL.resize(pl.NQ * pl.AA);
+  }
+  a.V.resize(planes * pl.nv);
+  a.Fo.resize(planes * pl.nv);
+  a.partial.resize(3 * pl.NQ);
+}
+
+// density stage of one spin: compact density -> the planes of V at dV
+static void xc_density_stage(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, const XCPlan &pl, const double *dPc, double *dV) {
+  const int A = t->A, E = t->E, p = t->p, nq = t->nq, G = t->G, nth = t->ntheta;
+  hipLaunchKernelGGL(k_xc_density_radial, dim3(A * A, E), dim3(256), xc_density_radial_lds(p, nq, pl.do_lapl), ctx->stream, dPc,
+                     t->rad_B.p, t->rad_dB.p, (const double *)t->rad_L.p, A, E, p, nq, pl.do_grad, pl.do_tau, pl.do_lapl,
                      ctx->shard_rank, ctx->shard_n, a.D0.p, a.D1.p, a.D2.p, a.D3.p);
-  hipLaunchKernelGGL(k_xc_density_theta, dim3((unsigned)NQ, G * G), dim3(std::min(256, round_up64(nth))),
-                     (do_lapl ? 4 : 3) * maxgrp * maxgrp * sizeof(double), ctx->stream, a.D0.p, a.D1.p, a.D2.p, (const double *)a.D3.p,
-                     t->Th.p, t->dTh.p, t->shell_l.p, t->rad_sh.p, A, nth, G, t->grp_off.p, t->grp_shell.p, do_grad, do_tau, do_lapl,
-                     NQ, ctx->shard_rank, ctx->shard_n, a.V.p);
-  size_t shb = (size_t)((do_lapl ? 6 : 5) * nth * nphi + 3 * 4) * sizeof(double);
-  if (do_lapl && shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the grid kernel's LDS planes");
-  const bool ext = (x_func > 0 && xc::is_ext(x_func)) || (c_func > 0 && xc::is_ext(c_func));
-  const void *kgrid = ext ? (const void *)k_xc_grid<true> : (const void *)k_xc_grid<false>;
-  if (shb > 64 * 1024) HFG_HIP_CHECK(hipFuncSetAttribute(kgrid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  if (ext)
-    hipLaunchKernelGGL(k_xc_grid<true>, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
-                       t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
-                       x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p);
-  else
-    hipLaunchKernelGGL(k_xc_grid<false>, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
-                       t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
-                       x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p);
-  launch_xc_fock_theta(ctx, NQ, G, nth, maxgrp, a.Fo.p, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, do_grad, do_tau, ctx->shard_rank,
-                       ctx->shard_n, a.GA.p, a.GB.p, a.GC.p, do_lapl, a.GL.p);
-  hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))), xc_fock_radial_lds(p, nq, do_lapl),
-                     ctx->stream, a.GA.p, a.GB.p, a.GC.p, (const double *)a.GL.p, t->rad_B.p, t->rad_dB.p, (const double *)t->rad_L.p,
-                     t->shell_l.p, t->rad_sh.p, A, E, p, nq, do_grad, do_tau, do_lapl, ctx->shard_rank, ctx->shard_n, dHc);
-  hipLaunchKernelGGL(k_xc_sum_partials, dim3(1), dim3(64), 0, ctx->stream, a.partial.p, NQ, dScal);
+  hipLaunchKernelGGL(k_xc_density_theta, dim3((unsigned)pl.NQ, G * G), dim3(std::min(256, round_up64(nth))),
+                     (pl.do_lapl ? 4 : 3) * pl.maxgrp * pl.maxgrp * sizeof(double), ctx->stream, a.D0.p, a.D1.p, (const double *)a.D2.p,
+                     (const double *)a.D3.p, t->Th.p, t->dTh.p, t->shell_l.p, t->rad_sh.p, A, nth, G, t->grp_off.p, t->grp_shell.p,
+                     pl.do_grad, pl.do_tau, pl.do_lapl, pl.NQ, ctx->shard_rank, ctx->shard_n, dV);
+}
+
+// Fock stage of one spin: the planes of Fo at dFo -> compact matrix
+static void xc_fock_stage(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, const XCPlan &pl, double *dFo, double *dHc) {
+  const int A = t->A, E = t->E, p = t->p, nq = t->nq;
+  launch_xc_fock_theta(ctx, pl.NQ, t->G, t->ntheta, pl.maxgrp, dFo, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, pl.do_grad,
+                       pl.do_tau, ctx->shard_rank, ctx->shard_n, a.GA.p, a.GB.p, a.GC.p, pl.do_lapl, a.GL.p);
+  hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))), xc_fock_radial_lds(p, nq, pl.do_lapl),
+                     ctx->stream, a.GA.p, a.GB.p, (const double *)a.GC.p, (const double *)a.GL.p, t->rad_B.p, t->rad_dB.p,
+                     (const double *)t->rad_L.p, t->shell_l.p, t->rad_sh.p, A, E, p, nq, pl.do_grad, pl.do_tau, pl.do_lapl, ctx->shard_rank,
+                     ctx->shard_n, dHc);
+}
+
+// the grid kernel of one build: its EXT instantiation if the plan asks for it, shb bytes of dynamic LDS, one workgroup per
+// radial point; tail: the arguments behind the tables that both grid kernels share
+template <typename K, typename... Tail>
+static void launch_xc_grid(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, const XCPlan &pl, K k_ext, K k_plain, size_t shb,
+                           int x_func, int c_func, Tail... tail) {
+  K k = pl.ext ? k_ext : k_plain;
+  if (shb > 64 * 1024) HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
+  hipLaunchKernelGGL(k, dim3((unsigned)pl.NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p, t->th_s.p, t->th_w.p,
+                     t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, t->G, t->ntheta, t->nphi, t->Rhalf, t->geom, x_func, c_func, pl.do_grad,
+                     pl.do_tau, pl.do_lapl, pl.thr, pl.NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, tail...);
+}
+
+void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPc, double *dHc, double *dScal,
+                double thr) {
+  hfg_dev_tables *t = tables_of(ctx, basis);
+  const XCPlan pl = xc_plan(t, x_func, c_func, thr);
+  FockAux &a = aux_for(ctx, basis);
+  const int npl = pl.do_lapl ? 6 : 5;  // planes of V and Fo, and of the kernel's LDS potentials
+  xc_buffers(a, pl, npl);
+  xc_density_stage(ctx, t, a, pl, dPc, a.V.p);
+  size_t shb = (size_t)(npl * t->ntheta * t->nphi + 3 * 4) * sizeof(double);
+  if (pl.do_lapl && shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the grid kernel's LDS planes");
+  launch_xc_grid(ctx, t, a, pl, k_xc_grid<true>, k_xc_grid<false>, shb, x_func, c_func);
+  xc_fock_stage(ctx, t, a, pl, a.Fo.p, dHc);
+  hipLaunchKernelGGL(k_xc_sum_partials, dim3(1), dim3(64), 0, ctx->stream, a.partial.p, pl.NQ, dScal);
   HFG_HIP_CHECK(hipGetLastError());
 }
 
-/// External functional parameters for the following XC builds on this stream (NULL / 0: the functional's defaults).
-/// Supported: lda_x {alpha}, gga_x_pbe {kappa, mu}, gga_c_pbe {beta, gamma, BB}, and {omega} of gga_x_ityh, gga_x_sfat,
-/// gga_x_ityh_pbe, gga_x_sfat_pbe -- libxc's parameter lists; anything else throws (std::runtime_error, as libxc's "number of parameters" check does through the reference).
+/// The n external parameters of functional id into the XCPar fields its row names, in order (host/xc_funcs.h); the count has
+/// passed check_xc_params.  A range-separation constant must be positive.
+static void fill_xcpar(xc::XCPar &par, int id, const double *pars, int n) {
+  const helfem::XCFunc *f = helfem::find_xc_func(id);
+  const char *name = f ? f->pars : "";
+  for (int i = 0; i < n; i++) {
+    const size_t len = strcspn(name, ",");
+    double *field = nullptr;
+#define FIELD(m) \
+  if (len == strlen(#m) && !strncmp(name, #m, len)) field = &par.m;
+    FIELD(x_alpha) FIELD(x_kappa) FIELD(x_mu) FIELD(c_beta) FIELD(c_gamma) FIELD(c_BB) FIELD(x_omega)
+#undef FIELD
+    if (!field) throw std::logic_error("xc_funcs.h names an XCPar field that does not exist\n");
+    if (field == &par.x_omega && !(pars[i] > 0.0)) throw std::runtime_error("The range-separation constant omega must be positive.\n");
+    *field = pars[i];
+    name += len + (name[len] == ',');
+  }
+}
+
+/// External functional parameters for the following XC builds on this stream (NULL / 0: the functional's defaults), libxc's
+/// parameter lists as the npar / pars columns of host/xc_funcs.h give them; anything else throws (std::runtime_error, as
+/// libxc's "number of parameters" check does through the reference).
 void set_xc_params(hfg_ctx *ctx, int x_func, const double *x_pars, int nx, int c_func, const double *c_pars, int nc) {
   xc::XCPar par = HFG_XCPAR_DEFAULTS;
   if (nx > 0 && !x_pars) throw std::runtime_error("Exchange functional parameters missing.\n");
   if (nc > 0 && !c_pars) throw std::runtime_error("Correlation functional parameters missing.\n");
   helfem::check_xc_params(x_func, nx, c_func, nc);
-  if (nx > 0) {
-    if (x_func == 1) par.x_alpha = x_pars[0];
-    else if (xc::is_rsgga_x(x_func)) {
-      if (!(x_pars[0] > 0.0)) throw std::runtime_error("The range-separation constant omega must be positive.\n");
-      par.x_omega = x_pars[0];
-    } else {
-      par.x_kappa = x_pars[0];
-      par.x_mu = x_pars[1];
-    }
-  }
-  if (nc > 0) {
-    par.c_beta = c_pars[0];
-    par.c_gamma = c_pars[1];
-    par.c_BB = c_pars[2];
-  }
+  fill_xcpar(par, x_func, x_pars, nx);
+  fill_xcpar(par, c_func, c_pars, nc);
   // the host copy must stay valid until the asynchronous copy has run: a small per-thread ring
   static thread_local xc::XCPar staged[8];
   static thread_local int slot = 0;
@@ -1410,10 +1438,7 @@ void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double 
       double e = 0.0, vr = 0.0, vs = 0.0, vt = 0.0, vl = 0.0;
       if (r >= thr && r > 0.0) {
         const bool live = 0.5 * r >= thr;
-        if (xc::is_ext(id)) xc::eval_add_ext(id, r, s, t, live, e, vr, vs, vt);
-        else if (xc::is_mgga_lapl(id)) xc::eval_add_mgga_lapl(id, r, s, t, l, live, e, vr, vs, vt, vl);
-        else if (xc::is_mgga(id)) xc::eval_add_mgga(id, r, s, t, live, e, vr, vs, vt);
-        else xc::eval_add(id, r, s, live, e, vr, vs);
+        HFG_XC_EVAL_POINT(true, id, r, s, t, l, live, e, vr, vs, vt, vl);
         if (!std::isfinite(vl)) vl = 0.0;
       }
       out(exc, i, e);
@@ -1429,14 +1454,7 @@ void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double 
       const double ra = std::max(r0, thr), rb = std::max(r1, thr);
       const double saa = in(sigma, 3 * i), sab = in(sigma, 3 * i + 1), sbb = in(sigma, 3 * i + 2);
       const double ta = in(tau, 2 * i), tb = in(tau, 2 * i + 1), la = in(lapl, 2 * i), lb = in(lapl, 2 * i + 1);
-      if (xc::is_ext(id))
-        xc::eval_add_ext_pol(id, ra, rb, saa, sab, sbb, ta, tb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb, vta, vtb);
-      else if (xc::is_mgga_lapl(id))
-        xc::eval_add_mgga_lapl_pol(id, ra, rb, saa, sab, sbb, ta, tb, la, lb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb, vta, vtb,
-                                   vla, vlb);
-      else if (xc::is_mgga(id))
-        xc::eval_add_mgga_pol(id, ra, rb, saa, sab, sbb, ta, tb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb, vta, vtb);
-      else xc::eval_add_pol(id, ra, rb, saa, sab, sbb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb);
+      HFG_XC_EVAL_POINT_POL(true, id, ra, rb, saa, sab, sbb, ta, tb, la, lb, r0 >= thr, r1 >= thr, e, va, vb, vsaa, vsab, vsbb, vta, vtb, vla, vlb);
       if (!std::isfinite(vla)) vla = 0.0;
       if (!std::isfinite(vlb)) vlb = 0.0;
     }
@@ -1461,22 +1479,11 @@ void xc_eval_host_ext(int id, const double *pars, int npars, int nspin, size_t n
   if (npars > 0 && !pars) throw std::runtime_error("Functional parameters missing.\n");
   xc::XCPar par = HFG_XCPAR_DEFAULTS;
   if (npars > 0) {
-    if (id == 130) {
-      helfem::check_xc_params(0, 0, id, npars);
-      par.c_beta = pars[0];
-      par.c_gamma = pars[1];
-      par.c_BB = pars[2];
-    } else {
-      helfem::check_xc_params(id, npars, 0, 0);
-      if (id == 1) par.x_alpha = pars[0];
-      else if (xc::is_rsgga_x(id)) {
-        if (!(pars[0] > 0.0)) throw std::runtime_error("The range-separation constant omega must be positive.\n");
-        par.x_omega = pars[0];
-      } else {
-        par.x_kappa = pars[0];
-        par.x_mu = pars[1];
-      }
-    }
+    // in the role of its row; an id that takes no parameters is refused in the words for an exchange functional
+    const helfem::XCFunc *f = helfem::find_xc_func(id);
+    if (f && f->npar > 0 && !strcmp(f->role, "c")) helfem::check_xc_params(0, 0, id, npars);
+    else helfem::check_xc_params(id, npars, 0, 0);
+    fill_xcpar(par, id, pars, npars);
   }
   struct Reset {  // the defaults come back whatever happens
     ~Reset() { xc::host_xcpar() = xc::XCPar HFG_XCPAR_DEFAULTS; }
@@ -1503,75 +1510,19 @@ void xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const d
 void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPca, const double *dPcb,
                     double *dHca, double *dHcb, double *dScal, double thr) {
   hfg_dev_tables *t = tables_of(ctx, basis);
-  if (!t->have_xc) throw std::runtime_error("XC grid tables were not uploaded (hfg_basis_upload with ldft,mdft > 0)\n");
-  if ((x_func > 0 && !xc::is_supported(x_func)) || (c_func > 0 && !xc::is_supported(c_func)))
-    throw std::runtime_error("Functional not found!");
+  const XCPlan pl = xc_plan(t, x_func, c_func, thr);
   FockAux &a = aux_for(ctx, basis);
-  const int A = t->A, E = t->E, p = t->p, nq = t->nq, G = t->G, nth = t->ntheta, nphi = t->nphi;
-  const size_t NQ = (size_t)E * nq, AA = (size_t)A * A;
-  int do_grad = ((x_func > 0 && xc::is_gga(x_func)) || (c_func > 0 && xc::is_gga(c_func))) ? 1 : 0;
-  // Laplacian-dependent meta-GGAs (the atomic program only; both available ones need tau as well)
-  const int do_lapl = ((x_func > 0 && xc::is_mgga_lapl(x_func)) || (c_func > 0 && xc::is_mgga_lapl(c_func))) ? 1 : 0;
-  if (do_lapl && t->geom != 1) throw std::logic_error("Laplacian not implemented!\n");  // diatomic dftgrid.cpp:115-116, 209-210
-  int do_tau = ((x_func > 0 && xc::is_mgga(x_func)) || (c_func > 0 && xc::is_mgga(c_func)) || do_lapl) ? 1 : 0;
-  // meta-GGAs: a floor under the density threshold.  Below 1e-50 the tau-dependent expressions overflow (tau_unif ~ n^(5/3),
-  // p ~ sigma / n^(8/3)) and return NaN where the point carries nothing; libxc keeps such points out with its own tau and
-  // sigma thresholds, --dftthr 0 would switch the density threshold off.  Far-field densities of an SCF density are
-  // rounding noise of the eigensolver at that level (tests/test_gpu_fullsize.py::test_fullsize_xc_without_density_threshold).
-  if (do_tau) thr = std::max(thr, 1e-40);
-  const int npl = do_lapl ? 6 : (do_tau ? 5 : 3);
-  a.D0.resize(NQ * AA);
-  a.D1.resize(NQ * AA);
-  a.GA.resize(NQ * AA);
-  a.GB.resize(NQ * AA);
-  if (do_tau) {
-    a.D2.resize(NQ * AA);
-    a.GC.resize(NQ * AA);
-  }
-  if (do_lapl) {
-    a.D3.resize(NQ * AA);
-    a.GL.resize(NQ * AA);
-  }
-  const size_t nv = NQ * G * G * nth;
-  a.V.resize(2 * npl * nv);
-  a.Fo.resize(2 * npl * nv);
-  a.partial.resize(3 * NQ);
-  int maxgrp = 0;
-  for (int g = 0; g < G; g++) maxgrp = std::max(maxgrp, t->h_grp_off[g + 1] - t->h_grp_off[g]);
-  for (int sp = 0; sp < 2; sp++) {
-    hipLaunchKernelGGL(k_xc_density_radial, dim3(A * A, E), dim3(256), xc_density_radial_lds(p, nq, do_lapl),
-                       ctx->stream, sp ? dPcb : dPca, t->rad_B.p, t->rad_dB.p, (const double *)t->rad_L.p, A, E, p, nq, do_grad, do_tau,
-                       do_lapl, ctx->shard_rank, ctx->shard_n, a.D0.p, a.D1.p, a.D2.p, a.D3.p);
-    hipLaunchKernelGGL(k_xc_density_theta, dim3((unsigned)NQ, G * G), dim3(std::min(256, round_up64(nth))),
-                       (do_lapl ? 4 : 3) * maxgrp * maxgrp * sizeof(double), ctx->stream, a.D0.p, a.D1.p, (const double *)a.D2.p,
-                       (const double *)a.D3.p, t->Th.p, t->dTh.p, t->shell_l.p, t->rad_sh.p, A, nth, G, t->grp_off.p, t->grp_shell.p,
-                       do_grad, do_tau, do_lapl, NQ, ctx->shard_rank, ctx->shard_n, a.V.p + (size_t)sp * npl * nv);
-  }
-  const int npot2 = do_lapl ? 12 : (do_tau ? 10 : 8);  // LDS potential planes, both spins
-  int rowc = nth;  // theta rows per pass through LDS
-  while ((size_t)(npot2 * rowc * nphi + 3 * 4) * sizeof(double) > tuning().xc_lds_limit && rowc > 1) rowc = (rowc + 1) / 2;
-  size_t shb = (size_t)(npot2 * rowc * nphi + 3 * 4) * sizeof(double);
+  const int npl = pl.do_lapl ? 6 : (pl.do_tau ? 5 : 3);  // planes of V and Fo per spin
+  xc_buffers(a, pl, 2 * npl);
+  for (int sp = 0; sp < 2; sp++) xc_density_stage(ctx, t, a, pl, sp ? dPcb : dPca, a.V.p + (size_t)sp * npl * pl.nv);
+  const int npot2 = pl.do_lapl ? 12 : (pl.do_tau ? 10 : 8);  // LDS potential planes, both spins
+  int rowc = t->ntheta;  // theta rows per pass through LDS
+  while ((size_t)(npot2 * rowc * t->nphi + 3 * 4) * sizeof(double) > tuning().xc_lds_limit && rowc > 1) rowc = (rowc + 1) / 2;
+  size_t shb = (size_t)(npot2 * rowc * t->nphi + 3 * 4) * sizeof(double);
   if (shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the polarised grid kernel's LDS tile");
-  const bool ext = (x_func > 0 && xc::is_ext(x_func)) || (c_func > 0 && xc::is_ext(c_func));
-  const void *kgrid = ext ? (const void *)k_xc_grid_pol<true> : (const void *)k_xc_grid_pol<false>;
-  if (shb > 64 * 1024) HFG_HIP_CHECK(hipFuncSetAttribute(kgrid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  if (ext)
-    hipLaunchKernelGGL(k_xc_grid_pol<true>, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
-                       t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
-                       x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, rowc);
-  else
-    hipLaunchKernelGGL(k_xc_grid_pol<false>, dim3((unsigned)NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p,
-                       t->th_s.p, t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, G, nth, nphi, t->Rhalf, t->geom,
-                       x_func, c_func, do_grad, do_tau, do_lapl, thr, NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, rowc);
-  for (int sp = 0; sp < 2; sp++) {
-    launch_xc_fock_theta(ctx, NQ, G, nth, maxgrp, a.Fo.p + (size_t)sp * npl * nv, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, do_grad,
-                         do_tau, ctx->shard_rank, ctx->shard_n, a.GA.p, a.GB.p, a.GC.p, do_lapl, a.GL.p);
-    hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))), xc_fock_radial_lds(p, nq, do_lapl),
-                       ctx->stream, a.GA.p, a.GB.p, (const double *)a.GC.p, (const double *)a.GL.p, t->rad_B.p, t->rad_dB.p,
-                       (const double *)t->rad_L.p, t->shell_l.p, t->rad_sh.p, A, E, p, nq, do_grad, do_tau, do_lapl, ctx->shard_rank,
-                       ctx->shard_n, sp ? dHcb : dHca);
-  }
-  hipLaunchKernelGGL(k_xc_sum_partials, dim3(1), dim3(64), 0, ctx->stream, a.partial.p, NQ, dScal);
+  launch_xc_grid(ctx, t, a, pl, k_xc_grid_pol<true>, k_xc_grid_pol<false>, shb, x_func, c_func, rowc);
+  for (int sp = 0; sp < 2; sp++) xc_fock_stage(ctx, t, a, pl, a.Fo.p + (size_t)sp * npl * pl.nv, sp ? dHcb : dHca);
+  hipLaunchKernelGGL(k_xc_sum_partials, dim3(1), dim3(64), 0, ctx->stream, a.partial.p, pl.NQ, dScal);
   HFG_HIP_CHECK(hipGetLastError());
 }
 

@@ -128,6 +128,15 @@ thread_local int g_iguess = 0;  // --iguess of the following hfg_scf_* calls of 
 
 bool host_driver() { return helfem::tuning_live().scf_host; }  // (read at every call)
 
+// --method in the drivers' options: the two ids and, from the exchange id's row, the exact exchange the loop adds (throws on
+// an unknown functional)
+void set_method(helfem::scf::Options &o, const char *method) {
+  o.method = method;
+  helfem::parse_xc_func(o.x_func, o.c_func, o.method);
+  helfem::range_separation(o.x_func, o.omega, o.kfrac, o.kshort);
+  o.rs_kind = helfem::rs_kind(o.x_func);
+}
+
 // set-up of src/diatomic/main.cpp:245-430 (basis, quadrature defaults, symmetry), then the device-resident loop
 helfem::scf::Result run_diatomic_device(hfg_ctx *ctx, const helfem::scf::Options &opt) {
   int nel = opt.Z1 + opt.Z2 - opt.Q;
@@ -238,17 +247,10 @@ int hfg_scf_diatomic(hfg_ctx *ctx, int Z1, int Z2, double Rbond, const int *lmma
     o.igrid = igrid;
     o.zexp = zexp;
     o.lpad = lpad;
-    o.method = method;
-    helfem::parse_xc_func(o.x_func, o.c_func, o.method);
+    set_method(o, method);
     o.iguess = g_iguess;
     o.readocc = g_readocc;
     o.occs = g_occs;
-    helfem::range_separation(o.x_func, o.omega, o.kfrac, o.kshort);
-    {
-      bool erf, yuk;
-      helfem::is_range_separated(o.x_func, erf, yuk);
-      o.rs_kind = yuk ? 1 : (erf ? 2 : 0);
-    }
     o.ldft = ldft;
     o.mdft = mdft;
     o.symmetry = symmetry;
@@ -307,17 +309,10 @@ int hfg_scf_atomic(hfg_ctx *ctx, int Z, int Q, int lmax, int mmax, int nelem, in
     o.Rmax = Rmax;
     o.igrid = igrid;
     o.zexp = zexp;
-    o.method = method;
-    helfem::parse_xc_func(o.x_func, o.c_func, o.method);
+    set_method(o, method);
     o.iguess = g_iguess;
     o.readocc = g_readocc;
     o.occs = g_occs;
-    helfem::range_separation(o.x_func, o.omega, o.kfrac, o.kshort);
-    {
-      bool erf, yuk;
-      helfem::is_range_separated(o.x_func, erf, yuk);
-      o.rs_kind = yuk ? 1 : (erf ? 2 : 0);
-    }
     o.ldft = ldft;
     o.mdft = mdft;
     o.symmetry = symmetry;
@@ -519,9 +514,7 @@ static void check_options(const hfg_scf_options &p, const hfg_scf_atomic_extras 
   }
   int x_func, c_func;
   helfem::parse_xc_func(x_func, c_func, p.method);  // throws on unknown functionals
-  bool erf, yuk;
-  helfem::is_range_separated(x_func, erf, yuk);
-  if (p.program == 0 && (erf || yuk)) throw std::logic_error("Range separated functionals are not supported.\n");  // diatomic/main.cpp:393
+  if (p.program == 0 && helfem::rs_kind(x_func)) throw std::logic_error("Range separated functionals are not supported.\n");  // diatomic/main.cpp:393
   if (p.program == 0 && (helfem::needs_laplacian(x_func) || helfem::needs_laplacian(c_func)))
     throw std::logic_error("Laplacian not implemented!\n");  // diatomic dftgrid.cpp:115-116
   helfem::check_xc_params(x_func, p.n_x_pars, c_func, p.n_c_pars);  // before the device: the refusal of set_xc_params
@@ -580,14 +573,7 @@ static void map_options(const hfg_scf_options &p, const hfg_scf_atomic_extras *x
   o.maxit = p.maxit;
   o.convthr = p.convthr;
   o.diag = p.diag != 0;
-  o.method = p.method;
-  helfem::parse_xc_func(o.x_func, o.c_func, o.method);
-  helfem::range_separation(o.x_func, o.omega, o.kfrac, o.kshort);
-  {
-    bool erf, yuk;
-    helfem::is_range_separated(o.x_func, erf, yuk);
-    o.rs_kind = yuk ? 1 : (erf ? 2 : 0);
-  }
+  set_method(o, p.method);
   o.ldft = p.ldft;
   o.mdft = p.mdft;
   o.dftthr = p.dftthr;

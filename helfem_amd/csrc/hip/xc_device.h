@@ -6,6 +6,7 @@
 // dual numbers), deliberately a different route from the oracle's hand-derived formulas.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../host/xc_funcs.h"
 
 namespace hfg {
 namespace xc {
@@ -247,25 +248,31 @@ __host__ __device__ inline Dual eps_gga_c_pbe(Dual rho, Dual sigma, double beta,
   return ec + H;
 }
 
-// gga_x_ityh_pbe / gga_x_sfat_pbe: the integer ids are libxc's as recalled, not confirmed against libxc itself;
-// the names are the interface
-#define HFG_ID_ITYH_PBE 623
-#define HFG_ID_SFAT_PBE 601
-__host__ __device__ inline bool is_gga(int id) {
-  return id == 101 || id == 130 || id == 406 || id == 202 || id == 231 || id == 106 || id == 131 || id == 402 || id == 206 ||
-         id == 72 || id == 102 || id == 116 || id == 133 || id == 263 || id == 264 || id == 267 || id == 529 || id == 530 ||
-         id == HFG_ID_ITYH_PBE || id == HFG_ID_SFAT_PBE || id == 433 || id == 470 || id == 455 || id == 468 || id == 467;
-}
-__host__ __device__ inline bool is_supported(int id) {
-  return id == 1 || id == 7 || id == 8 || id == 12 || id == 13 || id == 101 || id == 130 || id == 406 || id == 202 || id == 231 ||
-         id == 546 || id == 641 || id == 178 || id == 106 || id == 131 || id == 402 || id == 206 || id == 72 || id == 102 || id == 116 ||
-         id == 133 || id == 263 || id == 264 || id == 267 || id == 529 || id == 530 || id == HFG_ID_ITYH_PBE ||
-         id == HFG_ID_SFAT_PBE || id == 433 || id == 470 || id == 455 || id == 468 || id == 467;
-}
-
-__host__ __device__ inline bool is_exchange(int id) {
-  return id == 1 || id == 101 || id == 546 || id == 641 || id == 202 || id == 106 || id == 102 || id == 116 || id == 263 || id == 264;
-}
+// The id predicates of the point code and of the launch plan, generated from the rows of host/xc_funcs.h (the columns are
+// explained there); an id that is not in the list answers false everywhere.
+#define HFG_XC_PREDICATE(fn)                                                                                  \
+  __host__ __device__ inline bool fn(int id) {                                                                \
+    switch (id) {                                                                                             \
+      HELFEM_XC_FUNCS(HFG_XC_CASE_##fn)                                                                       \
+      default: return false;                                                                                  \
+    }                                                                                                         \
+  }
+#define HFG_XC_CASE_is_supported(id_, ...) case id_: return true;
+#define HFG_XC_CASE_is_gga(id_, name, role, grad, ...) case id_: return grad;
+#define HFG_XC_CASE_is_mgga(id_, name, role, grad, tau, lapl, ...) case id_: return (tau) && !(lapl);
+#define HFG_XC_CASE_is_mgga_lapl(id_, name, role, grad, tau, lapl, ...) case id_: return lapl;
+#define HFG_XC_CASE_is_ext(id_, name, role, grad, tau, lapl, ext, ...) case id_: return (ext) != 0;
+#define HFG_XC_CASE_is_rsgga_x(id_, name, role, grad, tau, lapl, ext, ...) case id_: return (ext) == 2;
+#define HFG_XC_CASE_is_rsgga_hyb(id_, name, role, grad, tau, lapl, ext, ...) case id_: return (ext) == 3;
+#define HFG_XC_CASE_is_exchange(id_, name, role, grad, tau, lapl, ext, skip_dead, ...) case id_: return skip_dead;
+HFG_XC_PREDICATE(is_supported)
+HFG_XC_PREDICATE(is_gga)        /// needs the gradient (the meta-GGAs included)
+HFG_XC_PREDICATE(is_mgga)       /// tau-dependent without the Laplacian: eval_add_mgga, or eval_add_ext for SCAN's ids
+HFG_XC_PREDICATE(is_mgga_lapl)  /// Laplacian-dependent (tau as well): eval_add_mgga_lapl
+HFG_XC_PREDICATE(is_ext)        /// evaluated by eval_add_ext / eval_add_ext_pol alone
+HFG_XC_PREDICATE(is_rsgga_x)    /// short-range GGA exchange primitive
+HFG_XC_PREDICATE(is_rsgga_hyb)  /// range-separated GGA hybrid
+HFG_XC_PREDICATE(is_exchange)   /// the skip_dead column: left out as a whole where a spin channel is below the threshold
 
 /// adds functional id's exc (per particle), vrho, vsigma at one point; rho >= threshold assumed.
 /// live: the density of one spin channel, rho/2, reaches the threshold.  Exchange is a sum over the spin channels and
@@ -727,9 +734,6 @@ __host__ __device__ inline T3 mg_eps_tpss_c(T3 rho, T3 sig, T3 tau) {
   return rev * (1.0 + d * rev * z2 * z);
 }
 
-/// tau-dependent (SCAN's ids included: the grid kernels run them in their is_ext instantiation, below)
-__host__ __device__ inline bool is_mgga(int id) { return id == 202 || id == 231 || id == 263 || id == 264 || id == 267; }
-
 /// adds a meta-GGA's exc, vrho, vsigma, vtau at one point (rho >= threshold assumed)
 __host__ __device__ inline void eval_add_mgga(int id, double rho, double sigma, double tau, bool live, double &exc,
                                               double &vrho, double &vsigma, double &vtau) {
@@ -955,8 +959,6 @@ __host__ __device__ inline Dual fx_pbe(Dual rho, Dual sigma, double kappa, doubl
   Dual s2 = sigma / (4.0 * kf * kf * rho * rho);
   return 1.0 + kappa - kappa / (1.0 + (mu / kappa) * s2);
 }
-__host__ __device__ inline bool is_rsgga_x(int id) { return id == 529 || id == 530 || id == HFG_ID_ITYH_PBE || id == HFG_ID_SFAT_PBE; }
-__host__ __device__ inline bool is_rsgga_hyb(int id) { return id == 433 || id == 470 || id == 455 || id == 468 || id == 467; }
 /// exchange part of a short-range GGA primitive or hybrid: eps_x^LDA F_x [wx + wsr att(a)].  Always inlined: as a device function
 /// of its own it would renumber the local labels of every kernel behind it in the module, and the kernels of the other
 /// functionals are kept identical to what they were, text included.
@@ -1005,9 +1007,6 @@ __host__ __device__ __attribute__((always_inline)) inline Dual eps_rsgga_x(int i
   return eps_lda_x(rho) * (wx * F + wsr * Fatt);
 }
 
-__host__ __device__ inline bool is_ext(int id) {
-  return id == 263 || id == 264 || id == 267 || id == 102 || id == 116 || id == 133 || is_rsgga_x(id) || is_rsgga_hyb(id);
-}
 __host__ __device__ inline double ext_pbe_kappa(int id) { return id == 102 ? 1.245 : 0.804; }
 __host__ __device__ inline double ext_pbe_mu(int id) { return id == 102 ? HFG_PBE_MU : 10.0 / 81.0; }
 
@@ -1340,8 +1339,6 @@ __host__ __device__ inline DN<9> cs_pol(const DN<9> &ra, const DN<9> &rb, const 
   return (-HFG_LYP_A) * gam * (n + (2.0 * HFG_LYP_B) * rm53 * br * dnexp((-HFG_LYP_C) * rm13)) / den;
 }
 
-__host__ __device__ inline bool is_mgga_lapl(int id) { return id == 206 || id == 72; }
-
 /// adds a Laplacian-dependent meta-GGA's exc, vrho, vsigma, vtau, vlapl at one point (rho >= threshold assumed); live as in
 /// eval_add (the exchange channels carry rho/2 each)
 __host__ __device__ inline void eval_add_mgga_lapl(int id, double rho, double sigma, double tau, double lapl, bool live, double &exc,
@@ -1396,5 +1393,31 @@ __host__ __device__ inline void eval_add_mgga_lapl_pol(int id, double ra, double
   vlb += en.d[8];
 }
 
+
 }  // namespace xc
 }  // namespace hfg
+
+// One functional at one point through the evaluator its row names: the four-way chain, written once for the grid kernels and
+// for xc_eval_host (fock.hip).  EXT_: whether eval_add_ext can be reached (the kernels' template argument; true on the host);
+// without it an is_ext id falls through to evaluators that ignore it.  The arguments are those of the eval_add_* functions.
+// Macros, not functions: through a function, always inlined or not, the compiler allocates the registers of k_xc_grid<false>
+// and k_xc_grid_pol<false> differently (4 bytes more scratch), and these kernels are kept as they were, instruction by instruction.
+#define HFG_XC_EVAL_POINT(EXT_, id, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap)                          \
+  do {                                                                                                                 \
+    if (EXT_ && xc::is_ext(id)) xc::eval_add_ext(id, rho, sigma, tau, live, exc, vrho, vsig, vtau);                    \
+    else if (xc::is_mgga_lapl(id)) xc::eval_add_mgga_lapl(id, rho, sigma, tau, lapl, live, exc, vrho, vsig, vtau, vlap); \
+    else if (xc::is_mgga(id)) xc::eval_add_mgga(id, rho, sigma, tau, live, exc, vrho, vsig, vtau);                     \
+    else xc::eval_add(id, rho, sigma, live, exc, vrho, vsig);                                                          \
+  } while (0)
+#define HFG_XC_EVAL_POINT_POL(EXT_, id, ra, rb, saa, sab, sbb, ta, tb, la, lb, live_a, live_b, exc, va, vb, vsaa, vsab, vsbb, vta, vtb, \
+                              vla, vlb)                                                                                \
+  do {                                                                                                                 \
+    if (EXT_ && xc::is_ext(id))                                                                                        \
+      xc::eval_add_ext_pol(id, ra, rb, saa, sab, sbb, ta, tb, live_a, live_b, exc, va, vb, vsaa, vsab, vsbb, vta, vtb); \
+    else if (xc::is_mgga_lapl(id))                                                                                     \
+      xc::eval_add_mgga_lapl_pol(id, ra, rb, saa, sab, sbb, ta, tb, la, lb, live_a, live_b, exc, va, vb, vsaa, vsab, vsbb, vta, vtb, \
+                                 vla, vlb);                                                                            \
+    else if (xc::is_mgga(id))                                                                                          \
+      xc::eval_add_mgga_pol(id, ra, rb, saa, sab, sbb, ta, tb, live_a, live_b, exc, va, vb, vsaa, vsab, vsbb, vta, vtb); \
+    else xc::eval_add_pol(id, ra, rb, saa, sab, sbb, live_a, live_b, exc, va, vb, vsaa, vsab, vsbb);                   \
+  } while (0)

@@ -196,19 +196,10 @@ int hfg_exchange(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *K);
 /* arma::mat atomic::basis::TwoDBasis::rs_exchange(const arma::mat & P) const   TwoDBasis.h:184, TwoDBasis.cpp:1142 */
 int hfg_rs_exchange(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *K);
 /* void DFTGrid::eval_Fxc(x_func,x_pars,c_func,c_pars,P,H,Exc,Nel,Ekin,thr)   dftgrid.h:179 (restricted).
- * Functional ids are libxc's: 1 lda_x, 7 lda_c_vwn, 12 lda_c_pw, 101 gga_x_pbe, 130 gga_c_pbe, 406 hyb_gga_xc_pbeh
- * (its 0.25 exact exchange is the caller's K), 202 mgga_x_tpss, 231 mgga_c_tpss (Ekin returns the integral of tau),
- * 13 lda_c_pw_mod, 546 lda_x_erf, 641 lda_x_yukawa (omega = 0.3, libxc's default), 178 hyb_lda_xc_cam_lda0 (DFT part;
- * the caller adds 0.5 K - 0.25 K_erfc(omega = 1/3)), 206 mgga_x_br89 and 72 mgga_c_cs (these two depend on the density
- * Laplacian: atomic bases only, a diatomic basis fails with "Laplacian not implemented!"), 263 mgga_x_scan, 267 mgga_c_scan,
- * 264 hyb_mgga_x_scan0 (DFT part: 0.75 mgga_x_scan; the caller adds 0.25 K), 102 gga_x_pbe_r (revPBE), 116 gga_x_pbe_sol,
- * 133 gga_c_pbe_sol; the short-range GGA exchange primitives 529 gga_x_ityh (B88, erfc, omega = 0.2), 530 gga_x_sfat (B88,
- * Yukawa, omega = 0.44), 623 gga_x_ityh_pbe, 601 gga_x_sfat_pbe (the same with PBE's enhancement factor; these two integer ids
- * are not confirmed against libxc, the names are the interface), and the DFT parts of the range-separated GGA hybrids 433
- * hyb_gga_xc_cam_b3lyp, 470 hyb_gga_xc_camy_b3lyp, 455 hyb_gga_xc_camy_blyp, 468 hyb_gga_xc_lcy_blyp, 467 hyb_gga_xc_lcy_pbe
- * (the caller adds alpha K + beta K_screened of hfg_xc_exact_exchange, the screened kernel being that of hfg_xc_rs_kind);
- * <=0 none.  The spin-polarised
- * entry takes the same ids. */
+ * Functional ids are libxc's; hfg_xc_func_table() lists the ones of this build, <= 0 is none.  Of a hybrid the DFT part is
+ * evaluated: the caller adds alpha K + beta K_screened of hfg_xc_exact_exchange, the screened kernel being that of
+ * hfg_xc_rs_kind.  The Laplacian-dependent functionals take atomic bases only (a diatomic basis fails with "Laplacian not
+ * implemented!"); for the meta-GGAs Ekin returns the integral of tau.  The spin-polarised entry takes the same ids. */
 int hfg_xc_fock(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *P, double *H, double *Exc,
                 double *Nel, double *Ekin, double dens_thr);
 /* void DFTGrid::eval_Fxc(x_func,x_pars,c_func,c_pars,Pa,Pb,Ha,Hb,Exc,Nel,Ekin,beta,thr)   dftgrid.h:181,
@@ -248,6 +239,12 @@ int hfg_xc_exact_exchange(int x_func, double *omega, double *alpha, double *beta
 /* The screened kernel of an exchange id (is_range_separated, dftfuncs.cpp:464): 0 none, 1 Yukawa exp(-omega r)/r, 2
  * erfc(omega r)/r -- the rs_kind hfg_compute_rs_tei needs for the beta term of hfg_xc_exact_exchange */
 int hfg_xc_rs_kind(int x_func);
+/* The functionals of this build (no context, no device), one line each, tab separated: id, name, role (x, c or xc), needs
+ * the gradient, tau, the Laplacian (0 / 1 each), evaluated by the EXT instantiation of the grid kernels (0 no; 1 SCAN and the
+ * PBE variants, 2 short-range GGA exchange primitive, 3 range-separated GGA hybrid), skipped as a whole where a spin channel
+ * is below the density threshold, then kfrac, kshort, omega, rs_kind as hfg_xc_exact_exchange (alpha, beta) and hfg_xc_rs_kind
+ * return them, the number of external parameters and the parameters they set, a remark.  buf / cap as hfg_tuning_table. */
+int hfg_xc_func_table(char *buf, size_t cap);
 /* Radial tables of an atomic basis at the quadrature points of element iel (nquad x Nprim(iel), column-major): which 0 =
  * B/r (RadialBasis::get_bf), 1 = d/dr (B/r) (get_df), 2 = d^2/dr^2 (B/r) (get_lf), 3 = the radial coordinates
  * (nquad x 1).  out = NULL returns the shape only. */
