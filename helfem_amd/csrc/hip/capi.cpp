@@ -1,10 +1,9 @@
 // C ABI (include/helfem_gpu.h): contexts, host-side basis API, host-pointer and device-pointer
 // entry points.  No torch types, no exceptions across the boundary.
-#include "common.h"
+#include "internal.h"
 #include "../host/checkpoint.h"
 #include "../host/diis.h"
 #include "../host/dftfuncs.h"
-#include "tables.h"
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -13,53 +12,6 @@ namespace hfg {
 static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
 
-// implemented in the .hip translation units
-void coulomb_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dJ);
-void xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dH, double *dScal,
-                 double thr);
-void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, bool rs = false, const double *Lknown = nullptr,
-                  int rknown = 0);
-void set_xc_params(hfg_ctx *ctx, int x_func, const double *x_pars, int nx, int c_func, const double *c_pars, int nc);
-void xc_fock_pol_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPa, const double *dPb,
-                     double *dHa, double *dHb, double *dScal, double thr);
-void model_potential_dev(hfg_ctx *ctx, hfg_basis *basis, int kind1, int Z1, double d1, double H1, int kind2, int Z2,
-                         double d2, double H2, double *dH);
-void fock_release(hfg_dev_tables *t);
-void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double *sigma, const double *lapl, const double *tau,
-                  double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau, double thr);
-void xc_eval_host_ext(int id, const double *pars, int npars, int nspin, size_t np, const double *rho, const double *sigma,
-                      const double *lapl, const double *tau, double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau,
-                      double thr);
-size_t fock_compact_size(hfg_basis *basis);
-void fock_compact_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dFc,
-                      double *dScal, double thr);
-void fock_finish_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const double *dH0, const int *dBlockId,
-                     double *dF);
-void exchange_release(hfg_dev_tables *t);
-void exchange_lr_release(hfg_dev_tables *t);
-void compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis);
-void eig_release(hfg_ctx *ctx);
-void dc_release(hfg_ctx *ctx);
-void trd_release(hfg_ctx *ctx);
-void trdp_release(hfg_ctx *ctx);
-void trdp_check_status(hfg_ctx *ctx);
-void trd_measure_gemv(hfg_ctx *ctx, double *ms, int64_t *launches);
-void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda,
-              const double *B, int ldb, double beta, double *C, int ldc);
-void eig_sym_dev(hfg_ctx *ctx, int n, const double *dA, double *dE, double *dC);
-void eig_gsym_dev(hfg_ctx *ctx, int N, int n, const double *dF, const double *dS, double *dE, double *dC);
-void eig_gsym_sub_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
-                      const int64_t *blk_idx, double *dE, double *dC);
-size_t eig_block_buf_size(int nblk, const int64_t *blk_ptr);
-void eig_gsym_sub_pair_dev(hfg_ctx *ctx, int N, const double *dFa, const double *dFb, const double *dS, int nblk, const int64_t *blk_ptr,
-                           const int64_t *blk_idx, double *dEa, double *dCa, double *dEb, double *dCb);
-void eig_blocks_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
-                    const int64_t *blk_idx, double *dBlockBuf);
-void eig_assemble_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
-                      const double *dBlockBuf, double *dE, double *dC);
-void form_sinvh_dev(hfg_ctx *ctx, int N, const double *dS, bool chol, int nblk, const int64_t *blk_ptr,
-                    const int64_t *blk_idx, double *dSinvh);
-void form_density_dev(hfg_ctx *ctx, int N, int ncols, const double *dC, int nocc, double *dP);
 }  // namespace hfg
 
 using namespace hfg;

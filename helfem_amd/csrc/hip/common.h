@@ -107,7 +107,6 @@ struct hfg_ctx {
   std::vector<hipEvent_t> event_pool;
   // scratch
   hfg::DevBuf<double> ws[8];
-  hfg::DevBuf<double> hstage;  // unused placeholder
   double *pinned = nullptr;
   size_t pinned_bytes = 0;
 
@@ -140,7 +139,7 @@ struct hfg_basis {
 };
 
 namespace hfg {
-// one product C = A B (column-major) of a device-side task list (k_dgemm_tasks, dc.hip)
+// one product C = A B (column-major) of a device-side task list (gemm_tasklist_dev, gemm.hip; k_dgemm_tasks, dc.hip)
 struct GemmTask {
   const double *A;
   const double *B;
@@ -156,7 +155,7 @@ struct GemmTask {
                  // 128-row tile are readable memory (their products land in rows of C that are not stored), bit 1 -- likewise
                  // the columns of op(B) from N up to the tile edge; lets partial edge tiles use the 16-byte loads.
                  // (Also fills the struct: task lists are compared bytewise, upload_cached.)
-  // column maps (gemm_tasklist64_map_dev only; op(A) = A, beta == 0): column k of A is A[:, amap[k]], column j of the
+  // column maps (k_dgemm_tasklist_map, GemmHow::map, only; op(A) = A, beta == 0): column k of A is A[:, amap[k]], column j of the
   // product is stored at C[:, cmap[j]].  The merges of divide and conquer (dc.hip) read the non-deflated columns of Q
   // and store every new eigenvector at its ranked place through them.
   const int *amap = nullptr, *cmap = nullptr;

@@ -19,7 +19,7 @@
 //           lam_i = d[org_i] + mu_i by the two-pole "middle way" iteration with bisection safeguard;
 //           zhat_j^2 = prod_i (lam_i - d_j) / (rho prod_{i != j} (d_i - d_j));  U_ji = zhat_j / (d_j - lam_i)
 //           (columns normalised); Q <- [Q_nd U | Q_deflated] sorted by eigenvalue.
-#include "common.h"
+#include "internal.h"
 #include <cstring>
 #include "wave.h"
 
@@ -800,8 +800,6 @@ __global__ void k_dc_copyback(DCBatch b, const DCNode *__restrict__ nodes, int n
 }
 
 // ---- batched FP64 MFMA GEMM over device-side task descriptors (C = A B, column-major) ----------------------------
-void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);  // gemm.hip
-void gemm_tasklist64_map_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
 // (honours the column maps of a task, GemmTask::amap / cmap, like k_dgemm_tasklist_map)
@@ -849,15 +847,6 @@ __global__ __launch_bounds__(256) void k_dgemm_tasks(const GemmTask *__restrict_
         int gm = bm + wm + i * 16 + l15, gn = bn + wn + j * 16 + l4 + 4 * r;
         if (gm < M && gn < N) t.C[(size_t)(t.cmap ? t.cmap[gn] : gn) * t.ldc + gm] = acc[i][j][r];
       }
-}
-
-void gemm_tasks_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int max_tiles) {
-  if (ntasks <= 0 || max_tiles <= 0) return;
-  for (int t0 = 0; t0 < ntasks; t0 += 65535) {
-    int nt = std::min(65535, ntasks - t0);
-    hipLaunchKernelGGL(k_dgemm_tasks, dim3(max_tiles, nt), dim3(256), 0, ctx->stream, dtasks + t0);
-  }
-  HFG_HIP_CHECK(hipGetLastError());
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1045,7 +1034,7 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
       if (tuning().dc_gemm_small)
         hipLaunchKernelGGL(k_dgemm_tasks, dim3(((mx + 63) / 64) * ((mx + 63) / 64), nn), dim3(256), 0, s, w.tasks.p);
       else
-        gemm_tasklist64_map_dev(ctx, w.tasks.p, nn, mx, mx);
+        gemm_tasklist_dev(ctx, w.tasks.p, nn, mx, mx, {GemmTile::T64, /*acc*/ false, /*split2*/ false, /*map*/ true});
       continue;
     }
     hipLaunchKernelGGL(k_dc_zhat, dim3((mx + 3) / 4, nn), dim3(256), 0, s, b, w.nodes.p, node0, w.kcount.p, w.rho_eff.p);
@@ -1059,7 +1048,7 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
       int tiles = ((mx + 63) / 64) * ((mx + 63) / 64);
       hipLaunchKernelGGL(k_dgemm_tasks, dim3(tiles, nn), dim3(256), 0, s, w.tasks.p);
     } else
-      gemm_tasklist64_dev(ctx, w.tasks.p, nn, mx, mx);
+      gemm_tasklist_dev(ctx, w.tasks.p, nn, mx, mx, {GemmTile::T64});
     if (shr > 64 * 1024)
       HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_dc_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shr));
     hipLaunchKernelGGL(k_dc_rank, dim3(nn, (mx + 31) / 32), dim3(256), shr, s, b, w.nodes.p, node0, w.kcount.p);

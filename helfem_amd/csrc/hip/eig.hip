@@ -15,28 +15,12 @@
 //   5. back-transformation Z <- H_0 ... H_{n-3} Z                k_backtransform (column-parallel, no
 //                                                                inter-workgroup dependency at all)
 //   6. C = X Z                                                   GEMM, then rank sort + scatter
-#include "common.h"
+#include "internal.h"
 #include "wave.h"
 #include <cstdlib>
 #include <cstring>
 
 namespace hfg {
-
-void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_split2_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-bool gemm_prefers_128(hfg_ctx *ctx, long tiles128);
-bool tridiagonalize_takes_chain(int nblk, const int *ns);  // trdp.hip
-void gemm_tasklist_acc_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, bool tile64);
-void gemm_mirror_lower_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxN);
-void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda,
-              const double *B, int ldb, double beta, double *C, int ldc);
-
-void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, double *const *e, double *const *Z);
-int dc_status(hfg_ctx *ctx);
-void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *A, double *const *d, double *const *e,
-                          double *const *tau);
 
 constexpr int MAXB = 8;
 struct EigBatch {
@@ -630,8 +614,7 @@ __global__ __launch_bounds__(64) void k_bt_T(EigBatch b, double *const *__restri
 }
 
 struct EigWork {
-  bool split_full = false;  // this batch's full products run as two half-K workgroups per tile
-  bool tile64 = false;
+  GemmHow full_how;  // how this batch's full products are launched (split2: two half-K workgroups per tile)
   std::vector<int64_t> asm_rows;  // eig_assemble_dev: the index list whose device copy is asm_rows_dev
   DevBuf<long long> asm_rows_dev;
   bool folded = false;      // the last batch formed Y = (X Q)^T beside the divide-and-conquer stage (bt_wy_fold_x)
@@ -917,10 +900,10 @@ static void bt_wy_prepare(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk,
   try {
     double *const *dptr = w.btptr.p;
     hipLaunchKernelGGL(k_bt_extract, dim3((nmax + 255) / 256, nmax, nblk), dim3(256), 0, q, b, dptr);
-    gemm_tasklist64_dev(ctx, w.btgram.p, BT_GS * P * nblk, BT_KB, BT_KB);
+    gemm_tasklist_dev(ctx, w.btgram.p, BT_GS * P * nblk, BT_KB, BT_KB, {GemmTile::T64});
     hipLaunchKernelGGL(k_bt_T, dim3(P, nblk), dim3(BT_KB), 0, q, b, dptr + nblk, dptr + 2 * nblk, P);
-    gemm_tasklist64_dev(ctx, w.bttasks.p, P * nblk, nmax, BT_KB);
-    gemm_tasklist64_dev(ctx, w.btcpl.p, BT_GS * ((P + 1) / 2) * nblk, BT_KB, BT_KB);
+    gemm_tasklist_dev(ctx, w.bttasks.p, P * nblk, nmax, BT_KB, {GemmTile::T64});
+    gemm_tasklist_dev(ctx, w.btcpl.p, BT_GS * ((P + 1) / 2) * nblk, BT_KB, BT_KB, {GemmTile::T64});
   } catch (...) {
     ctx->stream = main;
     ctx->profiling = prof;
@@ -939,12 +922,12 @@ static void bt_wy_apply(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, i
   if (tuning().bt_side && !ctx->avoid_side) HFG_HIP_CHECK(hipStreamWaitEvent(s, ctx->side_ev[1], 0));  // (not reached when X Q was folded)
   // pairs of reflector blocks, last to first: three launches and one read-modify-write of Z per 128 reflectors
   for (int g = NP - 1; g >= 0; g--) {
-    gemm_tasklist64_dev(ctx, w.btslab.p + (size_t)g * BT_S * nblk, BT_S * nblk, BT_PW, nmax);
+    gemm_tasklist_dev(ctx, w.btslab.p + (size_t)g * BT_S * nblk, BT_S * nblk, BT_PW, nmax, {GemmTile::T64});
     // (summing the slabs inside the update's operand loads instead was measured: 2.73 -> 3.11 ms, six times the operand
     // traffic on every tile's critical path)
     hipLaunchKernelGGL(k_bt_wpair, dim3((nmax + 4 * BT_WREP - 1) / (4 * BT_WREP), nblk), dim3(256), 0, s, b, dptr + 3 * nblk, dptr + 4 * nblk,
                        dptr + 5 * nblk, BT_S, BT_GS, NP, g, 0);
-    gemm_tasklist_acc_dev(ctx, w.btupd.p + (size_t)g * nblk, nblk, nmax, nmax, tuning().acc_tile != 128);
+    gemm_tasklist_dev(ctx, w.btupd.p + (size_t)g * nblk, nblk, nmax, nmax, {tuning().acc_tile != 128 ? GemmTile::T64 : GemmTile::T128, /*acc*/ true});
   }
   HFG_HIP_CHECK(hipGetLastError());
 }
@@ -969,10 +952,10 @@ static void bt_wy_fold_x(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, 
     hipLaunchKernelGGL(k_transpose_batch, dim3((nmax + 63) / 64, (nmax + 63) / 64, nblk), dim3(256), 0, q, t);
     double *const *dptr = w.btptr.p;
     for (int g = 0; g < NP; g++) {
-      gemm_tasklist64_dev(ctx, w.btslabR.p + (size_t)g * BT_S * nblk, BT_S * nblk, BT_PW, nmax);
+      gemm_tasklist_dev(ctx, w.btslabR.p + (size_t)g * BT_S * nblk, BT_S * nblk, BT_PW, nmax, {GemmTile::T64});
       hipLaunchKernelGGL(k_bt_wpair, dim3((nmax + 4 * BT_WREP - 1) / (4 * BT_WREP), nblk), dim3(256), 0, q, b, dptr + 3 * nblk, dptr + 4 * nblk,
                          dptr + 5 * nblk, BT_S, BT_GS, NP, g, 1);
-      gemm_tasklist_acc_dev(ctx, w.btupdR.p + (size_t)g * nblk, nblk, nmax, nmax, true);
+      gemm_tasklist_dev(ctx, w.btupdR.p + (size_t)g * nblk, nblk, nmax, nmax, {GemmTile::T64, /*acc*/ true});
     }
   } catch (...) {
     ctx->stream = main;
@@ -1098,8 +1081,6 @@ static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, con
   HFG_HIP_CHECK(hipGetLastError());
 }
 
-bool tridiagonalize_takes_chain(int nblk, const int *ns);  // trdp.hip
-void trdp_check_status(hfg_ctx *ctx);        // trdp.hip
 static void check_status(hfg_ctx *ctx, EigWork &w, int nblk) {
   if (w.used_dc) {
     if (dc_status(ctx) != 0) throw std::logic_error("Eigendecomposition failed!\n");
@@ -1167,8 +1148,8 @@ size_t eig_block_buf_size(int nblk, const int64_t *blk_ptr) {
 // nF Fock matrices at once (the two spins of an unrestricted iteration): their blocks join ONE batch -- the
 // tridiagonalisation is a chain of dependent launches whose length does not depend on the number of blocks in it, so two
 // spins cost about what one costs
-void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
-                          const int64_t *blk_idx, double *const *dBlockBufs);
+static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
+                                 const int64_t *blk_idx, double *const *dBlockBufs);
 static int eig_num_cus(hfg_ctx *ctx) {
   static int ncu = 0;
   if (!ncu) {
@@ -1181,8 +1162,8 @@ void eig_blocks_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int
                     const int64_t *blk_idx, double *dBlockBuf) {
   eig_blocks_multi_dev(ctx, N, 1, &dF, dS, nblk, blk_ptr, blk_idx, &dBlockBuf);
 }
-void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
-                          const int64_t *blk_idx, double *const *dBlockBufs) {
+static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
+                                 const int64_t *blk_idx, double *const *dBlockBufs) {
   EigWork &w = work_for(ctx);
   hipStream_t s = ctx->stream;
   if (blk_ptr[nblk] != N) throw std::logic_error("Symmetry mismatch in eig_gsym_sub\n");
@@ -1313,30 +1294,26 @@ void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs,
       const int slots = 2 * eig_num_cus(ctx);
       const bool split_full = force_split >= 0 ? force_split != 0 : (full_tiles < slots && nm >= 256);
       const bool split_low = force_split >= 0 ? force_split != 0 : (low_tiles < slots && nm >= 256);
-      w.split_full = split_full;
       ProfScope pp3(ctx, "eig_products");  // the N^3 products alone (bench.py: MFMA fraction of the tile engine)
       // 64 x 64 tiles unless the batch's 128 x 128 tiles would fill whole rounds of the chip (gemm_prefers_128): 386 large
       // tiles on 512 slots ran at 34 TFLOP/s as two half-K workgroups each, 1452 small ones at 37 and without zeroing C.
       // HELFEM_GEMM_SPLITK=1 / HELFEM_GEMM_TILE=128 bring the large tiles back (checkers).
       const bool tile64 = force_split < 0 && !gemm_prefers_128(ctx, full_tiles);
-      w.tile64 = tile64;
-      if (tile64) {
-        gemm_tasklist64_dev(ctx, w.gtasks.p, nb, nm, nm);
-        gemm_tasklist64_dev(ctx, w.gtasks.p + nb, nb, nm, nm);
-        gemm_mirror_lower_dev(ctx, w.gtasks.p + nb, nb, nm);
-      } else {
-      if (split_full) {
-        for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(T1.p + (size_t)k * nmax * nmax, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
-        gemm_tasklist_split2_dev(ctx, w.gtasks.p, nb, nm, nm);
-      } else if (tuning().gemm_rect) gemm_tasklist_rect_dev(ctx, w.gtasks.p, nb, nm, nm);
-      else gemm_tasklist_dev(ctx, w.gtasks.p, nb, nm, nm);
-      if (split_low) {
-        for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(w.A[k].p, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
-        gemm_tasklist_split2_dev(ctx, w.gtasks.p + nb, nb, nm, nm);
-      } else
-        gemm_tasklist_dev(ctx, w.gtasks.p + nb, nb, nm, nm);      // lower tiles of X^T (F X) only (GemmTask::sym)
-      gemm_mirror_lower_dev(ctx, w.gtasks.p + nb, nb, nm);        // the tridiagonalisation sweeps the full square
+      GemmHow full, low;  // the full products F X and X Z; X^T (F X), of which only the lower tiles are formed (GemmTask::sym)
+      if (tile64) full.tile = low.tile = GemmTile::T64;
+      else {
+        if (split_full) full.tile = GemmTile::T128, full.split2 = true;
+        else if (tuning().gemm_rect) full.tile = GemmTile::T128x64;
+        if (split_low) low.tile = GemmTile::T128, low.split2 = true;
       }
+      w.full_how = full;
+      if (full.split2)
+        for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(T1.p + (size_t)k * nmax * nmax, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
+      gemm_tasklist_dev(ctx, w.gtasks.p, nb, nm, nm, full);
+      if (low.split2)
+        for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(w.A[k].p, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
+      gemm_tasklist_dev(ctx, w.gtasks.p + nb, nb, nm, nm, low);
+      gemm_mirror_lower_dev(ctx, w.gtasks.p + nb, nb, nm);  // the tridiagonalisation sweeps the full square
     }
     eig_sym_batch(ctx, w, nb, ns.data(), Xptr);
     {
@@ -1356,10 +1333,7 @@ void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs,
       {
         ProfScope pp3(ctx, "eig_products");
         const GemmTask *last = w.gtasks.p + (w.folded ? 3 : 2) * (size_t)nb;
-        if (w.tile64) gemm_tasklist64_dev(ctx, last, nb, nm, nm);
-        else if (w.split_full) gemm_tasklist_split2_dev(ctx, last, nb, nm, nm);  // the block slots were zeroed above
-        else if (tuning().gemm_rect) gemm_tasklist_rect_dev(ctx, last, nb, nm, nm);
-        else gemm_tasklist_dev(ctx, last, nb, nm, nm);
+        gemm_tasklist_dev(ctx, last, nb, nm, nm, w.full_how);  // (split2: the block slots were zeroed above)
       }
     }
     check_status(ctx, w, nb);

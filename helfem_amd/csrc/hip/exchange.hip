@@ -11,7 +11,7 @@
 // follows the reference: in-element blocks contract the primitive integrals (index-permuted reads
 // of prim_tei replace the reference's prim_ktei copies), cross-element blocks use the factorised
 // disjoint P/Q integrals.
-#include "tables.h"
+#include "internal.h"
 
 namespace hfg {
 
@@ -271,7 +271,6 @@ static ExAux &exaux_for(hfg_ctx *ctx, hfg_dev_tables *t) {
   return *a;
 }
 
-bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, double *dK, const double *Lknown, int rknown);
 
 // rs: the range-separated kernel of TwoDBasis::rs_exchange (src/atomic/TwoDBasis.cpp:1142) through basis->dev_rs
 void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, bool rs, const double *Lknown, int rknown) {

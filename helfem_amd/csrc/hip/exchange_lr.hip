@@ -18,20 +18,11 @@
 // matrices of an SCF run; signs s_o make rank-deficient indefinite inputs work too).  The factorisation is
 // verified (max |P - L S L^T|); if it does not reproduce P to 1e-13 within HFG_EXL_RMAX columns the caller falls
 // back to the general kernels of exchange.hip.  Same sums as the reference, different association order.
-#include "tables.h"
+#include "internal.h"
 #include <algorithm>
 #include <cstdlib>
 
 namespace hfg {
-
-void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda,
-              const double *B, int ldb, double beta, double *C, int ldc);
-void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_split2_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_wl_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, int nwg, int tiles);
-void gemm_tasklist_wl_split2_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, int nwg);
-void gemm_tasklist_split2_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
 
 constexpr int EXL_RMAX = 64;
 constexpr int EXL_QMAX = 16;  // rows per thread in the factorisation kernel: N <= 1024 * EXL_QMAX
@@ -1273,18 +1264,14 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
       if (tuning().exl_splitk && tiles < 2048 && ncol >= 512) {
         if (!grouped) HFG_HIP_CHECK(hipMemsetAsync(a.G.p, 0, sizeof(double) * ct.size() * Ap * Ap, s));
         // 128 x 64 tiles: the blocks of ~300 columns pad to 320 instead of 384 (11.6 -> 11.5 ms per build; HELFEM_EXL_CRECT=0: square)
-        if (tuning().exl_crect && grouped && tuning().exl_wl) {
+        const GemmTile tile = (tuning().exl_crect && grouped) ? GemmTile::T128x64 : GemmTile::T128;
+        if (tile == GemmTile::T128x64 && tuning().exl_wl) {
           // all tiles of a product on one XCD: its operand blocks are fetched once (2.4 GB were fetched for 0.3 GB of aP, aQw)
-          std::vector<int2> &wl = a.h_cwl;
-          wl.clear();
-          for (size_t k = 0; k < ct.size(); k++) {
-            const int nt = ((ct[k].M + 127) / 128) * ((ct[k].N + 63) / 64);
-            for (int q = 0; q < 2 * nt; q++) wl.push_back(make_int2((int)k, q));
-          }
-          a.cwl.upload(wl, s);
-          gemm_tasklist_wl_split2_rect_dev(ctx, a.ctasks.p, a.cwl.p, (int)wl.size());
-        } else if (tuning().exl_crect && grouped) gemm_tasklist_split2_rect_dev(ctx, a.ctasks.p, (int)ct.size(), maxMN, maxMN);
-        else gemm_tasklist_split2_dev(ctx, a.ctasks.p, (int)ct.size(), maxMN, maxMN);
+          gemm_worklist(ct, tile, true, a.h_cwl);
+          a.cwl.upload(a.h_cwl, s);
+          gemm_worklist_dev(ctx, a.ctasks.p, a.cwl.p, (int)a.h_cwl.size(), tile, true);
+        } else
+          gemm_tasklist_dev(ctx, a.ctasks.p, (int)ct.size(), maxMN, maxMN, {tile, /*acc*/ false, /*split2*/ true});
       } else
         gemm_tasklist_dev(ctx, a.ctasks.p, (int)ct.size(), maxMN, maxMN);
     }
@@ -1437,17 +1424,12 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
       // short pair lists: 64 x 64 tiles (three workgroups per CU; 5.71 against 6.08 ms with 128 x 64 at Nbf = 4230); long lists:
       // 128 x 128 (15.5 against 15.8 ms with 64 x 64 at Nbf = 6102).  HELFEM_EXL_RECT = 0 / 1 / 2 forces 128 x 128 / 128 x 64 / 64 x 64
       const int tile_mode = rect_env >= 0 ? rect_env : (rect_tiles ? 2 : 0);
-      const int BMt = tile_mode == 2 ? 64 : 128, BNt = tile_mode == 0 ? 128 : 64;
-      std::vector<int2> &wl = a.h_gwl;
-      wl.clear();
-      for (size_t k = 0; k < tasks.size(); k++) {
-        const int nt = ((tasks[k].M + BMt - 1) / BMt) * ((tasks[k].N + BNt - 1) / BNt);
-        for (int q = 0; q < nt; q++) wl.push_back(make_int2((int)k, q));
-      }
-      a.gwl.upload(wl, s);  // (h_gwl lives in the aux until the synchronisation at the end of the build)
-      gemm_tasklist_wl_dev(ctx, a.tasks.p, a.gwl.p, (int)wl.size(), tile_mode);
-    } else if (rect_tiles) gemm_tasklist_rect_dev(ctx, a.tasks.p, (int)tasks.size(), pp, maxN);
-    else gemm_tasklist_dev(ctx, a.tasks.p, (int)tasks.size(), pp, maxN);
+      const GemmTile tile = tile_mode == 2 ? GemmTile::T64 : tile_mode == 1 ? GemmTile::T128x64 : GemmTile::T128;
+      gemm_worklist(tasks, tile, false, a.h_gwl);
+      a.gwl.upload(a.h_gwl, s);  // (h_gwl lives in the aux until the synchronisation at the end of the build)
+      gemm_worklist_dev(ctx, a.tasks.p, a.gwl.p, (int)a.h_gwl.size(), tile);
+    } else
+      gemm_tasklist_dev(ctx, a.tasks.p, (int)tasks.size(), pp, maxN, {rect_tiles ? GemmTile::T128x64 : GemmTile::Auto});
   }
   if (pair)
     hipLaunchKernelGGL(k_exl_reduce_pair, dim3(A * A, E * (E + 1) / 2), dim3(256), 0, s, a.C.p, a.c_off.p, a.S_off.p, a.pos.p,

@@ -18,7 +18,7 @@
 //    sums, different association order; ~2000x fewer flops, no O(Ng * ne) intermediates.
 //  * No atomics anywhere: every output element has exactly one writer and a fixed summation order,
 //    so results are bitwise reproducible run to run.
-#include "tables.h"
+#include "internal.h"
 #include "xc_device.h"
 #include "../host/dftfuncs.h"
 #include <cstring>
@@ -1225,13 +1225,13 @@ static hfg_dev_tables *tables_of(hfg_ctx *ctx, hfg_basis *basis) {
   return basis->dev;
 }
 
-void gather_compact(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dPc) {
+static void gather_compact(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dPc) {
   hfg_dev_tables *t = basis->dev;
   hipLaunchKernelGGL(k_gather_compact, dim3(t->A * t->A * t->E), dim3(256), 0, ctx->stream, dP, t->N, t->A, t->R, t->E,
                      t->p, t->shell_off.p, t->shell_skip.p, dPc);
 }
 
-void scatter_dense(hfg_ctx *ctx, hfg_basis *basis, const double *dXc, double *dOut) {
+static void scatter_dense(hfg_ctx *ctx, hfg_basis *basis, const double *dXc, double *dOut) {
   hfg_dev_tables *t = basis->dev;
   FockAux &a = aux_for(ctx, basis);
   dim3 grid((t->N + 63) / 64, (t->N + 3) / 4);
@@ -1240,7 +1240,7 @@ void scatter_dense(hfg_ctx *ctx, hfg_basis *basis, const double *dXc, double *dO
 }
 
 // J (compact) from P (compact)
-void coulomb_compact(hfg_ctx *ctx, hfg_basis *basis, const double *dPc, double *dJc) {
+static void coulomb_compact(hfg_ctx *ctx, hfg_basis *basis, const double *dPc, double *dJc) {
   hfg_dev_tables *t = tables_of(ctx, basis);
   FockAux &a = aux_for(ctx, basis);
   const int pp = t->p * t->p;
@@ -1364,8 +1364,8 @@ static void launch_xc_grid(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, co
                      pl.do_tau, pl.do_lapl, pl.thr, pl.NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, tail...);
 }
 
-void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPc, double *dHc, double *dScal,
-                double thr) {
+static void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPc, double *dHc, double *dScal,
+                       double thr) {
   hfg_dev_tables *t = tables_of(ctx, basis);
   const XCPlan pl = xc_plan(t, x_func, c_func, thr);
   FockAux &a = aux_for(ctx, basis);
@@ -1507,8 +1507,8 @@ void xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const d
 }
 
 // spin-polarised XC: Hc_a, Hc_b (compact) from Pc_a, Pc_b (compact); dScal = (Exc, Nel, 0)
-void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPca, const double *dPcb,
-                    double *dHca, double *dHcb, double *dScal, double thr) {
+static void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPca, const double *dPcb,
+                           double *dHca, double *dHcb, double *dScal, double thr) {
   hfg_dev_tables *t = tables_of(ctx, basis);
   const XCPlan pl = xc_plan(t, x_func, c_func, thr);
   FockAux &a = aux_for(ctx, basis);

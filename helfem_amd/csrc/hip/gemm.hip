@@ -30,7 +30,7 @@
 // chosen by the launcher so that small problems still give >= 256 workgroups), BK = 16.
 // LDS tiles are stored [k][m] with the row padded by 16 doubles: the four k-rows a wave reads at
 // once then fall on disjoint 128-B bank groups (conflict-free ds_read_b64).
-#include "common.h"
+#include "internal.h"
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -441,25 +441,6 @@ __global__ __launch_bounds__(256, 2) void k_dgemm_tasklist_split2(const GemmTask
   dgemm_tile<BM, BN, false, 1>(tile, t.tA, t.tB, t.M, t.N, t.K, t.alpha, t.A, t.lda, t.B, t.ldb, 0.0, t.C, t.ldc, As, Bs, sym, kbeg, kend);
 }
 
-/// HELFEM_MFMA=4x4x4 selects the v_mfma_f64_4x4x4_4b_f64 form of the tile engine (A/B runs; same speed, more LDS reads)
-static bool mfma4() { return tuning().mfma_4x4x4; }
-
-/// task lists whose products accumulate into C (beta != 0 in every active task): streaming epilogue
-void gemm_tasklist_acc_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, bool tile64) {
-  if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
-  ProfScope ps(ctx, "gemm");
-  if (tile64) {
-    const int tiles = ((maxM + 63) / 64) * ((maxN + 63) / 64);
-    if (mfma4()) hipLaunchKernelGGL((k_dgemm_tasklist<64, 64, true, 0>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
-    else hipLaunchKernelGGL((k_dgemm_tasklist<64, 64, true>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
-  } else {
-    const int tiles = ((maxM + 127) / 128) * ((maxN + 127) / 128);
-    if (mfma4()) hipLaunchKernelGGL((k_dgemm_tasklist<128, 128, true, 0>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
-    else hipLaunchKernelGGL((k_dgemm_tasklist<128, 128, true>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
-  }
-  HFG_HIP_CHECK(hipGetLastError());
-}
-
 // upper triangle := transpose of the lower one for the symmetric products of a task list (sym tasks only): 64 x 64
 // blocks through LDS, coalesced on both sides
 __global__ __launch_bounds__(256) void k_mirror_lower(const GemmTask *__restrict__ tasks) {
@@ -494,92 +475,91 @@ void gemm_mirror_lower_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int
   HFG_HIP_CHECK(hipGetLastError());
 }
 
-/// launches the task list with 64 x 64 tiles (small products, more workgroups)
-void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN) {
-  if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
-  ProfScope ps(ctx, "gemm");
-  const int tiles = ((maxM + 63) / 64) * ((maxN + 63) / 64);
-  for (int t0 = 0; t0 < ntasks; t0 += 65535) {  // (the grid's second dimension ends at 65535)
-    const int nt = std::min(65535, ntasks - t0);
-    if (mfma4()) hipLaunchKernelGGL((k_dgemm_tasklist<64, 64, false, 0>), dim3(tiles, nt), dim3(256), 0, ctx->stream, dtasks + t0);
-    else hipLaunchKernelGGL((k_dgemm_tasklist<64, 64>), dim3(tiles, nt), dim3(256), 0, ctx->stream, dtasks + t0);
+/// HELFEM_MFMA=4x4x4 selects the v_mfma_f64_4x4x4_4b_f64 form of the tile engine (A/B runs; same speed, more LDS reads):
+/// honoured by gemm_dev and by the plain, accumulating and column-map task lists
+static bool mfma4() { return tuning().mfma_4x4x4; }
+
+namespace {
+struct TileShape {
+  int bm, bn;
+};
+TileShape tile_shape(GemmTile tile) {
+  switch (tile) {
+    case GemmTile::T64: return {64, 64};
+    case GemmTile::T128: return {128, 128};
+    case GemmTile::T128x64: return {128, 64};
+    default: throw std::logic_error("GEMM tile engine: GemmTile::Auto names no tile shape");
   }
-  HFG_HIP_CHECK(hipGetLastError());
+}
+int tile_count(TileShape s, int M, int N) { return ((M + s.bm - 1) / s.bm) * ((N + s.bn - 1) / s.bn); }
+const char *tile_name(GemmTile tile) {
+  const char *names[] = {"Auto", "T64", "T128", "T128x64"};
+  return (unsigned)tile < 4u ? names[(int)tile] : "(unknown)";
 }
 
-/// the same for tasks with column maps (GemmTask::amap and cmap set in every active task)
-void gemm_tasklist64_map_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN) {
+// the kernel of a task list: every legal combination maps to one instantiation, anything else is refused
+typedef void (*TaskKernel)(const GemmTask *);
+constexpr int ACC = 1, SPLIT2 = 2, MAP = 4;
+constexpr int variant(GemmTile tile, int flags) { return 8 * (int)tile + flags; }
+TaskKernel tasklist_kernel(GemmTile tile, const GemmHow &how) {
+  const bool m4 = mfma4();
+  switch (variant(tile, how.acc * ACC + how.split2 * SPLIT2 + how.map * MAP)) {
+    case variant(GemmTile::T64, 0): return m4 ? k_dgemm_tasklist<64, 64, false, 0> : k_dgemm_tasklist<64, 64>;
+    case variant(GemmTile::T128, 0): return m4 ? k_dgemm_tasklist<128, 128, false, 0> : k_dgemm_tasklist<128, 128>;
+    case variant(GemmTile::T128x64, 0): return k_dgemm_tasklist<128, 64>;
+    case variant(GemmTile::T64, ACC): return m4 ? k_dgemm_tasklist<64, 64, true, 0> : k_dgemm_tasklist<64, 64, true>;
+    case variant(GemmTile::T128, ACC): return m4 ? k_dgemm_tasklist<128, 128, true, 0> : k_dgemm_tasklist<128, 128, true>;
+    case variant(GemmTile::T64, MAP): return m4 ? k_dgemm_tasklist_map<0> : k_dgemm_tasklist_map<1>;
+    case variant(GemmTile::T128, SPLIT2): return k_dgemm_tasklist_split2<128, 128>;
+    case variant(GemmTile::T128x64, SPLIT2): return k_dgemm_tasklist_split2<128, 64>;
+    default:
+      throw std::logic_error(std::string("gemm_tasklist_dev: no kernel for tile ") + tile_name(tile) + (how.acc ? " acc" : "") +
+                             (how.split2 ? " split2" : "") + (how.map ? " map" : ""));
+  }
+}
+}  // namespace
+
+/// Launches the task list: grid (tiles of a maxM x maxN product, tasks).  GemmHow (internal.h) says which tiles and which
+/// variant of the engine: acc -- streaming epilogue, beta != 0 in every active task; split2 -- two workgroups per tile, each
+/// half of K, beta == 0 tasks whose outputs the caller has ZEROED; map -- GemmTask::amap and cmap set in every active task
+void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, GemmHow how) {
   if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
+  GemmTile tile = how.tile;
+  if (tile == GemmTile::Auto)  // (an upper bound of the tile count: tasks may be smaller)
+    tile = (ntasks <= 65535 && !gemm_prefers_128(ctx, (long)ntasks * tile_count({128, 128}, maxM, maxN))) ? GemmTile::T64 : GemmTile::T128;
+  const TaskKernel kernel = tasklist_kernel(tile, how);
+  const int tiles = tile_count(tile_shape(tile), maxM, maxN) * (how.split2 ? 2 : 1);
   ProfScope ps(ctx, "gemm");
-  const int tiles = ((maxM + 63) / 64) * ((maxN + 63) / 64);
-  if (mfma4()) hipLaunchKernelGGL((k_dgemm_tasklist_map<0>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
-  else hipLaunchKernelGGL((k_dgemm_tasklist_map<1>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
+  for (int t0 = 0; t0 < ntasks; t0 += 65535)  // (the grid's second dimension ends at 65535)
+    hipLaunchKernelGGL(kernel, dim3(tiles, std::min(65535, ntasks - t0)), dim3(256), 0, ctx->stream, dtasks + t0);
   HFG_HIP_CHECK(hipGetLastError());
 }
 
-/// launches the task list with 128 x 128 tiles; max_mn = largest (M, N) over the tasks
-/// the same with 128 x 64 tiles (no symmetric tasks): twice as many, half as large workgroups -- for batches whose
-/// 128 x 128 tiles do not divide evenly over the CUs
-void gemm_tasklist_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN) {
-  if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
-  ProfScope ps(ctx, "gemm");
-  const int tiles = ((maxM + 127) / 128) * ((maxN + 63) / 64);
-  hipLaunchKernelGGL((k_dgemm_tasklist<128, 64>), dim3(tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
-  HFG_HIP_CHECK(hipGetLastError());
+/// The work list of gemm_worklist_dev: (task, tile), or for split K (task, 2 tile + half), for every tile of every
+/// non-empty task, in task order
+void gemm_worklist(const std::vector<GemmTask> &tasks, GemmTile tile, bool split2, std::vector<int2> &out) {
+  const TileShape shape = tile_shape(tile);
+  out.clear();
+  for (size_t t = 0; t < tasks.size(); t++) {
+    if (tasks[t].M <= 0 || tasks[t].N <= 0) continue;
+    const int n = tile_count(shape, tasks[t].M, tasks[t].N) * (split2 ? 2 : 1);
+    for (int q = 0; q < n; q++) out.push_back(make_int2((int)t, q));
+  }
 }
 
-/// C = A B for task lists with beta == 0 whose outputs the caller has ZEROED: two workgroups per 128 x 128 tile
-void gemm_tasklist_split2_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN) {
-  if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
-  ProfScope ps(ctx, "gemm");
-  const int tiles = ((maxM + 127) / 128) * ((maxN + 127) / 128);
-  hipLaunchKernelGGL((k_dgemm_tasklist_split2<128, 128>), dim3(2 * tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
-  HFG_HIP_CHECK(hipGetLastError());
-}
-
-/// task list with a workgroup list (task, tile) in XCD order; rect: 128 x 64 tiles, else 128 x 128 (beta == 0 tasks, no sym)
-/// tiles: 0 = 128 x 128, 1 = 128 x 64, 2 = 64 x 64 (the work list must have been enumerated with the same tile shape)
-void gemm_tasklist_wl_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, int nwg, int tiles) {
+/// Task list with a workgroup list in XCD order (gemm_worklist with the same tile and split2; beta == 0 tasks, no sym).
+/// split2 (128 x 64 tiles only): two list entries per tile, C zeroed by the caller
+void gemm_worklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, int nwg, GemmTile tile, bool split2) {
+  void (*kernel)(const GemmTask *, const int2 *, int) = nullptr;
+  if (split2) {
+    if (tile == GemmTile::T128x64) kernel = k_dgemm_tasklist_wl<128, 64, true>;
+  } else if (tile == GemmTile::T128) kernel = k_dgemm_tasklist_wl<128, 128>;
+  else if (tile == GemmTile::T128x64) kernel = k_dgemm_tasklist_wl<128, 64>;
+  else if (tile == GemmTile::T64) kernel = k_dgemm_tasklist_wl<64, 64>;
+  if (!kernel) throw std::logic_error(std::string("gemm_worklist_dev: no kernel for tile ") + tile_name(tile) + (split2 ? " split2" : ""));
   if (nwg <= 0) return;
   ProfScope ps(ctx, "gemm");
-  const unsigned grid = 8u * (unsigned)((nwg + 7) / 8);
-  if (tiles == 2) hipLaunchKernelGGL((k_dgemm_tasklist_wl<64, 64>), dim3(grid), dim3(256), 0, ctx->stream, dtasks, dwl, nwg);
-  else if (tiles == 1) hipLaunchKernelGGL((k_dgemm_tasklist_wl<128, 64>), dim3(grid), dim3(256), 0, ctx->stream, dtasks, dwl, nwg);
-  else hipLaunchKernelGGL((k_dgemm_tasklist_wl<128, 128>), dim3(grid), dim3(256), 0, ctx->stream, dtasks, dwl, nwg);
-  HFG_HIP_CHECK(hipGetLastError());
-}
-
-/// split-K form of the above with 128 x 64 tiles: two list entries per tile, C zeroed by the caller
-void gemm_tasklist_wl_split2_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, int nwg) {
-  if (nwg <= 0) return;
-  ProfScope ps(ctx, "gemm");
-  hipLaunchKernelGGL((k_dgemm_tasklist_wl<128, 64, true>), dim3(8u * (unsigned)((nwg + 7) / 8)), dim3(256), 0, ctx->stream, dtasks, dwl, nwg);
-  HFG_HIP_CHECK(hipGetLastError());
-}
-
-/// the same with 128 x 64 tiles
-void gemm_tasklist_split2_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN) {
-  if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
-  ProfScope ps(ctx, "gemm");
-  const int tiles = ((maxM + 127) / 128) * ((maxN + 63) / 64);
-  hipLaunchKernelGGL((k_dgemm_tasklist_split2<128, 64>), dim3(2 * tiles, ntasks), dim3(256), 0, ctx->stream, dtasks);
-  HFG_HIP_CHECK(hipGetLastError());
-}
-
-bool gemm_prefers_128(hfg_ctx *ctx, long tiles128);
-void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN) {
-  if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
-  const int tiles = ((maxM + 127) / 128) * ((maxN + 127) / 128);
-  if (ntasks <= 65535 && !gemm_prefers_128(ctx, (long)ntasks * tiles)) {  // (an upper bound of the tile count: tasks may be smaller)
-    gemm_tasklist64_dev(ctx, dtasks, ntasks, maxM, maxN);
-    return;
-  }
-  ProfScope ps(ctx, "gemm");
-  for (int t0 = 0; t0 < ntasks; t0 += 65535) {
-    int nt = std::min(65535, ntasks - t0);
-    if (mfma4()) hipLaunchKernelGGL((k_dgemm_tasklist<128, 128, false, 0>), dim3(tiles, nt), dim3(256), 0, ctx->stream, dtasks + t0);
-    else hipLaunchKernelGGL((k_dgemm_tasklist<128, 128>), dim3(tiles, nt), dim3(256), 0, ctx->stream, dtasks + t0);
-  }
+  hipLaunchKernelGGL(kernel, dim3(8u * (unsigned)((nwg + 7) / 8)), dim3(256), 0, ctx->stream, dtasks, dwl, nwg);
   HFG_HIP_CHECK(hipGetLastError());
 }
 
@@ -604,23 +584,12 @@ void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha,
               const double *B, int ldb, double beta, double *C, int ldc) {
   if (M <= 0 || N <= 0) return;
   ProfScope ps(ctx, "gemm");
-  long big_tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
-  if (gemm_prefers_128(ctx, big_tiles)) {
-    if (mfma4())
-      hipLaunchKernelGGL((k_dgemm<128, 128, 0>), dim3((unsigned)big_tiles), dim3(256), 0, ctx->stream, (int)tA, (int)tB, M, N, K,
-                         alpha, A, lda, B, ldb, beta, C, ldc);
-    else
-      hipLaunchKernelGGL((k_dgemm<128, 128>), dim3((unsigned)big_tiles), dim3(256), 0, ctx->stream, (int)tA, (int)tB, M, N, K,
-                         alpha, A, lda, B, ldb, beta, C, ldc);
-  } else {
-    long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
-    if (mfma4())
-      hipLaunchKernelGGL((k_dgemm<64, 64, 0>), dim3((unsigned)tiles), dim3(256), 0, ctx->stream, (int)tA, (int)tB, M, N, K, alpha, A,
-                         lda, B, ldb, beta, C, ldc);
-    else
-      hipLaunchKernelGGL((k_dgemm<64, 64>), dim3((unsigned)tiles), dim3(256), 0, ctx->stream, (int)tA, (int)tB, M, N, K, alpha, A,
-                         lda, B, ldb, beta, C, ldc);
-  }
+  const long big_tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
+  const bool big = gemm_prefers_128(ctx, big_tiles), m4 = mfma4();
+  const long tiles = big ? big_tiles : (long)((M + 63) / 64) * ((N + 63) / 64);
+  const auto kernel = big ? (m4 ? k_dgemm<128, 128, 0> : k_dgemm<128, 128>) : (m4 ? k_dgemm<64, 64, 0> : k_dgemm<64, 64>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, (int)tA, (int)tB, M, N, K, alpha, A, lda, B, ldb, beta, C,
+                     ldc);
   HFG_HIP_CHECK(hipGetLastError());
 }
 

@@ -1,0 +1,110 @@
+// Every hfg:: function that is defined in one translation unit of csrc/hip/ and called from another (or from a probe
+// under tests/gpu_probe/), declared once, grouped by the file that defines it.  Default arguments live here and nowhere
+// else.  The defining file includes this header too, so a definition that drifts from its declaration shows up as an
+// ambiguous call or a missing-prototype warning (tests/test_internal_header_cpu.py).  Not a public header: the C ABI is
+// include/helfem_gpu.h.  (set_error is declared in common.h; upload_tables and upload_rs_tables in tables.h.)
+#pragma once
+#include "common.h"
+#include "tables.h"
+#include "../host/scf.h"
+
+namespace hfg {
+
+// gemm.hip: the FP64 tile engine.  One launcher for task lists, one for task lists with a work list.
+enum class GemmTile { Auto, T64, T128, T128x64 };  // Auto: gemm_prefers_128() picks T64 or T128 (T64 only up to 65535 tasks)
+struct GemmHow {
+  GemmTile tile = GemmTile::Auto;
+  bool acc = false, split2 = false, map = false;
+};
+// kernel by (tile, variant); HELFEM_MFMA=4x4x4 reaches the plain, acc and map lists and gemm_dev:
+//   {} / {T64} / {T128}           k_dgemm_tasklist<64, 64> or <128, 128>
+//   {T128x64}                     k_dgemm_tasklist<128, 64>
+//   {T64 or T128, acc}            k_dgemm_tasklist<.., true>      C = alpha A B + beta C, beta != 0 in every active task
+//   {T64, map}                    k_dgemm_tasklist_map            GemmTask::amap and cmap set in every active task
+//   {T128 or T128x64, split2}     k_dgemm_tasklist_split2<..>     beta == 0 tasks, C zeroed by the caller
+// anything else throws std::logic_error
+void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, GemmHow how = {});  // gemm.hip
+// k_dgemm_tasklist_wl<tile>; T64, T128 or T128x64, split2 with T128x64 only
+void gemm_worklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, int nwg, GemmTile tile, bool split2 = false);  // gemm.hip
+// host: (task, tile) or, split2, (task, 2 tile + half) for every tile of every non-empty task, in task order
+void gemm_worklist(const std::vector<GemmTask> &tasks, GemmTile tile, bool split2, std::vector<int2> &out);  // gemm.hip
+void gemm_mirror_lower_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxN);  // gemm.hip
+bool gemm_prefers_128(hfg_ctx *ctx, long tiles128);  // gemm.hip
+void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda, const double *B, int ldb,
+              double beta, double *C, int ldc);  // gemm.hip
+
+// fock.hip
+void coulomb_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dJ);  // fock.hip
+void set_xc_params(hfg_ctx *ctx, int x_func, const double *x_pars, int nx, int c_func, const double *c_pars, int nc);  // fock.hip
+void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double *sigma, const double *lapl, const double *tau,
+                  double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau, double thr);  // fock.hip
+void xc_eval_host_ext(int id, const double *pars, int npars, int nspin, size_t np, const double *rho, const double *sigma,
+                      const double *lapl, const double *tau, double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau,
+                      double thr);  // fock.hip
+void xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dH, double *dScal,
+                 double thr);  // fock.hip
+void xc_fock_pol_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPa, const double *dPb, double *dHa,
+                     double *dHb, double *dScal, double thr);  // fock.hip
+void model_potential_dev(hfg_ctx *ctx, hfg_basis *basis, int kind1, int Z1, double d1, double H1, int kind2, int Z2, double d2,
+                         double H2, double *dH);  // fock.hip
+size_t fock_compact_size(hfg_basis *basis);  // fock.hip
+void fock_compact_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dFc, double *dScal,
+                      double thr);  // fock.hip
+void fock_finish_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const double *dH0, const int *dBlockId,
+                     double *dF);  // fock.hip
+void fock_release(hfg_dev_tables *t);  // fock.hip
+
+// exchange.hip, exchange_lr.hip
+void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, bool rs = false, const double *Lknown = nullptr,
+                  int rknown = 0);  // exchange.hip
+void exchange_release(hfg_dev_tables *t);  // exchange.hip
+bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, double *dK, const double *Lknown,
+                          int rknown);  // exchange_lr.hip
+void exchange_lr_release(hfg_dev_tables *t);  // exchange_lr.hip
+
+// tei_dev.hip
+void compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis);  // tei_dev.hip
+
+// eig.hip
+void eig_sym_dev(hfg_ctx *ctx, int n, const double *dA, double *dE, double *dC);  // eig.hip
+void eig_gsym_dev(hfg_ctx *ctx, int N, int n, const double *dF, const double *dS, double *dE, double *dC);  // eig.hip
+void eig_gsym_sub_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
+                      const int64_t *blk_idx, double *dE, double *dC);  // eig.hip
+void eig_gsym_sub_pair_dev(hfg_ctx *ctx, int N, const double *dFa, const double *dFb, const double *dS, int nblk,
+                           const int64_t *blk_ptr, const int64_t *blk_idx, double *dEa, double *dCa, double *dEb,
+                           double *dCb);  // eig.hip
+size_t eig_block_buf_size(int nblk, const int64_t *blk_ptr);  // eig.hip
+void eig_blocks_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
+                    const int64_t *blk_idx, double *dBlockBuf);  // eig.hip
+void eig_assemble_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx, const double *dBlockBuf,
+                      double *dE, double *dC);  // eig.hip
+void eig_block_supports(hfg_ctx *ctx, int N, const double *dS, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
+                        std::vector<int64_t> &cols);  // eig.hip
+void eig_release(hfg_ctx *ctx);  // eig.hip
+
+// dc.hip, trd.hip, trdp.hip: the stages of the eigensolver
+void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, double *const *e, double *const *Z);  // dc.hip
+int dc_status(hfg_ctx *ctx);  // dc.hip
+void dc_release(hfg_ctx *ctx);  // dc.hip
+void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *A, double *const *d, double *const *e,
+                          double *const *tau);  // trd.hip
+void trd_measure_gemv(hfg_ctx *ctx, double *ms, int64_t *launches);  // trd.hip
+void trd_release(hfg_ctx *ctx);  // trd.hip
+bool tridiagonalize_takes_chain(int nblk, const int *ns);  // trdp.hip
+void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *const *A, double *const *d, double *const *e,
+                               double *const *tau, std::vector<char> &done);  // trdp.hip
+void trdp_check_status(hfg_ctx *ctx);  // trdp.hip
+void trdp_release(hfg_ctx *ctx);  // trdp.hip
+
+// misc.hip
+void form_sinvh_dev(hfg_ctx *ctx, int N, const double *dS, bool chol, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
+                    double *dSinvh);  // misc.hip
+void form_density_dev(hfg_ctx *ctx, int N, int ncols, const double *dC, int nocc, double *dP);  // misc.hip
+
+// scf_device.hip
+helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::scf::Options &opt, int nel, double Enucr, int symm,
+                                    const std::vector<std::vector<size_t> > &dsym, int ldft, int mdft,
+                                    const std::vector<std::vector<std::vector<size_t> > > &avg_idx =
+                                        std::vector<std::vector<std::vector<size_t> > >());  // scf_device.hip
+
+}  // namespace hfg

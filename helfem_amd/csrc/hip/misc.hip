@@ -1,14 +1,10 @@
 // Small helpers around the eigensolver: S^{-1/2} per symmetry block (reference utils::invh,
 // libhelfem/src/utils.cpp:160-183 and TwoDBasis::Sinvh, src/diatomic/basis.cpp:627-652) and
 // scf::form_density (src/general/scf_helpers.cpp:22-29).
-#include "common.h"
+#include "internal.h"
 #include <algorithm>
 
 namespace hfg {
-
-void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda,
-              const double *B, int ldb, double beta, double *C, int ldc);
-void eig_sym_dev(hfg_ctx *ctx, int n, const double *dA, double *dE, double *dC);
 
 // Sn(i,j) = S(rows[i],rows[j]) / sqrt(S_ii S_jj)
 __global__ void k_gather_normalized(const double *__restrict__ S, int N, const int64_t *__restrict__ rows, int n,

@@ -4,7 +4,7 @@
 // scalars (energies, the DIIS error norm and the small B matrix) cross PCIe per iteration.  The host-pointer
 // driver (host/scf.cpp with GPUBackend, scf_gpu.cpp) computes the same numbers and is kept as the checker of
 // this one (HELFEM_SCF=host).
-#include "tables.h"
+#include "internal.h"
 #include "wave.h"
 #include "../host/dftfuncs.h"
 #include "../host/diis.h"
@@ -17,36 +17,6 @@
 #include <memory>
 
 namespace hfg {
-
-void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda,
-              const double *B, int ldb, double beta, double *C, int ldc);
-void coulomb_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dJ);
-void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, bool rs = false, const double *Lknown = nullptr,
-                  int rknown = 0);
-void xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dH, double *dScal,
-                 double thr);
-void xc_fock_pol_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPa, const double *dPb,
-                     double *dHa, double *dHb, double *dScal, double thr);
-void form_sinvh_dev(hfg_ctx *ctx, int N, const double *dS, bool chol, int nblk, const int64_t *blk_ptr,
-                    const int64_t *blk_idx, double *dSinvh);
-void form_density_dev(hfg_ctx *ctx, int N, int ncols, const double *dC, int nocc, double *dP);
-void eig_sym_dev(hfg_ctx *ctx, int n, const double *dA, double *dE, double *dC);
-void eig_block_supports(hfg_ctx *ctx, int N, const double *dS, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
-                        std::vector<int64_t> &cols);
-void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void eig_gsym_sub_pair_dev(hfg_ctx *ctx, int N, const double *dFa, const double *dFb, const double *dS, int nblk, const int64_t *blk_ptr,
-                           const int64_t *blk_idx, double *dEa, double *dCa, double *dEb, double *dCb);
-void eig_gsym_sub_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
-                      const int64_t *blk_idx, double *dE, double *dC);
-void upload_tables(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft);
-void upload_rs_tables(hfg_ctx *ctx, hfg_basis *basis);
-void model_potential_dev(hfg_ctx *ctx, hfg_basis *basis, int kind1, int Z1, double d1, double H1, int kind2, int Z2,
-                         double d2, double H2, double *dH);
-void compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis);
-void fock_release(hfg_dev_tables *t);
-void exchange_release(hfg_dev_tables *t);
-void exchange_lr_release(hfg_dev_tables *t);
 
 namespace {
 
@@ -436,8 +406,8 @@ struct DevSCF {
     t.insert(t.end(), t3.begin(), t3.end());
     be.tasks.upload(t, s);
     HFG_HIP_CHECK(hipStreamSynchronize(s));  // t lives on this stack frame
-    gemm_tasklist64_dev(ctx, be.tasks.p, (int)t1.size(), be.nmax, kmax);
-    gemm_tasklist64_dev(ctx, be.tasks.p + t1.size(), (int)t2.size(), be.nmax, kmax);
+    gemm_tasklist_dev(ctx, be.tasks.p, (int)t1.size(), be.nmax, kmax, {GemmTile::T64});
+    gemm_tasklist_dev(ctx, be.tasks.p + t1.size(), (int)t2.size(), be.nmax, kmax, {GemmTile::T64});
     gemm_tasklist_dev(ctx, be.tasks.p + t1.size() + t2.size(), (int)t3.size(), be.nmax, be.nmax);
   }
 };

@@ -1,6 +1,6 @@
 // GPU backend of the SCF driver (host/scf.h): every per-iteration operation goes through the
 // C ABI entry points of include/helfem_gpu.h, exactly as an Armadillo-based caller would.
-#include "common.h"
+#include "internal.h"
 #include "../host/dftfuncs.h"
 #include "../host/checkpoint.h"
 #include "../host/scf.h"
@@ -112,14 +112,6 @@ struct GPUBackend : public helfem::scf::Backend {
   }
 };
 }  // namespace
-
-namespace hfg {
-void set_xc_params(hfg_ctx *ctx, int x_func, const double *x_pars, int nx, int c_func, const double *c_pars, int nc);  // fock.hip
-helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::scf::Options &opt, int nel, double Enucr,
-                                    int symm, const std::vector<std::vector<size_t> > &dsym, int ldft, int mdft,
-                                    const std::vector<std::vector<std::vector<size_t> > > &avg_idx =
-                                        std::vector<std::vector<std::vector<size_t> > >());
-}
 
 namespace {
 thread_local int g_readocc = 0;  // --readocc of the following hfg_scf_diatomic / hfg_scf_atomic calls (hfg_scf_set_occupations)
@@ -444,8 +436,8 @@ int hfg_scf_options_default(hfg_scf_options *o, int program) {
 
 namespace hfg {
 // what the reference's drivers leave in their checkpoint (diatomic/main.cpp:236-537, 790-963), in its HDF5 layout
-void write_checkpoint(const hfg_scf_options &p, const helfem::scf::Options &o, const helfem::scf::Result &r,
-                      const helfem::scf::AtomicOptions *a = nullptr, bool extended = false) {
+static void write_checkpoint(const hfg_scf_options &p, const helfem::scf::Options &o, const helfem::scf::Result &r,
+                             const helfem::scf::AtomicOptions *a = nullptr, bool extended = false) {
   helfem::Checkpoint chk(p.save, true);
   chk.write("nela", r.nela);
   chk.write("nelb", r.nelb);

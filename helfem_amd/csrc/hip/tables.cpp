@@ -1,4 +1,4 @@
-#include "tables.h"
+#include "internal.h"
 #include <algorithm>
 #include <cmath>
 #include <functional>

@@ -9,12 +9,10 @@
 //   W_kl[ilm] = (bb0 diag(wQ_k[ilm])) inner_l[ilm]^T                               (p^2 x p^2, FP64 MFMA task list)
 //   tei_kl = W_kl + W_lk^T   written straight into the padded device layout of hip/tables.h
 // so the 1 GB of tables never exists on the host and never crosses PCIe.
-#include "tables.h"
+#include "internal.h"
 #include <vector>
 
 namespace hfg {
-
-void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
 
 // inner[(l*Nlm + ilm)][isub][(ij)]: one workgroup per (ilm, l); thread = (ij)
 __global__ __launch_bounds__(256) void k_tei_inner(const double *__restrict__ bbs, const double *__restrict__ wP, int Np,
@@ -129,7 +127,7 @@ void compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis) {
         }
     d_tasks.upload(tasks, s);
     HFG_HIP_CHECK(hipStreamSynchronize(s));  // host vectors of this element live on this stack frame
-    gemm_tasklist64_dev(ctx, d_tasks.p, nty * nty * Nlm, Np, Np);
+    gemm_tasklist_dev(ctx, d_tasks.p, nty * nty * Nlm, Np, Np, {GemmTile::T64});
     // diatomic elements hold their primitives from index 0 (the last one has p-1 of them); the first atomic element has
     // lost its first primitive (hip/tables.cpp: lo)
     const int lo = (atomic && e == 0) ? 1 : 0;

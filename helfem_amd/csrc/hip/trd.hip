@@ -15,7 +15,7 @@
 //                                          and the next column A(:,i+1) - V W(i+1,:)^T - W V(i+1,:)^T
 //                                          together with the partial norms its Householder vector needs.
 // No atomics; all reductions have a fixed order, so the factorisation is bitwise reproducible.
-#include "common.h"
+#include "internal.h"
 #include "wave.h"
 #include <cstdio>
 #include <vector>
@@ -23,14 +23,6 @@
 #include <cstring>
 
 namespace hfg {
-
-void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda,
-              const double *B, int ldb, double beta, double *C, int ldc);
-void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_acc_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, bool tile64);
-void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *const *A, double *const *d, double *const *e,
-                               double *const *tau, std::vector<char> &done);  // trdp.hip
 
 constexpr int TB_MAXB = 8;
 constexpr int TB_NB = 16;   // panel width (measured: 16 beats 8 and 32 at n ~ 1400 x 3 blocks; 32 again after the DPP work: 11.7 vs 7.6 us per column)
@@ -1351,7 +1343,7 @@ void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *
       const int mt = nmax - j0 - TB_NB;
       if (mt > 0) {
         const GemmTask *pt = w.ptasks.p + (size_t)(j0 / TB_NB) * nblk;
-        gemm_tasklist_acc_dev(ctx, pt, nblk, mt, mt, tuning().acc_tile != 128);
+        gemm_tasklist_dev(ctx, pt, nblk, mt, mt, {tuning().acc_tile != 128 ? GemmTile::T64 : GemmTile::T128, /*acc*/ true});
       }
     }
     for (int k = 0; k < nblk; k++) {

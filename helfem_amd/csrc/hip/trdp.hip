@@ -28,7 +28,7 @@
 // bounded by a wall-clock limit; a workgroup that runs into it sets the status word and the launch drains.
 // Co-residency of the grid is checked by hipLaunchCooperativeKernel; when it refuses, or the matrices do not fit the
 // register file, tridiagonalize_batch (trd.hip) runs its chain of launches instead.
-#include "common.h"
+#include "internal.h"
 #include "wave.h"
 #include <cstdio>
 #include <cstdlib>
@@ -902,17 +902,6 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
   if (w.pending_this_batch) HFG_HIP_CHECK(hipMemcpyAsync(w.h_status, w.ring.p, TP_MAXLAUNCH * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   w.pending_this_batch = false;
   for (int i = 0; i < nblk; i++) done[i] = touched[i] && !failed[i];
-}
-
-/// replay of the last batch's launch on scratch copies is not possible (the kernel consumes its input); the bench
-/// times the launch inside the eigensolve through the profiling events of the "eig_tridiag" scope instead.
-void trdp_last_shape(hfg_ctx *ctx, int *R, int *U, int *grid) {
-  *R = *U = *grid = 0;
-  auto it = g_trdp.find(ctx);
-  if (it == g_trdp.end()) return;
-  *R = it->second->last_R;
-  *U = it->second->last_U;
-  *grid = it->second->last_grid;
 }
 
 }  // namespace hfg

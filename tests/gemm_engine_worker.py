@@ -210,6 +210,7 @@ def probe():
         dp, ip, lp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)
         _probe.probe_gemm_launch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, lp, dp, dp, ctypes.c_int64, dp,
                                              ctypes.c_int64, dp, ctypes.c_int64, ip, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ip]
+        _probe.probe_gemm_worklist.argtypes = [ctypes.c_int, ip, ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip]
     return _probe
 
 
@@ -381,6 +382,34 @@ def wl_tasks(tile, target, split):
     raise RuntimeError("no third task gives a work list of length %d mod 8" % target)
 
 
+WL_EDGES = [1, 64, 65, 128, 129]
+WL_TILES = [("64", 1, (64, 64)), ("128", 2, (128, 128)), ("128x64", 3, (128, 64))]  # (name, GemmTile, (BM, BN))
+
+
+def worklist_cases():
+    """the list gemm_worklist builds (host work) against its enumeration written out here: (task, tile), or for split K
+    (task, 2 tile + half), for every tile of every non-empty task in task order; two tasks around an empty one"""
+    ip = ctypes.POINTER(ctypes.c_int)
+    for tname, tile, (BM, BN) in WL_TILES:
+        for split in (0, 1):
+            ok, detail, count = True, "", 0
+            for i, m in enumerate(WL_EDGES):
+                for j, n in enumerate(WL_EDGES):
+                    shapes = [(m, n), ((0, 50), (50, 0))[(i + j) % 2], (WL_EDGES[(j + 2) % 5], WL_EDGES[(i + 1) % 5])]
+                    want = [(t, q) for t, (M, N) in enumerate(shapes) if M > 0 and N > 0
+                            for q in range(-(-M // BM) * -(-N // BN) * (2 if split else 1))]
+                    mn = np.asarray(shapes, dtype=np.int32).ravel()
+                    out = np.full(2 * len(want) + 8, -7, dtype=np.int32)
+                    n_out = ctypes.c_int(-1)
+                    rc = probe().probe_gemm_worklist(len(shapes), mn.ctypes.data_as(ip), tile, split, out.ctypes.data_as(ip), out.size // 2,
+                                                     ctypes.byref(n_out))
+                    got = [tuple(int(x) for x in out[2 * k:2 * k + 2]) for k in range(max(0, min(n_out.value, out.size // 2)))]
+                    count += len(want)
+                    if ok and (rc != 0 or n_out.value != len(want) or got != want):
+                        ok, detail = False, "tasks %r: %d entries %r..., want %d %r..." % (shapes, n_out.value, got[:6], len(want), want[:6])
+            record("worklist-host/%s%s" % (tname, "-split2" if split else ""), ok, True, 0.0, detail or "%d entries" % count)
+
+
 def bitwise_equal(a, b):
     return np.array_equal(a.view(np.int64), b.view(np.int64))
 
@@ -454,6 +483,7 @@ def engine_cases():
             out = run_variant("worklist%d" % target, var, wl_tasks(var[3], target, split), 1000 + target)
             nwg = out["exact"][2]
             record("worklist%d/%s/length" % (target, name), nwg % 8 == target and nwg >= 8, True, 0.0, "nwg = %d" % nwg)
+    worklist_cases()
     # ---- empty tasks and a task far smaller than maxM x maxN ----
     empty = [Task(200, 200, 24), Task(0, 50, 24), Task(5, 3, 24, alpha=-1.0), Task(50, 0, 24), Task(190, 70, 24, 1, 1, beta=1.0)]
     for var in VARIANTS:

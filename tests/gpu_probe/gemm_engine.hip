@@ -2,25 +2,10 @@
 // tests/test_gpu_gemm_engine.py: one call uploads the operand buffers and a list of task descriptions, runs ONE named
 // launcher once and copies the WHOLE C buffer back, padding included.  A probe library of its own
 // (tests/gpu_probe/libgemm_engine_probe.so, linked against libhelfem_amd.so); the product library gains no entry point.
-#include "../../helfem_amd/csrc/hip/common.h"
+#include "../../helfem_amd/csrc/hip/internal.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-
-namespace hfg {
-void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda, const double *B, int ldb,
-              double beta, double *C, int ldc);
-void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_acc_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, bool tile64);
-void gemm_tasklist64_map_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_split2_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_split2_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_wl_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, int nwg, int tiles);
-void gemm_tasklist_wl_split2_rect_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, int nwg);
-void gemm_mirror_lower_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxN);
-}  // namespace hfg
 
 using namespace hfg;
 #define HFG_TRY try {
@@ -36,25 +21,29 @@ namespace {
 // launcher numbers of probe_gemm_launch (tests/gemm_engine_worker.py holds the same table)
 enum Launcher {
   L_GEMM = 0,         // gemm_dev on task 0
-  L_TASKLIST = 1,     // gemm_tasklist_dev
-  L_TASKLIST64 = 2,   // gemm_tasklist64_dev
-  L_RECT = 3,         // gemm_tasklist_rect_dev
-  L_ACC = 4,          // gemm_tasklist_acc_dev, flag != 0: 64 x 64 tiles
-  L_MAP64 = 5,        // gemm_tasklist64_map_dev
-  L_SPLIT2 = 6,       // gemm_tasklist_split2_dev
-  L_SPLIT2_RECT = 7,  // gemm_tasklist_split2_rect_dev
-  L_WL = 8,           // gemm_tasklist_wl_dev, flag = tiles (0: 128 x 128, 1: 128 x 64, 2: 64 x 64)
-  L_WL_SPLIT2_RECT = 9,  // gemm_tasklist_wl_split2_rect_dev
+  L_TASKLIST = 1,     // gemm_tasklist_dev, {}: Auto
+  L_TASKLIST64 = 2,   // {T64}
+  L_RECT = 3,         // {T128x64}
+  L_ACC = 4,          // {T64 (flag != 0) or T128, acc}
+  L_MAP64 = 5,        // {T64, map}
+  L_SPLIT2 = 6,       // {T128, split2}
+  L_SPLIT2_RECT = 7,  // {T128x64, split2}
+  L_WL = 8,           // gemm_worklist_dev, flag = tiles (0: T128, 1: T128x64, 2: T64)
+  L_WL_SPLIT2_RECT = 9,  // gemm_worklist_dev, T128x64 with split2
   L_MIRROR = 10       // gemm_mirror_lower_dev (maxN)
 };
 constexpr int TI = 16;  // integers per task description
 }  // namespace
 
 extern "C" {
+int probe_gemm_launch(hfg_ctx *ctx, int launcher, int flag, int ntasks, const int64_t *ti, const double *td, const double *A,
+                      int64_t nA, const double *B, int64_t nB, double *C, int64_t nC, const int *maps, int64_t nmaps, int maxM,
+                      int maxN, int *nwg_out);
+int probe_gemm_worklist(int ntasks, const int *mn, int tile, int split2, int *out, int cap, int *n_out);
+
 // ti[t * 16 + ...]: 0 offA, 1 offB, 2 offC (elements inside the buffers A, B, C), 3 M, 4 N, 5 K, 6 lda, 7 ldb, 8 ldc, 9 tA,
 // 10 tB, 11 sym, 12 over, 13 / 14 offsets of amap / cmap inside `maps` (-1: none); td[t * 2 + ...]: alpha, beta.
-// The work-list launchers get their list from here: (task, tile) for every tile tm + nbm * tn of every task in task order,
-// (task, 2 tile + half) for split K -- as exchange_lr.hip enumerates them; *nwg_out receives its length.
+// The work-list launchers get their list from gemm_worklist, as exchange_lr.hip does; *nwg_out receives its length.
 int probe_gemm_launch(hfg_ctx *ctx, int launcher, int flag, int ntasks, const int64_t *ti, const double *td, const double *A,
                       int64_t nA, const double *B, int64_t nB, double *C, int64_t nC, const int *maps, int64_t nmaps, int maxM,
                       int maxN, int *nwg_out) {
@@ -93,15 +82,11 @@ int probe_gemm_launch(hfg_ctx *ctx, int launcher, int flag, int ntasks, const in
   dtasks.resize(tasks.size());
   HFG_HIP_CHECK(hipMemcpy((void *)dtasks.p, (const void *)tasks.data(), sizeof(GemmTask) * tasks.size(), hipMemcpyHostToDevice));
   int nwg = 0;
+  GemmTile wl_tile = GemmTile::Auto;
   if (launcher == L_WL || launcher == L_WL_SPLIT2_RECT) {
-    const bool split = launcher == L_WL_SPLIT2_RECT;
-    const int BM = (!split && flag == 2) ? 64 : 128, BN = (!split && flag == 0) ? 128 : 64;
+    wl_tile = launcher == L_WL_SPLIT2_RECT ? GemmTile::T128x64 : flag == 2 ? GemmTile::T64 : flag == 1 ? GemmTile::T128x64 : GemmTile::T128;
     std::vector<int2> wl;
-    for (int t = 0; t < ntasks; t++) {
-      if (tasks[t].M <= 0 || tasks[t].N <= 0) continue;
-      const int nt = ((tasks[t].M + BM - 1) / BM) * ((tasks[t].N + BN - 1) / BN);
-      for (int q = 0; q < (split ? 2 * nt : nt); q++) wl.push_back(make_int2(t, q));
-    }
+    gemm_worklist(tasks, wl_tile, launcher == L_WL_SPLIT2_RECT, wl);
     nwg = (int)wl.size();
     dwl.resize(wl.size() ? wl.size() : 1);
     if (nwg) HFG_HIP_CHECK(hipMemcpy((void *)dwl.p, (const void *)wl.data(), sizeof(int2) * wl.size(), hipMemcpyHostToDevice));
@@ -111,19 +96,35 @@ int probe_gemm_launch(hfg_ctx *ctx, int launcher, int flag, int ntasks, const in
   switch (launcher) {
     case L_GEMM: gemm_dev(ctx, g0.tA != 0, g0.tB != 0, g0.M, g0.N, g0.K, g0.alpha, g0.A, g0.lda, g0.B, g0.ldb, g0.beta, g0.C, g0.ldc); break;
     case L_TASKLIST: gemm_tasklist_dev(ctx, dtasks.p, ntasks, maxM, maxN); break;
-    case L_TASKLIST64: gemm_tasklist64_dev(ctx, dtasks.p, ntasks, maxM, maxN); break;
-    case L_RECT: gemm_tasklist_rect_dev(ctx, dtasks.p, ntasks, maxM, maxN); break;
-    case L_ACC: gemm_tasklist_acc_dev(ctx, dtasks.p, ntasks, maxM, maxN, flag != 0); break;
-    case L_MAP64: gemm_tasklist64_map_dev(ctx, dtasks.p, ntasks, maxM, maxN); break;
-    case L_SPLIT2: gemm_tasklist_split2_dev(ctx, dtasks.p, ntasks, maxM, maxN); break;
-    case L_SPLIT2_RECT: gemm_tasklist_split2_rect_dev(ctx, dtasks.p, ntasks, maxM, maxN); break;
-    case L_WL: gemm_tasklist_wl_dev(ctx, dtasks.p, dwl.p, nwg, flag); break;
-    case L_WL_SPLIT2_RECT: gemm_tasklist_wl_split2_rect_dev(ctx, dtasks.p, dwl.p, nwg); break;
+    case L_TASKLIST64: gemm_tasklist_dev(ctx, dtasks.p, ntasks, maxM, maxN, {GemmTile::T64}); break;
+    case L_RECT: gemm_tasklist_dev(ctx, dtasks.p, ntasks, maxM, maxN, {GemmTile::T128x64}); break;
+    case L_ACC: gemm_tasklist_dev(ctx, dtasks.p, ntasks, maxM, maxN, {flag != 0 ? GemmTile::T64 : GemmTile::T128, /*acc*/ true}); break;
+    case L_MAP64: gemm_tasklist_dev(ctx, dtasks.p, ntasks, maxM, maxN, {GemmTile::T64, /*acc*/ false, /*split2*/ false, /*map*/ true}); break;
+    case L_SPLIT2: gemm_tasklist_dev(ctx, dtasks.p, ntasks, maxM, maxN, {GemmTile::T128, /*acc*/ false, /*split2*/ true}); break;
+    case L_SPLIT2_RECT: gemm_tasklist_dev(ctx, dtasks.p, ntasks, maxM, maxN, {GemmTile::T128x64, /*acc*/ false, /*split2*/ true}); break;
+    case L_WL: gemm_worklist_dev(ctx, dtasks.p, dwl.p, nwg, wl_tile); break;
+    case L_WL_SPLIT2_RECT: gemm_worklist_dev(ctx, dtasks.p, dwl.p, nwg, wl_tile, true); break;
     case L_MIRROR: gemm_mirror_lower_dev(ctx, dtasks.p, ntasks, maxN); break;
     default: throw std::logic_error("probe_gemm_launch: unknown launcher");
   }
   HFG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (nC > 0) HFG_HIP_CHECK(hipMemcpy(C, dC.p, sizeof(double) * nC, hipMemcpyDeviceToHost));
+  HFG_CATCH
+}
+
+// gemm_worklist alone (host work): tasks of mn[2 t] rows and mn[2 t + 1] columns; tile 1: 64 x 64, 2: 128 x 128, 3: 128 x 64
+// (the values of GemmTile); out receives the first `cap` (task, entry) pairs, *n_out the length of the list
+int probe_gemm_worklist(int ntasks, const int *mn, int tile, int split2, int *out, int cap, int *n_out) {
+  HFG_TRY
+  std::vector<GemmTask> tasks(ntasks);
+  for (int t = 0; t < ntasks; t++) {
+    memset((void *)&tasks[t], 0, sizeof(GemmTask));
+    tasks[t].M = mn[2 * t], tasks[t].N = mn[2 * t + 1];
+  }
+  std::vector<int2> wl;
+  gemm_worklist(tasks, (GemmTile)tile, split2 != 0, wl);
+  *n_out = (int)wl.size();
+  for (int i = 0; i < std::min(cap, *n_out); i++) out[2 * i] = wl[i].x, out[2 * i + 1] = wl[i].y;
   HFG_CATCH
 }
 }

@@ -18,15 +18,12 @@
 //   back-transformation  Z <- Q1 (Q2 Z):  Q2 (the SB-long reflectors of stage 2) applied sweep by sweep to column slabs
 //            of Z resident in LDS, Q1 through the compact-WY machinery of eig.hip.
 // tools/two_stage_model.py is the NumPy statement of the same algorithm with the same index conventions.
-#include "../../helfem_amd/csrc/hip/common.h"
+#include "../../helfem_amd/csrc/hip/internal.h"
 #include "../../helfem_amd/csrc/hip/wave.h"
 #include <cstdlib>
 #include <cstring>
 
 namespace hfg {
-
-void gemm_tasklist64_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN);
-void gemm_tasklist_acc_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, bool tile64);
 
 constexpr int SB = 32;             // half-bandwidth of the intermediate band matrix
 constexpr int SB_LDB = 2 * SB;     // band storage: AB[j * SB_LDB + d] = A[j + d][j], d < 2 SB (room for the bulge)
@@ -590,7 +587,7 @@ struct SbWork {
   std::vector<GemmTask> h_xtasks, h_utasks;
 };
 static std::map<hfg_ctx *, SbWork *> g_sb;
-void sb_release(hfg_ctx *ctx) {
+static void sb_release(hfg_ctx *ctx) {
   auto it = g_sb.find(ctx);
   if (it != g_sb.end()) {
     delete it->second;
@@ -605,7 +602,7 @@ static SbWork &sb_work(hfg_ctx *ctx) {
   return *w;
 }
 
-bool sb_supported(int nblk, const int *ns) {
+static bool sb_supported(int nblk, const int *ns) {
   if (nblk > SB_MAXB) return false;
   for (int i = 0; i < nblk; i++)
     if (ns[i] - SB > SBP_NG * SB_TMAX || ns[i] < 4 * SB) return false;
@@ -614,7 +611,7 @@ bool sb_supported(int nblk, const int *ns) {
 
 /// stage 1 for a batch: A[blk] (n x n full symmetric, ld n) -> band form in place + band storage AB; reflectors in the
 /// work area (read by the back-transformation)
-void sb_reduce_to_band(hfg_ctx *ctx, int nblk, const int *ns, double *const *A) {
+static void sb_reduce_to_band(hfg_ctx *ctx, int nblk, const int *ns, double *const *A) {
   if (!sb_supported(nblk, ns)) throw std::logic_error("sb_reduce_to_band: problem size outside the two-stage kernels' range");
   SbWork &w = sb_work(ctx);
   hipStream_t s = ctx->stream;
@@ -708,13 +705,13 @@ void sb_reduce_to_band(hfg_ctx *ctx, int nblk, const int *ns, double *const *A) 
       else hipLaunchKernelGGL(k_sb_panel<SB_TMAX>, dim3(nblk), dim3(SBP_NT), 0, s, db, j0);
     }
     if (last_step < 2) break;
-    gemm_tasklist64_dev(ctx, w.xtasks.p + (size_t)p * SB_KS * nblk, SB_KS * nblk, mmax, SB);
+    gemm_tasklist_dev(ctx, w.xtasks.p + (size_t)p * SB_KS * nblk, SB_KS * nblk, mmax, SB, {GemmTile::T64});
     if (last_step < 3) break;
     const int ntile = (mmax + SB_RT - 1) / SB_RT;
     hipLaunchKernelGGL(k_sb_w1, dim3(ntile, nblk), dim3(256), 0, s, db, j0);
     hipLaunchKernelGGL(k_sb_w2, dim3(ntile, nblk), dim3(256), 0, s, db, j0);
     if (last_step < 4) break;
-    gemm_tasklist_acc_dev(ctx, w.utasks.p + (size_t)p * nblk, nblk, mmax, mmax, mmax < 1024);
+    gemm_tasklist_dev(ctx, w.utasks.p + (size_t)p * nblk, nblk, mmax, mmax, {mmax < 1024 ? GemmTile::T64 : GemmTile::T128, /*acc*/ true});
   }
   hipLaunchKernelGGL(k_sb_gather_band, dim3((nmax + 3) / 4, nblk), dim3(256), 0, s, db);
   HFG_HIP_CHECK(hipGetLastError());
@@ -722,7 +719,7 @@ void sb_reduce_to_band(hfg_ctx *ctx, int nblk, const int *ns, double *const *A) 
 
 /// stage 2 for the batch last reduced by sb_reduce_to_band: band storage -> tridiagonal (d, e device arrays of n each);
 /// G sweeps in flight per block.  Throws when a wave's bounded wait ran out (status word).
-void sb_chase(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, double *const *e, int G, int delayed) {
+static void sb_chase(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, double *const *e, int G, int delayed) {
   SbWork &w = sb_work(ctx);
   hipStream_t s = ctx->stream;
   SbBatch b = w.hb;
@@ -754,7 +751,7 @@ void sb_chase(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, double *c
   hipLaunchKernelGGL(k_sb_finish, dim3((nmax + 255) / 256, nblk), dim3(256), 0, s, w.desc.p);
   HFG_HIP_CHECK(hipGetLastError());
 }
-int sb_chase_status(hfg_ctx *ctx) {
+static int sb_chase_status(hfg_ctx *ctx) {
   SbWork &w = sb_work(ctx);
   int st = 0;
   HFG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -763,21 +760,21 @@ int sb_chase_status(hfg_ctx *ctx) {
 }
 
 /// test access: band storage (n x SB_LDB, column j at [j * SB_LDB]) of the last reduction of this context, block blk
-void sb_fetch_band(hfg_ctx *ctx, int blk, int n, double *hostAB) {
+static void sb_fetch_band(hfg_ctx *ctx, int blk, int n, double *hostAB) {
   SbWork &w = sb_work(ctx);
   HFG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   HFG_HIP_CHECK(hipMemcpy(hostAB, w.AB[blk].p, sizeof(double) * (size_t)n * SB_LDB, hipMemcpyDeviceToHost));
 }
 /// diagnostics: the work arrays of block 0 (which: 0 A, 1 Vx, 2 T1, 3 X, 4 Lm, 5 Rm), whole arrays
-void sb_fetch_debug(hfg_ctx *ctx, int which, int n, double *host, size_t count) {
+static void sb_fetch_debug(hfg_ctx *ctx, int which, int n, double *host, size_t count) {
   SbWork &w = sb_work(ctx);
   HFG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   const double *src = which == 0 ? w.hb.A[0] : which == 1 ? w.Vx[0].p : which == 2 ? w.T1[0].p : which == 3 ? w.X[0].p : which == 4 ? w.Lm[0].p : w.Rm[0].p;
   (void)n;
   HFG_HIP_CHECK(hipMemcpy(host, src, sizeof(double) * count, hipMemcpyDeviceToHost));
 }
-int sb_bandwidth() { return SB; }
-int sb_ldb() { return SB_LDB; }
+static int sb_bandwidth() { return SB; }
+static int sb_ldb() { return SB_LDB; }
 
 }  // namespace hfg
 
@@ -797,6 +794,12 @@ using namespace hfg;
   }                                     \
   return 0;
 extern "C" {
+int probe_band_reduce(hfg_ctx *ctx, int64_t n, const double *A, int nrep, double *AB, int *bandwidth, int *ldb, double *ms);
+int probe_two_stage(hfg_ctx *ctx, int64_t n, const double *A, int nrep, int G, int delayed, double *d, double *e, double *ms1, double *ms2);
+int probe_band_fetch(hfg_ctx *ctx, int which, int64_t n, double *out, int64_t count);
+int probe_band_reduce_keep(hfg_ctx *ctx, int64_t n, const double *A, double *Aout);
+int probe_release(hfg_ctx *ctx);
+
 // Diagnostic access to the first stage of the two-stage tridiagonalisation (this file): nrep copies of the symmetric
 // matrix A (n x n) are reduced to band form in one batch; AB receives the band storage of the first copy
 // (AB[j * ldb + d] = A_band[j + d][j]), ms the device time of the reduction.
