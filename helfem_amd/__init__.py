@@ -650,6 +650,46 @@ class scf(object):
         return E, C
 
     @staticmethod
+    def eig_sel_count(m_idx, nev):
+        """number of eigenpairs eig_gsym_sub_sel returns: the sum over the blocks of min(nev, block size)"""
+        ptr, _ = scf._blocks(m_idx)
+        f = lib().hfg_eig_sel_count
+        f.restype = ctypes.c_int64
+        f.argtypes = [ctypes.c_int, c_i64_p, ctypes.c_int64]
+        return int(f(len(m_idx), ptr.ctypes.data_as(c_i64_p), int(nev)))
+
+    @staticmethod
+    def eig_sym_sel(A, nev, ctx=None):
+        """the lowest min(nev, n) eigenpairs of a symmetric matrix (hfg_eig_sym_sel): E ascending, C n x len(E)"""
+        ctx = ctx or default_context()
+        A = _f(A)
+        n = A.shape[0]
+        K = max(0, min(int(nev), n))
+        E = np.zeros(K)
+        C = np.zeros((n, K), order="F")
+        f = lib().hfg_eig_sym_sel
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int64, c_double_p, c_double_p]
+        _check(f(ctx.h, n, _p(A), int(nev), _p(E), _p(C)))
+        return E, C
+
+    @staticmethod
+    def eig_gsym_sub_sel(F, Sinvh, m_idx, nev, ctx=None):
+        """the lowest min(nev, block size) eigenpairs of every symmetry block, sorted globally (hfg_eig_gsym_sub_sel): E (K),
+        C (N x K), K = eig_sel_count(m_idx, nev).  The lowest m <= nev levels of the full problem are the first m returned."""
+        ctx = ctx or default_context()
+        F, Sinvh = _f(F), _f(Sinvh)
+        N = F.shape[0]
+        ptr, idx = scf._blocks(m_idx)
+        K = scf.eig_sel_count(m_idx, nev) if nev >= 1 else 0
+        E = np.zeros(K)
+        C = np.zeros((N, K), order="F")
+        f = lib().hfg_eig_gsym_sub_sel
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int, c_i64_p, c_i64_p, ctypes.c_int64, c_double_p,
+                      c_double_p]
+        _check(f(ctx.h, N, _p(F), _p(Sinvh), len(m_idx), ptr.ctypes.data_as(c_i64_p), idx.ctypes.data_as(c_i64_p), int(nev), _p(E), _p(C)))
+        return E, C
+
+    @staticmethod
     def form_Sinvh(S, chol, m_idx, ctx=None):
         ctx = ctx or default_context()
         S = _f(S)

@@ -19,7 +19,7 @@ LIBDIR = os.path.join(ROOT, "helfem_amd", "lib")
 OBJDIR = os.path.join(ROOT, "helfem_amd", "build")
 
 HOST_SRCS = ["host/fem.cpp", "host/special.cpp", "host/atomic_basis.cpp", "host/diatomic_basis.cpp", "host/scf.cpp", "host/diis.cpp", "host/checkpoint.cpp", "host/dftfuncs.cpp", "host/tuning.cpp"]
-HIP_SRCS = ["hip/tables.cpp", "hip/capi.cpp", "hip/fock.hip", "hip/exchange.hip", "hip/exchange_lr.hip", "hip/gemm.hip", "hip/eig.hip", "hip/dc.hip", "hip/trd.hip", "hip/trdp.hip",
+HIP_SRCS = ["hip/tables.cpp", "hip/capi.cpp", "hip/fock.hip", "hip/exchange.hip", "hip/exchange_lr.hip", "hip/gemm.hip", "hip/eig.hip", "hip/dc.hip", "hip/stsel.hip", "hip/trd.hip", "hip/trdp.hip",
             "hip/misc.hip", "hip/scf_gpu.cpp", "hip/scf_device.hip", "hip/tei_dev.hip"]
 
 
@@ -105,10 +105,15 @@ def build_cli(verbose=True, force=False):
 
 
 def build_adapter_test(verbose=True):
-    """tests/cpp/adapter_test: calls the hot path through include/helfem_gpu_arma.hpp (built next to the library; the GPU box
-    runs it from tests/test_gpu_adapter.py)"""
-    src = os.path.join(ROOT, "tests", "cpp", "adapter_test.cpp")
-    exe = os.path.join(ROOT, "tests", "cpp", "adapter_test")
+    """tests/cpp/adapter_test and tests/cpp/eigsel_adapter_test: call the hot path through include/helfem_gpu_arma.hpp (built
+    next to the library; the GPU box runs them from tests/test_gpu_adapter.py and tests/test_gpu_eigsel_adapter.py)"""
+    for name in ("adapter_test", "eigsel_adapter_test"):
+        _build_adapter_program(name, verbose)
+
+
+def _build_adapter_program(name, verbose):
+    src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
+    exe = os.path.join(ROOT, "tests", "cpp", name)
     lib = os.path.join(LIBDIR, "libhelfem_amd.so")
     deps = (os.path.join(ROOT, "include", "helfem_gpu_arma.hpp"), os.path.join(ROOT, "include", "helfem_gpu.h"), lib)
     if _newer(src, exe, deps):

@@ -169,6 +169,7 @@ int hfg_ctx_destroy(hfg_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   eig_release(c);
   dc_release(c);
+  stsel_release(c);
   trd_release(c);
   trdp_release(c);
   for (auto &kv : c->prof)
@@ -978,6 +979,43 @@ int hfg_eig_gsym_sub(hfg_ctx *ctx, int64_t N, const double *F, const double *S, 
   st.down(E, dE, N);
   st.down(C, dC, N * N);
   st.sync();
+  HFG_CATCH
+}
+int64_t hfg_eig_sel_count(int nblk, const int64_t *blk_ptr, int64_t nev) {
+  if (nblk < 0 || !blk_ptr || nev < 1) return 0;
+  return eig_sel_count(nblk, blk_ptr, nev);
+}
+int hfg_eig_sym_sel(hfg_ctx *ctx, int64_t n, const double *A, int64_t nev, double *E, double *C) {
+  HFG_TRY
+  if (nev < 1) throw std::logic_error("eig_sym_sel: nev must be at least 1\n");
+  if (n < 1) throw std::logic_error("eig_sym_sel: empty matrix\n");
+  const int64_t K = std::min(nev, n);
+  Stage st(ctx);
+  double *dA = st.up(A, n * n), *dE = st.alloc(K), *dC = st.alloc(n * K);
+  eig_sym_sel_dev(ctx, (int)n, dA, (int)K, dE, dC);
+  st.down(E, dE, K);
+  st.down(C, dC, n * K);
+  st.sync();
+  HFG_CATCH
+}
+int hfg_eig_gsym_sub_sel(hfg_ctx *ctx, int64_t N, const double *F, const double *S, int nblk, const int64_t *blk_ptr,
+                         const int64_t *blk_idx, int64_t nev, double *E, double *C) {
+  HFG_TRY
+  if (nev < 1) throw std::logic_error("eig_gsym_sub_sel: nev must be at least 1\n");
+  const int64_t K = eig_sel_count(nblk, blk_ptr, nev);
+  Stage st(ctx);
+  double *dF = st.up(F, N * N), *dS = st.up(S, N * N), *dE = st.alloc(std::max<int64_t>(K, 1)), *dC = st.alloc(std::max<int64_t>(N * K, 1));
+  eig_gsym_sub_sel_dev(ctx, (int)N, dF, dS, nblk, blk_ptr, blk_idx, (int)std::min<int64_t>(nev, N), dE, dC);
+  st.down(E, dE, K);
+  st.down(C, dC, N * K);
+  st.sync();
+  HFG_CATCH
+}
+int hfg_eig_gsym_sub_sel_dev(hfg_ctx *ctx, int64_t N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
+                             const int64_t *blk_idx, int64_t nev, double *dE, double *dC) {
+  HFG_TRY
+  if (nev < 1) throw std::logic_error("eig_gsym_sub_sel: nev must be at least 1\n");
+  eig_gsym_sub_sel_dev(ctx, (int)N, dF, dS, nblk, blk_ptr, blk_idx, (int)std::min<int64_t>(nev, N), dE, dC);
   HFG_CATCH
 }
 int hfg_eig_gsym_sub_pair(hfg_ctx *ctx, int64_t N, const double *Fa, const double *Fb, const double *S, int nblk, const int64_t *blk_ptr,

@@ -1067,6 +1067,15 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
   }
 }
 
+/// the status word that dc_status reads (4 ints), for the other solver of the tridiagonal stage (stsel.hip); the caller
+/// clears it on the stream before its kernels
+int *dc_status_word(hfg_ctx *ctx) {
+  auto it = g_dc.find(ctx);
+  if (it == g_dc.end()) it = g_dc.emplace(ctx, new DCWork()).first;
+  it->second->status.resize(4);
+  return it->second->status.p;
+}
+
 int dc_status(hfg_ctx *ctx) {
   auto it = g_dc.find(ctx);
   if (it == g_dc.end()) return 0;

@@ -17,6 +17,7 @@
 //   6. C = X Z                                                   GEMM, then rank sort + scatter
 #include "internal.h"
 #include "wave.h"
+#include "../host/eigsel_count.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -33,7 +34,8 @@ struct EigBatch {
   double *v[MAXB];    // n   current Householder vector (v[0]=1 stored explicitly)
   double *pp[MAXB];   // NCS x n partial gemv results
   double *dots[MAXB];  // partial v^T A v per gemv workgroup
-  double *Z[MAXB];    // n x n eigenvectors
+  double *Z[MAXB];    // n x nz eigenvectors
+  int nz[MAXB];       // columns of Z: n, or the wanted ones of a selected solve
   double *rot[MAXB];  // rotation log (c,s pairs)
   int *sweeps[MAXB];  // (l, m, offset, count) per QL sweep; sweeps[0] = number of sweeps, [1]=status
   long rotcap[MAXB];
@@ -322,7 +324,7 @@ __global__ __launch_bounds__(256) void k_backtransform(EigBatch b) {
   int n = b.n[blk];
   int col = blockIdx.x * 4 + (threadIdx.x >> 6);
   int lane = threadIdx.x & 63;
-  if (col >= n) return;
+  if (col >= b.nz[blk]) return;
   const double *A = b.A[blk];
   const double *tau = b.tau[blk];
   double *z = b.Z[blk] + (size_t)col * n;
@@ -366,7 +368,7 @@ __global__ __launch_bounds__(256) void k_backtransform_lds(EigBatch b) {
   int n = b.n[blk];
   int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   int col = blockIdx.x * 4 + wave;
-  if (col >= n) return;
+  if (col >= b.nz[blk]) return;
   const double *A = b.A[blk];
   const double *tau = b.tau[blk];
   double *z = b.Z[blk] + (size_t)col * n;
@@ -433,6 +435,18 @@ __global__ void k_scatter_cols(const double *__restrict__ Cb, int nrow, int ncol
   size_t r = rows ? (size_t)rows[i] : (size_t)i;
   Cout[(size_t)c * ldc + r] = Cb[(size_t)j * nrow + i];
   if (i == 0) Eout[c] = Eb[j];
+}
+
+// selected solve through the full one: column j of Z (n x n) with rank[j] < nev goes to column rank[j] of Zs (n x nev), its
+// eigenvalue to Ws[rank[j]]
+__global__ void k_take_lowest(const double *__restrict__ Z, const double *__restrict__ E, int n, int nev, const int *__restrict__ rank,
+                              double *__restrict__ Zs, double *__restrict__ Ws) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int j = blockIdx.y;
+  int c = rank[j];
+  if (i >= n || c >= nev) return;
+  Zs[(size_t)c * n + i] = Z[(size_t)j * n + i];
+  if (i == 0) Ws[c] = E[j];
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -622,6 +636,8 @@ struct EigWork {
   DevBuf<GemmTask> btslabR, btupdR;
   std::vector<GemmTask> h_btslabR, h_btupdR;
   DevBuf<double> A[MAXB], d[MAXB], e[MAXB], tau[MAXB], v[MAXB], pp[MAXB], dots[MAXB], Z[MAXB], rot[MAXB];
+  DevBuf<double> Zs[MAXB], Ws[MAXB];  // selected solve: the wanted eigenvectors (n x nev, ld n) and eigenvalues, ascending
+  DevBuf<int> selrank;
   DevBuf<int> sweeps[MAXB];
   DevBuf<int> ibuf1, ibuf2;
   DevBuf<GemmTask> gtasks, bttasks, btslab, btgram, btcpl, btupd;
@@ -708,6 +724,7 @@ __global__ __launch_bounds__(256) void k_transpose_batch(TrPtrs t) {
   }
 }
 
+/// b.nz: the columns of b.Z that the left application (bt_wy_apply) works on
 static void bt_wy_setup(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, const int *ns, int nmax, bool fold = false) {
   hipStream_t s = ctx->stream;
   const int P = (nmax - 3) / BT_KB + 1;  // reflector blocks of the largest matrix
@@ -811,7 +828,7 @@ static void bt_wy_setup(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, c
         q.C = w.Wp[k].p + (size_t)sl * BT_PW * n;
         q.tA = 1;
         q.M = kbp;
-        q.N = n;
+        q.N = b.nz[k];
         q.K = kk;  // empty slab: K = 0 writes zeros
         q.lda = q.ldb = n;
         q.ldc = BT_PW;
@@ -822,7 +839,7 @@ static void bt_wy_setup(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, c
       u.B = w.Wb[k].p;
       u.C = b.Z[k] + r0;
       u.M = mr;
-      u.N = n;
+      u.N = b.nz[k];
       u.K = kbp;
       u.lda = n;
       u.ldb = BT_PW;
@@ -971,21 +988,50 @@ static void bt_wy_fold_x(hfg_ctx *ctx, EigWork &w, const EigBatch &b, int nblk, 
 /// foldX != nullptr (device pointers of the blocks' X, n x n, ld n): the caller wants C = X Q Z; then X Q is formed beside
 /// the divide-and-conquer stage (w.Y = (X Q)^T, w.folded = true), w.Z keeps the tridiagonal matrix's eigenvectors and
 /// the caller multiplies Y^T Z.  Otherwise (and when the compact-WY path does not apply) Z <- Q Z as before.
-static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, const double *const *foldX = nullptr) {
+/// nev != nullptr (1 <= nev[i] <= ns[i]): the lowest nev[i] eigenpairs only, eigenvalues ascending in w.Ws[i], eigenvectors
+/// in w.Zs[i] (n x nev[i], ld n) in place of w.d and w.Z.  Two paths, chosen by eigsel_takes_stein: multisection and inverse
+/// iteration (stsel.hip), or the full tridiagonal solve followed by taking the lowest columns; the back-transformation
+/// works on the nev[i] columns in either.
+// Crossover of the selected solve: multisection and inverse iteration cost O(nev n) per block, all of it in serial chains
+// of about seven passes over n per vector; divide and conquer costs O(n^2) to O(n^3) whatever nev is.  The first value
+// from those counts was 1/8 of the columns.  Measured (n = 1470): the two curves do not meet, stein is
+// slower at 1/64, 1/16, 1/4 and 1/2 of the columns (8.8 ms against 0.73 ms at 1/64: dstein's clusters run their members one
+// after the other), so the crossover is 0 and sends every fraction to dc.  HELFEM_EIGSEL forces either path.
+constexpr double EIGSEL_CROSS = 0.0;  // stein where sum nev_b <= EIGSEL_CROSS sum n_b
+static bool eigsel_takes_stein(int nblk, const int *ns, const int *nev) {
+  const helfem::EigSel how = tuning().eigsel;
+  if (how != helfem::EigSel::crossover) return how == helfem::EigSel::stein;
+  long want = 0, all = 0;
+  for (int i = 0; i < nblk; i++) {
+    want += nev[i];
+    all += ns[i];
+  }
+  return (double)want <= EIGSEL_CROSS * (double)all;
+}
+static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, const double *const *foldX = nullptr,
+                          const int *nev = nullptr) {
   EigBatch b;
   b.nblk = nblk;
-  int nmax = 0;
+  int nmax = 0, nzmax = 0;
+  const bool stein = nev && eigsel_takes_stein(nblk, ns, nev);
   for (int i = 0; i < nblk; i++) {
     int n = ns[i];
     nmax = std::max(nmax, n);
     b.n[i] = n;
+    b.nz[i] = nev ? nev[i] : n;
+    nzmax = std::max(nzmax, b.nz[i]);
+    if (nev) {
+      if (nev[i] < 1 || nev[i] > n) throw std::logic_error("eig_sym_batch: 1 <= nev <= n violated\n");
+      w.Zs[i].resize((size_t)n * nev[i]);
+      w.Ws[i].resize(nev[i]);
+    }
     w.d[i].resize(n);
     w.e[i].resize(n);
     w.tau[i].resize(n);
     w.v[i].resize(n);
     w.pp[i].resize((size_t)TRD_NCS * n);
     w.dots[i].resize((size_t)TRD_NCS * ((n + 63) / 64) + 8);
-    w.Z[i].resize((size_t)n * n);
+    if (!stein) w.Z[i].resize((size_t)n * n);
     long cap = 3L * n * n + 1024;
     w.rot[i].resize(2 * (size_t)cap);
     w.sweeps[i].resize((size_t)4 * 64 * n + 8);
@@ -997,7 +1043,7 @@ static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, con
     b.v[i] = w.v[i].p;
     b.pp[i] = w.pp[i].p;
     b.dots[i] = w.dots[i].p;
-    b.Z[i] = w.Z[i].p;
+    b.Z[i] = stein ? nullptr : w.Z[i].p;  // (the tridiagonal stage's output; a selected solve continues on w.Zs below)
     b.rot[i] = w.rot[i].p;
     b.sweeps[i] = w.sweeps[i].p;
   }
@@ -1011,7 +1057,10 @@ static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, con
   w.folded = fold;
   if (fold)
     for (int i = 0; i < nblk; i++) w.Y[i].resize((size_t)ns[i] * ns[i]);
-  if (bt_wy) bt_wy_setup(ctx, w, b, nblk, ns, nmax, fold);
+  EigBatch bz = b;  // the batch as the back-transformation sees it: Z = the wanted columns
+  if (nev)
+    for (int i = 0; i < nblk; i++) bz.Z[i] = w.Zs[i].p;
+  if (bt_wy) bt_wy_setup(ctx, w, bz, nblk, ns, nmax, fold);
   {
     ProfScope ps(ctx, "eig_tridiag");
     if (tuning().trd_mode == TrdMode::unblocked) {
@@ -1039,7 +1088,18 @@ static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, con
   }
   if (bt_wy) bt_wy_prepare(ctx, w, b, nblk, nmax, fold);
   if (fold) bt_wy_fold_x(ctx, w, b, nblk, ns, nmax, foldX);
-  {
+  if (stein) {
+    ProfScope ps(ctx, "eig_tridiag_sel");
+    w.used_dc = true;  // the status word of this path is the divide-and-conquer stage's
+    double *dp[MAXB], *ep[MAXB], *wp[MAXB], *zp[MAXB];
+    for (int i = 0; i < nblk; i++) {
+      dp[i] = w.d[i].p;
+      ep[i] = w.e[i].p;
+      wp[i] = w.Ws[i].p;
+      zp[i] = w.Zs[i].p;
+    }
+    tridiag_sel_batch(ctx, nblk, ns, nev, dp, ep, wp, zp);
+  } else {
     ProfScope ps(ctx, "eig_tridiag_solve");
     w.used_dc = !tuning().tridiag_ql;
     if (!w.used_dc) {
@@ -1056,25 +1116,37 @@ static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, con
       }
       tridiag_dc_batch(ctx, nblk, ns, dp, ep, zp);
     }
+    if (nev) {  // the lowest columns of the full solve, in ascending order
+      size_t off = 0;
+      for (int i = 0; i < nblk; i++) off += ns[i] + 8;
+      w.selrank.resize(off);
+      off = 0;
+      for (int i = 0; i < nblk; i++) {
+        launch_rank(ctx, w.d[i].p, ns[i], w.selrank.p + off);
+        hipLaunchKernelGGL(k_take_lowest, dim3((ns[i] + 255) / 256, ns[i]), dim3(256), 0, s, w.Z[i].p, w.d[i].p, ns[i], nev[i],
+                           w.selrank.p + off, w.Zs[i].p, w.Ws[i].p);
+        off += ns[i] + 8;
+      }
+    }
   }
   {
     ProfScope ps(ctx, "eig_backtransform");
     if (fold) {
       HFG_HIP_CHECK(hipStreamWaitEvent(s, ctx->side_ev[1], 0));  // Y = (X Q)^T is complete
     } else if (bt_wy) {
-      bt_wy_apply(ctx, w, b, nblk, nmax);
+      bt_wy_apply(ctx, w, bz, nblk, nmax);
     } else {
-    dim3 grid((nmax + 3) / 4, nblk);
+    dim3 grid((nzmax + 3) / 4, nblk);
     if (nmax <= 64 * 8)
-      hipLaunchKernelGGL(k_backtransform<8>, grid, dim3(256), 0, s, b);
+      hipLaunchKernelGGL(k_backtransform<8>, grid, dim3(256), 0, s, bz);
     else if (nmax <= 64 * 24)
-      hipLaunchKernelGGL(k_backtransform<24>, grid, dim3(256), 0, s, b);
+      hipLaunchKernelGGL(k_backtransform<24>, grid, dim3(256), 0, s, bz);
     else {
       size_t shb = (size_t)4 * nmax * sizeof(double);
       if (shb > 64 * 1024)
         HFG_HIP_CHECK(
             hipFuncSetAttribute((const void *)k_backtransform_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-      hipLaunchKernelGGL(k_backtransform_lds, grid, dim3(256), shb, s, b);
+      hipLaunchKernelGGL(k_backtransform_lds, grid, dim3(256), shb, s, bz);
     }
     }
   }
@@ -1106,6 +1178,20 @@ void eig_sym_dev(hfg_ctx *ctx, int n, const double *dA, double *dE, double *dC) 
   launch_rank(ctx, w.d[0].p, n, rank.p);
   hipLaunchKernelGGL(k_scatter_cols, dim3((n + 255) / 256, n), dim3(256), 0, ctx->stream, w.Z[0].p, n, n,
                      (const int64_t *)nullptr, rank.p, 0, w.d[0].p, n, dC, dE);
+  check_status(ctx, w, 1);
+}
+
+// the lowest nev eigenpairs: E (nev, ascending), C (n x nev) ; all device pointers
+void eig_sym_sel_dev(hfg_ctx *ctx, int n, const double *dA, int nev, double *dE, double *dC) {
+  if (nev < 1) throw std::logic_error("eig_sym_sel: nev must be at least 1\n");
+  if (n < 1) throw std::logic_error("eig_sym_sel: empty matrix\n");
+  nev = std::min(nev, n);
+  EigWork &w = work_for(ctx);
+  w.A[0].resize((size_t)n * n + 2);
+  HFG_HIP_CHECK(hipMemcpyAsync(w.A[0].p, dA, sizeof(double) * n * n, hipMemcpyDeviceToDevice, ctx->stream));
+  eig_sym_batch(ctx, w, 1, &n, nullptr, &nev);
+  HFG_HIP_CHECK(hipMemcpyAsync(dC, w.Zs[0].p, sizeof(double) * (size_t)n * nev, hipMemcpyDeviceToDevice, ctx->stream));
+  HFG_HIP_CHECK(hipMemcpyAsync(dE, w.Ws[0].p, sizeof(double) * nev, hipMemcpyDeviceToDevice, ctx->stream));
   check_status(ctx, w, 1);
 }
 
@@ -1149,7 +1235,7 @@ size_t eig_block_buf_size(int nblk, const int64_t *blk_ptr) {
 // tridiagonalisation is a chain of dependent launches whose length does not depend on the number of blocks in it, so two
 // spins cost about what one costs
 static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
-                                 const int64_t *blk_idx, double *const *dBlockBufs);
+                                 const int64_t *blk_idx, double *const *dBlockBufs, int nev = 0);
 static int eig_num_cus(hfg_ctx *ctx) {
   static int ncu = 0;
   if (!ncu) {
@@ -1162,8 +1248,9 @@ void eig_blocks_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int
                     const int64_t *blk_idx, double *dBlockBuf) {
   eig_blocks_multi_dev(ctx, N, 1, &dF, dS, nblk, blk_ptr, blk_idx, &dBlockBuf);
 }
+/// nev > 0: the lowest min(nev, n_b) eigenpairs of every block only; slot ib then holds that many columns (ld n_b) and values
 static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
-                                 const int64_t *blk_idx, double *const *dBlockBufs) {
+                                 const int64_t *blk_idx, double *const *dBlockBufs, int nev) {
   EigWork &w = work_for(ctx);
   hipStream_t s = ctx->stream;
   if (blk_ptr[nblk] != N) throw std::logic_error("Symmetry mismatch in eig_gsym_sub\n");
@@ -1232,7 +1319,7 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
   Xall.resize(nmax * nmax * MAXB);
   for (size_t c0 = 0; c0 < mine.size(); c0 += MAXB) {
     int nb = (int)std::min<size_t>(MAXB, mine.size() - c0);
-    std::vector<int> ns(nb);
+    std::vector<int> ns(nb), nevs(nb);
     // the three products of every block (F X, X^T (F X), X Z) go through one task-list launch each, so that the
     // blocks fill the chip together with 128 x 128 tiles
     std::vector<GemmTask> gt(4 * (size_t)nb);  // [3 nb + k]: the last product when X Q was folded (eig_sym_batch): (X Q) Z = Y^T Z
@@ -1243,9 +1330,11 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
       double *dBlockBuf = dBlockBufs[mine[c0 + k] / nblk];
       int n = (int)(blk_ptr[ib + 1] - blk_ptr[ib]);
       ns[k] = n;
+      nevs[k] = nev > 0 ? std::min(nev, n) : n;
       nm = std::max(nm, n);
       w.A[k].resize((size_t)n * n + 2);  // + 2: the sweep's 16-byte row pairs may straddle the last element
-      w.Z[k].resize((size_t)n * n);
+      if (nev > 0) w.Zs[k].resize((size_t)n * nevs[k]);
+      else w.Z[k].resize((size_t)n * n);
       w.Y[k].resize((size_t)n * n);
       double *Xb = Xall.p + (size_t)k * nmax * nmax, *Fk = Fb.p + (size_t)k * nmax * nmax, *Tk = T1.p + (size_t)k * nmax * nmax;
       Xptr[k] = Xb;
@@ -1265,7 +1354,8 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
       g.sym = 0;
       g.tA = 0;
       g.A = Xb;
-      g.B = w.Z[k].p;
+      g.B = nev > 0 ? w.Zs[k].p : w.Z[k].p;
+      g.N = nevs[k];
       g.C = dBlockBuf + (size_t)ib * slot;
       gt[2 * nb + k] = g;
       g.A = w.Y[k].p;
@@ -1315,7 +1405,7 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
       gemm_tasklist_dev(ctx, w.gtasks.p + nb, nb, nm, nm, low);
       gemm_mirror_lower_dev(ctx, w.gtasks.p + nb, nb, nm);  // the tridiagonalisation sweeps the full square
     }
-    eig_sym_batch(ctx, w, nb, ns.data(), Xptr);
+    eig_sym_batch(ctx, w, nb, ns.data(), Xptr, nev > 0 ? nevs.data() : nullptr);
     {
       ProfScope ps(ctx, "eig_backtransform");
       // the eigenvalues are final: their copy into the slots goes ahead of the last product, not behind it
@@ -1325,15 +1415,18 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
       for (int k = 0; k < nb; k++) {
         const int ib = mine[c0 + k] % nblk;
         double *slotp = dBlockBufs[mine[c0 + k] / nblk] + (size_t)ib * slot;
-        csrc.push_back(w.d[k].p);
+        csrc.push_back(nev > 0 ? w.Ws[k].p : w.d[k].p);
         cdst.push_back(slotp + nmax * nmax);
-        cn.push_back(ns[k]);
+        cn.push_back(nevs[k]);
       }
       copy_slices(s, csrc, cdst, cn);
       {
         ProfScope pp3(ctx, "eig_products");
         const GemmTask *last = w.gtasks.p + (w.folded ? 3 : 2) * (size_t)nb;
-        gemm_tasklist_dev(ctx, last, nb, nm, nm, w.full_how);  // (split2: the block slots were zeroed above)
+        if (nev > 0)  // n x nev products: small tiles, no split
+          gemm_tasklist_dev(ctx, last, nb, nm, *std::max_element(nevs.begin(), nevs.end()), {GemmTile::T64});
+        else
+          gemm_tasklist_dev(ctx, last, nb, nm, nm, w.full_how);  // (split2: the block slots were zeroed above)
       }
     }
     check_status(ctx, w, nb);
@@ -1342,8 +1435,17 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
 }
 
 // phase 2: global sort of all eigenvalues and scatter of the block eigenvectors into C (N x N)
+static void eig_assemble_sel_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx, const double *dBlockBuf,
+                                 double *dE, double *dC, int nev);
 void eig_assemble_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
                       const double *dBlockBuf, double *dE, double *dC) {
+  eig_assemble_sel_dev(ctx, N, nblk, blk_ptr, blk_idx, dBlockBuf, dE, dC, 0);
+}
+int64_t eig_sel_count(int nblk, const int64_t *blk_ptr, int64_t nev) { return helfem::eig_sel_count(nblk, blk_ptr, nev); }
+/// nev > 0: slot ib holds the lowest min(nev, n_b) pairs of its block; the ranking runs over their K = eig_sel_count values
+/// (ties by position in block order, as over all N values), C is N x K
+static void eig_assemble_sel_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx, const double *dBlockBuf,
+                                 double *dE, double *dC, int nev) {
   EigWork &w = work_for(ctx);
   hipStream_t s = ctx->stream;
   ProfScope ps(ctx, "scatter");
@@ -1360,25 +1462,31 @@ void eig_assemble_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, con
   const size_t slot = nmax * nmax + nmax;
   DevBuf<double> &Etmp = ctx->ws[3];
   Etmp.resize(N);
+  std::vector<int64_t> koff(nblk + 1, 0);  // first of block ib's values among the K wanted ones (all of them: blk_ptr)
+  for (int ib = 0; ib < nblk; ib++) {
+    const int64_t n = blk_ptr[ib + 1] - blk_ptr[ib];
+    koff[ib + 1] = koff[ib] + (nev > 0 ? std::min<int64_t>(nev, n) : n);
+  }
+  const int K = (int)koff[nblk];
   {
     std::vector<const double *> csrc;
     std::vector<double *> cdst;
     std::vector<int> cn;
     for (int ib = 0; ib < nblk; ib++) {
       csrc.push_back(dBlockBuf + (size_t)ib * slot + nmax * nmax);
-      cdst.push_back(Etmp.p + blk_ptr[ib]);
-      cn.push_back((int)(blk_ptr[ib + 1] - blk_ptr[ib]));
+      cdst.push_back(Etmp.p + koff[ib]);
+      cn.push_back((int)(koff[ib + 1] - koff[ib]));
     }
     copy_slices(s, csrc, cdst, cn);
   }
   DevBuf<int> &rank = w.ibuf1;
   rank.resize(N + 8);
-  HFG_HIP_CHECK(hipMemsetAsync(dC, 0, sizeof(double) * (size_t)N * N, s));
-  launch_rank(ctx, Etmp.p, N, rank.p);
+  HFG_HIP_CHECK(hipMemsetAsync(dC, 0, sizeof(double) * (size_t)N * K, s));
+  launch_rank(ctx, Etmp.p, K, rank.p);
   for (int ib = 0; ib < nblk; ib++) {
-    int n = (int)(blk_ptr[ib + 1] - blk_ptr[ib]);
-    hipLaunchKernelGGL(k_scatter_cols, dim3((n + 255) / 256, n), dim3(256), 0, s, dBlockBuf + (size_t)ib * slot, n, n,
-                       drows + blk_ptr[ib], rank.p, (int)blk_ptr[ib], Etmp.p + blk_ptr[ib], N, dC, dE);
+    int n = (int)(blk_ptr[ib + 1] - blk_ptr[ib]), nc = (int)(koff[ib + 1] - koff[ib]);
+    hipLaunchKernelGGL(k_scatter_cols, dim3((n + 255) / 256, nc), dim3(256), 0, s, dBlockBuf + (size_t)ib * slot, n, nc,
+                       drows + blk_ptr[ib], rank.p, (int)koff[ib], Etmp.p + koff[ib], N, dC, dE);
   }
   HFG_HIP_CHECK(hipGetLastError());
 }
@@ -1394,6 +1502,27 @@ void eig_gsym_sub_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, i
     buf.resize(eig_block_buf_size(nblk, blk_ptr));
     eig_blocks_dev(ctx, N, dF, dS, nblk, blk_ptr, blk_idx, buf.p);
     eig_assemble_dev(ctx, N, nblk, blk_ptr, blk_idx, buf.p, dE, dC);
+  } catch (...) {
+    ctx->shard_rank = save_rank;
+    ctx->shard_n = save_n;
+    throw;
+  }
+  ctx->shard_rank = save_rank;
+  ctx->shard_n = save_n;
+}
+
+// the lowest min(nev, n_b) eigenpairs of every block on one device: E (K = eig_sel_count values, ascending), C (N x K)
+void eig_gsym_sub_sel_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
+                          const int64_t *blk_idx, int nev, double *dE, double *dC) {
+  if (nev < 1) throw std::logic_error("eig_gsym_sub_sel: nev must be at least 1\n");
+  int save_rank = ctx->shard_rank, save_n = ctx->shard_n;
+  ctx->shard_rank = 0;
+  ctx->shard_n = 1;
+  try {
+    DevBuf<double> &buf = ctx->ws[6];
+    buf.resize(eig_block_buf_size(nblk, blk_ptr));
+    eig_blocks_multi_dev(ctx, N, 1, &dF, dS, nblk, blk_ptr, blk_idx, &buf.p, nev);
+    eig_assemble_sel_dev(ctx, N, nblk, blk_ptr, blk_idx, buf.p, dE, dC, nev);
   } catch (...) {
     ctx->shard_rank = save_rank;
     ctx->shard_n = save_n;

@@ -80,12 +80,21 @@ void eig_assemble_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, con
                       double *dE, double *dC);  // eig.hip
 void eig_block_supports(hfg_ctx *ctx, int N, const double *dS, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
                         std::vector<int64_t> &cols);  // eig.hip
+// the lowest min(nev, n_b) eigenpairs of every block (hfg_eig_sym_sel, hfg_eig_gsym_sub_sel): E has K = eig_sel_count values, C K columns
+int64_t eig_sel_count(int nblk, const int64_t *blk_ptr, int64_t nev);  // eig.hip
+void eig_sym_sel_dev(hfg_ctx *ctx, int n, const double *dA, int nev, double *dE, double *dC);  // eig.hip
+void eig_gsym_sub_sel_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
+                          const int64_t *blk_idx, int nev, double *dE, double *dC);  // eig.hip
 void eig_release(hfg_ctx *ctx);  // eig.hip
 
-// dc.hip, trd.hip, trdp.hip: the stages of the eigensolver
+// dc.hip, stsel.hip, trd.hip, trdp.hip: the stages of the eigensolver
 void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, double *const *e, double *const *Z);  // dc.hip
 int dc_status(hfg_ctx *ctx);  // dc.hip
+int *dc_status_word(hfg_ctx *ctx);  // dc.hip
 void dc_release(hfg_ctx *ctx);  // dc.hip
+void tridiag_sel_batch(hfg_ctx *ctx, int nblk, const int *ns, const int *nev, double *const *d, double *const *e, double *const *W,
+                       double *const *Z);  // stsel.hip
+void stsel_release(hfg_ctx *ctx);  // stsel.hip
 void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *A, double *const *d, double *const *e,
                           double *const *tau);  // trd.hip
 void trd_measure_gemv(hfg_ctx *ctx, double *ms, int64_t *launches);  // trd.hip

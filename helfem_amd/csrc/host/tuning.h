@@ -7,6 +7,7 @@
 namespace helfem {
 constexpr int EXL_GMAX = 16;  // factor groups (residual factorisations) of the low-rank exchange at most
 enum class TrdMode { persistent, chain, twokernel, unblocked };
+enum class EigSel { crossover, stein, dc };
 // X(field, type, default, variable, LIVE, kind, value from the variable's text e, meaning)
 // kinds: "off if 0" = on unless atoi gives 0 (so empty or a word is off); "=w" = on when the text is exactly w; "int" = atoi
 // of the text; "present" = on when set to anything, the empty string included; "path" = the text (empty: unset)
@@ -49,6 +50,7 @@ enum class TrdMode { persistent, chain, twokernel, unblocked };
   X(tridiag_ql, bool, false, "HELFEM_TRIDIAG", false, "=ql", !strcmp(e, "ql"), "one-lane implicit QL for the tridiagonal problem instead of divide and conquer (checker)") \
   X(dc_gemm_small, bool, false, "HELFEM_DC_GEMM", false, "=small", !strcmp(e, "small"), "Q U of the divide-and-conquer merges by the first 64 x 64 kernel instead of the tile engine (checker)") \
   X(dc_levels, bool, false, "HELFEM_DC", false, "=levels", !strcmp(e, "levels"), "divide-and-conquer merges with the gather, scatter and copy-back passes over Q and ten launches per level (checker of the column-mapped product)") \
+  X(eigsel, EigSel, EigSel::crossover, "HELFEM_EIGSEL", false, "word", !strcmp(e, "stein") ? EigSel::stein : !strcmp(e, "dc") ? EigSel::dc : EigSel::crossover, "selected eigenpairs (hfg_eig_*_sel): stein = multisection and inverse iteration always; dc = the full divide and conquer, then the lowest columns (checker); unset or any other word = the crossover, which sends every wanted fraction to dc (measured: stein is slower down to 1/64 of the columns)") \
   X(dc_dbg, bool, false, "HELFEM_DC_DBG", false, "present", true, "merge statistics of divide and conquer on stderr") \
   X(bt_column, bool, false, "HELFEM_BT", false, "=column", !strcmp(e, "column"), "back-transformation reflector by reflector instead of compact WY (checker)") \
   X(bt_fold, bool, true, "HELFEM_BT_FOLD", false, "off if 0", atoi(e) != 0, "X Q formed on the side stream beside divide and conquer; off: Z <- Q Z on the main stream behind it") \

@@ -273,6 +273,20 @@ int hfg_eig_gsym_sub_pair(hfg_ctx *ctx, int64_t N, const double *Fa, const doubl
                           const int64_t *blk_ptr, const int64_t *blk_idx, double *Ea, double *Ca, double *Eb, double *Cb);
 /* arma::eig_sym(E,C,A) as used by utils::invh                         libhelfem/src/utils.cpp:172 */
 int hfg_eig_sym(hfg_ctx *ctx, int64_t n, const double *A, double *E, double *C);
+/* Selected eigenpairs: from every symmetry block the lowest min(nev, n_b) eigenpairs (LAPACK users: dsyevx / dsygvx with
+ * range = 'I'; the reference has no counterpart, it reaches LAPACK through arma::eig_sym on a submatrix only).
+ * K = hfg_eig_sel_count() pairs come back: E ascending over all of them, ties between blocks ordered as hfg_eig_gsym_sub
+ * orders them; column j of C (N x K, column-major) belongs to E[j], is S-orthonormal and zero outside its block's rows.
+ * nev >= the largest block gives the eigenvalues of hfg_eig_gsym_sub; nev < 1 is an error (status 1).
+ * Aufbau property, by construction: the globally lowest m <= nev values of the full spectrum are the first m returned (a
+ * block holds at most m of them, and its lowest nev are all here), which is why an SCF caller may pass nev = nocc + nvirt.
+ * HELFEM_EIGSEL = stein | dc forces the tridiagonal stage's path (multisection and inverse iteration | the full divide and
+ * conquer followed by taking the lowest columns); unset, a crossover on the wanted fraction chooses per call. */
+int64_t hfg_eig_sel_count(int nblk, const int64_t *blk_ptr, int64_t nev); /* K; needs no device */
+/* one dense matrix: E (min(nev, n) values), C (n x min(nev, n)) */
+int hfg_eig_sym_sel(hfg_ctx *ctx, int64_t n, const double *A, int64_t nev, double *E, double *C);
+int hfg_eig_gsym_sub_sel(hfg_ctx *ctx, int64_t N, const double *F, const double *Sinvh, int nblk, const int64_t *blk_ptr,
+                         const int64_t *blk_idx, int64_t nev, double *E /* K */, double *C /* N x K */);
 /* arma::mat TwoDBasis::Sinvh(bool chol, int sym) -> block-structured S^{-1/2}   basis.cpp:627 */
 int hfg_form_sinvh(hfg_ctx *ctx, int64_t N, const double *S, int chol, int nblk, const int64_t *blk_ptr,
                    const int64_t *blk_idx, double *Sinvh);
@@ -307,6 +321,9 @@ int hfg_fock_finish_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const
                         double *dF);
 int hfg_eig_gsym_sub_dev(hfg_ctx *ctx, int64_t N, const double *dF, const double *dSinvh, int nblk,
                          const int64_t *blk_ptr, const int64_t *blk_idx, double *dE, double *dC);
+/* hfg_eig_gsym_sub_sel on device pointers (blk_ptr and blk_idx stay host pointers); one device, whatever the shard */
+int hfg_eig_gsym_sub_sel_dev(hfg_ctx *ctx, int64_t N, const double *dF, const double *dSinvh, int nblk, const int64_t *blk_ptr,
+                             const int64_t *blk_idx, int64_t nev, double *dE /* K */, double *dC /* N x K */);
 /* Multi-GPU form of eig_gsym_sub: symmetry blocks are independent (scf_helpers.cpp:148-175), block ib is
  * solved by rank ib % nranks into a buffer of hfg_eig_block_buf_size() doubles (other slots zero); after a
  * sum all-reduce of that buffer every rank calls hfg_eig_assemble_dev() for the global sort (:183-185). */

@@ -330,6 +330,25 @@ void eig_gsym_sub(const Context &ctx, Vec &E, Mat &C, const Mat &F, const Mat &S
   check(hfg_eig_gsym_sub(ctx.handle(), (int64_t)N, detail::data_of(F, 0), detail::data_of(Sinvh, 0), (int)m_idx.size(), ptr.data(), idx.data(),
                          detail::data_of(E, 0), detail::data_of(C, 0)));
 }
+/// the lowest min(nev, block size) eigenpairs of every symmetry block, sorted globally (hfg_eig_gsym_sub_sel; no reference
+/// counterpart): E has K = hfg_eig_sel_count values, C is N x K.  The lowest m <= nev levels of the full problem are the
+/// first m returned, so an SCF loop may ask for nev = nocc + nvirt.  Throws std::logic_error for nev < 1.
+template <class Vec, class Mat, class UVec>
+void eig_gsym_sub_sel(const Context &ctx, Vec &E, Mat &C, const Mat &F, const Mat &Sinvh, const std::vector<UVec> &m_idx, size_t nev) {
+  const size_t N = F.n_rows;
+  if ((size_t)F.n_cols != N || (size_t)Sinvh.n_rows != N || (size_t)Sinvh.n_cols != N) throw std::logic_error("eig_gsym_sub_sel: incompatible dimensions\n");
+  if (nev < 1) throw std::logic_error("eig_gsym_sub_sel: nev must be at least 1\n");
+  std::vector<int64_t> ptr(1, 0), idx;
+  for (const UVec &b : m_idx) {
+    for (size_t k = 0; k < detail::len_of(b, 0); k++) idx.push_back((int64_t)detail::data_of(b, 0)[k]);
+    ptr.push_back((int64_t)idx.size());
+  }
+  const size_t K = (size_t)hfg_eig_sel_count((int)m_idx.size(), ptr.data(), (int64_t)nev);
+  detail::set_len(E, K, 0);
+  C = Mat(N, K);
+  check(hfg_eig_gsym_sub_sel(ctx.handle(), (int64_t)N, detail::data_of(F, 0), detail::data_of(Sinvh, 0), (int)m_idx.size(), ptr.data(), idx.data(),
+                             (int64_t)nev, detail::data_of(E, 0), detail::data_of(C, 0)));
+}
 /// the two eig_gsym_sub calls of an unrestricted iteration (diatomic/main.cpp:936-958) as one batch on the device
 /// (hfg_eig_gsym_sub_pair): in the reference's loop, replace
 ///     scf::eig_gsym_sub(Ea,Ca,Fa,Sinvh,dsym); ... scf::eig_gsym_sub(Eb,Cb,Fb,Sinvh,dsym);
