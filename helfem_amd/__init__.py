@@ -117,6 +117,10 @@ def lib():
         L.hfg_erfc_phi.restype = ctypes.c_double
         L.hfg_erfc_phi.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double]
         L.hfg_compute_rs_tei.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
+        L.hfg_compute_rs_tei_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
+        L.hfg_rs_special_dev.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int64, c_double_p]
+        L.hfg_set_erfc_binomial_mode.restype = None
+        L.hfg_set_erfc_binomial_mode.argtypes = [ctypes.c_int]
         L.hfg_model_potential.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(hfg_model_pot),
                                           ctypes.POINTER(hfg_model_pot), c_double_p]
         L.hfg_chebyshev_rule.restype = None
@@ -497,15 +501,26 @@ class AtomicTwoDBasis(TwoDBasis):
         _check(f(self.h, self.RADIAL_TABLES[name], int(iel), _p(out), ctypes.byref(r), ctypes.byref(c)))
         return out[:, 0] if name == "r" else out
 
-    def compute_yukawa(self, lam):
-        """TwoDBasis::compute_yukawa (src/atomic/TwoDBasis.cpp:741): tables of exp(-lambda r12)/r12 (host)"""
-        _check(lib().hfg_compute_rs_tei(self.h, 1, float(lam)))
+    def _compute_rs(self, kind, omega, device, ctx):
+        if device:
+            ctx = ctx or self.ctx
+            if ctx is None:
+                raise ValueError("device=True needs a context (ctx=... here or at construction)")
+            self.ctx = ctx
+            _check(lib().hfg_compute_rs_tei_dev(ctx.h, self.h, kind, float(omega)))
+        else:
+            _check(lib().hfg_compute_rs_tei(self.h, kind, float(omega)))
         self._uploaded = None
 
-    def compute_erfc(self, mu):
-        """TwoDBasis::compute_erfc (src/atomic/TwoDBasis.cpp:780): tables of erfc(mu r12)/r12 (host)"""
-        _check(lib().hfg_compute_rs_tei(self.h, 2, float(mu)))
-        self._uploaded = None
+    def compute_yukawa(self, lam, device=False, ctx=None):
+        """TwoDBasis::compute_yukawa (src/atomic/TwoDBasis.cpp:741): tables of exp(-lambda r12)/r12, on the host or,
+        device=True, on the GPU of ctx (hfg_compute_rs_tei_dev)"""
+        self._compute_rs(1, lam, device, ctx)
+
+    def compute_erfc(self, mu, device=False, ctx=None):
+        """TwoDBasis::compute_erfc (src/atomic/TwoDBasis.cpp:780): tables of erfc(mu r12)/r12, on the host or,
+        device=True, on the GPU of ctx (hfg_compute_rs_tei_dev)"""
+        self._compute_rs(2, mu, device, ctx)
 
     def rs_exchange(self, P):
         """TwoDBasis::rs_exchange (src/atomic/TwoDBasis.cpp:1142) on the GPU"""
@@ -750,6 +765,21 @@ def bessel_kl(x, L):
 
 def erfc_phi(n, Xi, xi):
     return lib().hfg_erfc_phi(int(n), float(Xi), float(xi))
+
+
+def set_erfc_binomial_mode(mode):
+    """binomials of the short-range series of Phi_L: 0 exact (default), 1 the reference's helper"""
+    lib().hfg_set_erfc_binomial_mode(int(mode))
+
+
+def rs_special_dev(which, L, a, b=None, ctx=None):
+    """the device versions of bessel_il (which 0), bessel_kl (1) and erfc_phi (2, b = xi) at the points a (hfg_rs_special_dev)"""
+    ctx = ctx or default_context()
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(a if b is None else b, dtype=np.float64)
+    out = np.zeros_like(a)
+    _check(lib().hfg_rs_special_dev(ctx.h, int(which), int(L), _p(a), _p(b), a.size, _p(out)))
+    return out
 
 
 def theta_lm(l, m, cth):

@@ -360,8 +360,24 @@ int hfg_compute_rs_tei(hfg_basis *b, int rs_kind, double omega) {
   if (rs_kind == 1) b->ab.compute_yukawa(omega);
   else if (rs_kind == 2) b->ab.compute_erfc(omega);
   else throw std::logic_error("unknown range-separation kernel (1 = Yukawa, 2 = erfc)\n");
+  b->rs_on_device = false;
   HFG_CATCH
 }
+
+int hfg_compute_rs_tei_dev(hfg_ctx *ctx, hfg_basis *b, int rs_kind, double omega) {
+  HFG_TRY compute_rs_tei_dev(ctx, b, rs_kind, omega);  // hip/rs_tei_dev.hip
+  HFG_CATCH
+}
+
+int hfg_rs_special_dev(hfg_ctx *ctx, int which, int L, const double *a, const double *b, int64_t n, double *out) {
+  HFG_TRY
+  if (!ctx) throw std::logic_error("hfg_rs_special_dev: a context is needed\n");
+  if (n < 0 || (n && (!a || !out || (which == 2 && !b)))) throw std::logic_error("hfg_rs_special_dev: missing arguments\n");
+  rs_special_dev(ctx, which, L, a, b, (size_t)n, out);
+  HFG_CATCH
+}
+
+void hfg_set_erfc_binomial_mode(int mode) { helfem::set_erfc_binomial_mode(mode); }
 
 int hfg_compute_tei_dev(hfg_ctx *ctx, hfg_basis *b, int exchange) {
   HFG_TRY
@@ -403,6 +419,39 @@ int hfg_basis_get_prim(hfg_ctx *ctx, const hfg_basis *b, int which, int ilm, int
     const size_t E = B.Nel(), NL = (size_t)B.N_L();
     if (which != 4 && !(which >= 12 && which <= 15) && ((which != 0 && which != 8 && which != 10) || ilm < 0 || (size_t)ilm >= NL || iel < 0 || (size_t)iel >= E))
       throw std::logic_error("hfg_basis_get_prim: index out of range\n");
+    if (which >= 12 && which <= 15 && b->rs_on_device) {
+      // built by hfg_compute_rs_tei_dev: read back from the padded device layout (hip/tables.h) and unpadded; 15 is the
+      // exchange-ordered permutation of 14 (utils::exchange_tei), formed here
+      if (!ctx) throw std::logic_error("hfg_basis_get_prim: the tables live on the device, a context is needed\n");
+      const bool pairs = which >= 14 && B.rs_kind == 2;
+      if ((which < 14 && B.rs_kind != 1) || ilm < 0 || (size_t)ilm >= NL || iel < 0 || (size_t)iel >= (pairs ? E * E : E))
+        throw std::logic_error("hfg_basis_get_prim: index out of range\n");
+      const size_t e = pairs ? (size_t)iel / E : (size_t)iel, f = pairs ? (size_t)iel % E : (size_t)iel;
+      const size_t p = B.max_Nprim(), pp = p * p, Ni = B.fem.nprim(e), Nf = B.fem.nprim(f), lo = e == 0, lof = f == 0;
+      // (exchange_tei: ktei(k Ni + j, l Ni + i) = tei(j Ni + i, l Nf + k), Nf Ni x Nf Ni)
+      *rows = (int64_t)(which < 14 ? Ni : which == 15 ? Nf * Ni : Ni * Ni);
+      *cols = (int64_t)(which < 14 ? Ni : which == 15 ? Nf * Ni : Nf * Nf);
+      if (!out) return 0;
+      HFG_HIP_CHECK(hipSetDevice(ctx->device));
+      HFG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      if (which < 14) {
+        std::vector<double> pad(pp);
+        HFG_HIP_CHECK(hipMemcpy(pad.data(), b->dev_rs_disj.p + (((size_t)(which - 12) * NL + ilm) * E + e) * pp, sizeof(double) * pp, hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < Ni; j++)
+          for (size_t i = 0; i < Ni; i++) out[j * Ni + i] = pad[(j + lo) * p + i + lo];
+        return 0;
+      }
+      std::vector<double> pad(pp * pp);
+      HFG_HIP_CHECK(hipMemcpy(pad.data(), b->dev_rs_tei.p + ((size_t)ilm * (pairs ? E * E : E) + iel) * pp * pp, sizeof(double) * pp * pp, hipMemcpyDeviceToHost));
+      helfem::Mat m(Ni * Ni, Nf * Nf);
+      for (size_t cj = 0; cj < Nf; cj++)
+        for (size_t ci = 0; ci < Nf; ci++)
+          for (size_t rj = 0; rj < Ni; rj++)
+            for (size_t ri = 0; ri < Ni; ri++) m(rj * Ni + ri, cj * Nf + ci) = pad[((cj + lof) * p + ci + lof) * pp + (rj + lo) * p + ri + lo];
+      if (which == 15) m = helfem::diatomic::exchange_tei(m, Ni, Ni, Nf, Nf);
+      std::copy(m.d.begin(), m.d.end(), out);
+      return 0;
+    }
     if (which == 4 || (which >= 12 && which <= 15)) {
       // 4 = prim_ktei[L] (host tables); range-separated tables of compute_yukawa / compute_erfc (TwoDBasis.cpp:741-815):
       // 12 = disjoint_iL, 13 = disjoint_kL, 14 = rs_tei, 15 = rs_ktei -- Yukawa: one table per (L, iel); erfc: one per

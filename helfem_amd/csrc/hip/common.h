@@ -128,6 +128,10 @@ struct hfg_basis {
   // primitive in-element integral tables built on the device (hip/tei_dev.hip) instead of host Mats
   hfg::DevBuf<double> dev_tei;
   bool tei_on_device = false;
+  // range-separated tables built on the device (hip/rs_tei_dev.hip) in the padded layout of dev_rs: tei[L][e][c][r] and
+  // disj[t][L][e][j][i] (Yukawa), tei[L][e][f][c][r] (erfc); the host then holds ab.rs_kind and ab.rs_lambda only
+  hfg::DevBuf<double> dev_rs_tei, dev_rs_disj;
+  bool rs_on_device = false;
 
   size_t Nbf() const { return kind ? ab.Nbf() : b.Nbf(); }
   size_t Ndummy() const { return kind ? ab.Nbf() : b.Ndummy(); }

@@ -65,6 +65,10 @@ void exchange_lr_release(hfg_dev_tables *t);  // exchange_lr.hip
 // tei_dev.hip
 void compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis);  // tei_dev.hip
 
+// rs_tei_dev.hip
+void compute_rs_tei_dev(hfg_ctx *ctx, hfg_basis *basis, int rs_kind, double omega);  // rs_tei_dev.hip
+void rs_special_dev(hfg_ctx *ctx, int which, int L, const double *a, const double *b, size_t n, double *out);  // rs_tei_dev.hip
+
 // eig.hip
 void eig_sym_dev(hfg_ctx *ctx, int n, const double *dA, double *dE, double *dC);  // eig.hip
 void eig_gsym_dev(hfg_ctx *ctx, int N, int n, const double *dF, const double *dS, double *dE, double *dC);  // eig.hip

@@ -537,8 +537,12 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
       compute_tei_dev(ctx, hb);  // in-element tables on the device (tei_dev.hip)
     if (opt.omega != 0.0) {  // atomic/main.cpp:709-712
       if (!hb->kind) throw std::logic_error("Range separated functionals are not supported.\n");
-      if (opt.rs_kind == 1) hb->ab.compute_yukawa(opt.omega);
-      else hb->ab.compute_erfc(opt.omega);
+      if (tuning().rs_tei == helfem::RsTei::dev) compute_rs_tei_dev(ctx, hb, opt.rs_kind, opt.omega);  // rs_tei_dev.hip
+      else {
+        if (opt.rs_kind == 1) hb->ab.compute_yukawa(opt.omega);
+        else hb->ab.compute_erfc(opt.omega);
+        hb->rs_on_device = false;
+      }
     }
     if (hb->dev) {
       fock_release(hb->dev);

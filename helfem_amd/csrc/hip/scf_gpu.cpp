@@ -47,6 +47,8 @@ struct GPUBackend : public helfem::scf::Backend {
     hb = new hfg_basis();
     hb->kind = 1;
     hb->ab = basis;
+    // HELFEM_RS_TEI=dev: the driver has named the kernel and left the tables to the device (host/scf.cpp run_atomic)
+    if (hb->ab.rs_kind && hb->ab.rs_tei.empty()) chk(hfg_compute_rs_tei_dev(ctx, hb, hb->ab.rs_kind, hb->ab.rs_lambda));
     chk(hfg_basis_upload(ctx, hb, ldft, mdft));
   }
   Mat coulomb(const Mat &P) override {

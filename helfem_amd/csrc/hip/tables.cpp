@@ -194,7 +194,9 @@ void upload_rs_tables(hfg_ctx *ctx, hfg_basis *basis) {
 
 static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_dev_tables *t, int ldft, int mdft) {
   hipStream_t s = ctx->stream;
-  const bool use_dev_tei = basis->tei_on_device && !b.rs_kind;
+  // tables already in this layout on the device: the Coulomb set of tei_dev.hip, the range-separated set of rs_tei_dev.hip
+  const bool use_dev_tei = b.rs_kind ? basis->rs_on_device : basis->tei_on_device;
+  const hfg::DevBuf<double> &dev_tei = b.rs_kind ? basis->dev_rs_tei : basis->dev_tei;
   t->rs_kind = b.rs_kind;
   t->pair_tei = b.pair_tei;
 
@@ -314,7 +316,13 @@ static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_
   const int Ntab = b.Ntab;
   {
     const size_t pp = (size_t)p * p;
-    std::vector<double> disj(std::max<size_t>((size_t)b.ndt * Ntab * E * pp, 1), 0.0);
+    const size_t ndisj = (size_t)b.ndt * Ntab * E * pp;
+    std::vector<double> disj(std::max<size_t>(ndisj, 1), 0.0);
+    if (b.rs_kind && use_dev_tei) {
+      if (basis->dev_rs_disj.n < ndisj) throw std::logic_error("device disjoint buffer has the wrong size");
+      t->disj.resize(disj.size());
+      if (ndisj) HFG_HIP_CHECK(hipMemcpyAsync(t->disj.p, basis->dev_rs_disj.p, sizeof(double) * ndisj, hipMemcpyDeviceToDevice, s));
+    } else {
     for (int tt = 0; tt < b.ndt; tt++)
       for (int tab = 0; tab < Ntab; tab++)
         for (int e = 0; e < E; e++) {
@@ -329,6 +337,7 @@ static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_
             }
         }
     t->disj.upload(disj, s);
+    }
     HFG_HIP_CHECK(hipStreamSynchronize(s));
   }
   {
@@ -337,8 +346,8 @@ static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_
     const int nper = b.pair_tei ? E * E : E;  // blocks per (type, slot)
     t->tei.resize((size_t)b.ntt * Ntab * nper * blk);
     if (use_dev_tei) {
-      if (basis->dev_tei.n < (size_t)b.ntt * Ntab * E * blk) throw std::logic_error("device tei buffer has the wrong size");
-      HFG_HIP_CHECK(hipMemcpyAsync(t->tei.p, basis->dev_tei.p, sizeof(double) * (size_t)b.ntt * Ntab * E * blk,
+      if (dev_tei.n < (size_t)b.ntt * Ntab * nper * blk) throw std::logic_error("device tei buffer has the wrong size");
+      HFG_HIP_CHECK(hipMemcpyAsync(t->tei.p, dev_tei.p, sizeof(double) * (size_t)b.ntt * Ntab * nper * blk,
                                    hipMemcpyDeviceToDevice, s));
       HFG_HIP_CHECK(hipStreamSynchronize(s));
     }

@@ -2,6 +2,7 @@
 #include <cfloat>
 #include <climits>
 #include "diis.h"
+#include "tuning.h"
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -810,7 +811,10 @@ Result run_atomic(const AtomicOptions &aopt, Backend &be) {
   pb.compute_tei_and_prepare = [&]() {
     basis.compute_tei(opt.kfrac != 0.0);
     if (opt.omega != 0.0) {  // atomic/main.cpp:709-712
-      if (opt.rs_kind == 1) basis.compute_yukawa(opt.omega);
+      if (tuning().rs_tei == RsTei::dev) {  // the backend builds the tables on its device (prepare_atomic)
+        basis.rs_kind = opt.rs_kind;
+        basis.rs_lambda = opt.omega;
+      } else if (opt.rs_kind == 1) basis.compute_yukawa(opt.omega);
       else basis.compute_erfc(opt.omega);
     }
     be.prepare_atomic(basis, opt.kfrac != 0.0, ldft, mdft);

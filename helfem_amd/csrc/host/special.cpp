@@ -432,6 +432,7 @@ double erfc_Phi_short(int n, double Xi, double xi) {
 }  // namespace
 
 void set_erfc_binomial_mode(int mode) { g_erfc_binomial_mode = mode; }
+int get_erfc_binomial_mode() { return g_erfc_binomial_mode; }
 
 double erfc_Phi(int n, double Xi, double xi) {
   if (n < 0) throw std::logic_error("erfc_Phi: negative order");

@@ -70,6 +70,7 @@ double erfc_Phi(int n, double Xi, double xi);
 /// which puts relative errors of up to 1e-5 into the short-range series; mode 1 reproduces that helper so the tests
 /// can measure what it does to integrals and energies.  Default 0 = exact binomials.  The product never sets it.
 void set_erfc_binomial_mode(int mode);
+int get_erfc_binomial_mode();
 
 /// Angular product rule: cos(theta) Chebyshev nodes (ltheta of them) x nphi uniform phi
 void angular_chebyshev(int ltheta, int nphi, Vec &cth, Vec &phi, Vec &w);

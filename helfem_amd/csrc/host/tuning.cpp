@@ -20,6 +20,7 @@ Tuning tuning_live() { return parse(tuning(), true); }
 static std::string show(bool v) { return v ? "on" : "off"; }
 static std::string show(const std::string &v) { return v; }
 static std::string show(TrdMode v) { return v == TrdMode::persistent ? "persistent" : v == TrdMode::chain ? "chain" : v == TrdMode::twokernel ? "twokernel" : "unblocked"; }
+static std::string show(RsTei v) { return v == RsTei::dev ? "dev" : "host"; }
 static std::string show(EigSel v) { return v == EigSel::stein ? "stein" : v == EigSel::dc ? "dc" : "crossover"; }
 template <class T> static std::string show(T v) { return std::to_string(v); }
 std::string tuning_table() {

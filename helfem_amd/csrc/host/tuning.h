@@ -8,12 +8,14 @@ namespace helfem {
 constexpr int EXL_GMAX = 16;  // factor groups (residual factorisations) of the low-rank exchange at most
 enum class TrdMode { persistent, chain, twokernel, unblocked };
 enum class EigSel { crossover, stein, dc };
+enum class RsTei { host, dev };
 // X(field, type, default, variable, LIVE, kind, value from the variable's text e, meaning)
 // kinds: "off if 0" = on unless atoi gives 0 (so empty or a word is off); "=w" = on when the text is exactly w; "int" = atoi
 // of the text; "present" = on when set to anything, the empty string included; "path" = the text (empty: unset)
 #define HELFEM_TUNING(X) \
   X(scf_host, bool, false, "HELFEM_SCF", true, "=host", !strcmp(e, "host"), "SCF loop driven from the host through the per-stage entry points (checker of the device-resident loop)") \
   X(tei_host, bool, false, "HELFEM_TEI", false, "=host", !strcmp(e, "host"), "in-element tables built by the threaded host code and uploaded (checker of tei_dev.hip)") \
+  X(rs_tei, RsTei, RsTei::host, "HELFEM_RS_TEI", false, "word", !strcmp(e, "dev") ? RsTei::dev : RsTei::host, "range-separated exchange tables of the SCF drivers: dev = built on the device (rs_tei_dev.hip); unset or any other word = built by the threaded host code and uploaded") \
   X(exchange_general, bool, false, "HELFEM_EXCHANGE", true, "=general", !strcmp(e, "general"), "general exchange kernels always, not only where the low-rank fast path declines") \
   X(exl_rb, int, 0, "HELFEM_EXL_RB", false, "int", atoi(e), "RB kernel of the low-rank exchange: 4 the 4 x 4 vector kernel, 1 the one-pair vector kernel (checkers), else the matrix-core kernel k_exl_RBm") \
   X(exl_mgroups, bool, true, "HELFEM_EXL_MGROUPS", false, "off if 0", atoi(e) != 0, "cross-element products by blocks of equal m; off: the full products") \

@@ -143,6 +143,10 @@ int hfg_compute_tei(hfg_basis *basis, int exchange);
  * then also places the screened-kernel tables in HBM.  A diatomic basis fails like the reference driver
  * ("Range separated functionals are not supported.", src/diatomic/main.cpp:393). */
 int hfg_compute_rs_tei(hfg_basis *basis, int rs_kind, double omega);
+/* the same range-separated tables built on the GPU: the Bessel / Phi_L weights are evaluated and summed on the device and the
+ * tables stay there in the layout hfg_basis_upload uses; the host keeps rs_kind and omega.  Follow with hfg_basis_upload.
+ * hfg_basis_get_prim (12-15) reads them back through ctx.  Same refusal of a diatomic basis as hfg_compute_rs_tei. */
+int hfg_compute_rs_tei_dev(hfg_ctx *ctx, hfg_basis *basis, int rs_kind, double omega);
 /* the same tables built on the GPU (diatomic: host computes quadrature points and Legendre values, the
  * O(Nlm nq p^4) sums run on the device and the tables stay there); follow with hfg_basis_upload */
 int hfg_compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis, int exchange);
@@ -160,7 +164,8 @@ int hfg_diis_weights(int n, const double *B, const double *T, const double *E, d
  *   element iel, column-major in the reference's shape (rows/cols returned; out may be NULL to query the shape).  Tables built
  *   by hfg_compute_tei_dev are copied back from the device (ctx required).  Atomic handles: ilm = L; which 0 prim_tei[L],
  *   4 prim_ktei[L], 8 disjoint_L, 10 disjoint_m1L, and after hfg_compute_rs_tei 12 disjoint_iL, 13 disjoint_kL, 14 rs_tei,
- *   15 rs_ktei (erfc tables, one per element pair: iel * Nel + kel in place of iel). */
+ *   15 rs_ktei (erfc tables, one per element pair: iel * Nel + kel in place of iel); after hfg_compute_rs_tei_dev these four are
+ *   copied back from the device (ctx required). */
 /* arma::mat TwoDBasis::overlap(const TwoDBasis &rh)   basis.cpp:713 and atomic/TwoDBasis.cpp:330: interbasis overlap
  * <a|b>, Nbf(a) x Nbf(b), of two bases of the same program (the projection of a checkpoint's orbitals onto another
  * basis, --load) */
@@ -180,6 +185,12 @@ double hfg_theta_lm(int l, int m, double cth);                                  
 double hfg_bessel_il(double x, int L);              /* utils::bessel_il, libhelfem/src/utils.cpp:47 */
 double hfg_bessel_kl(double x, int L);              /* utils::bessel_kl, libhelfem/src/utils.cpp:59 */
 double hfg_erfc_phi(int n, double Xi, double xi);   /* atomic::erfc_expn::Phi, libhelfem/src/erfc_expn.cpp:181 */
+/* binomials of the short-range series of Phi: 0 exact (default), 1 the helper of erfc_expn.cpp:46-70 (the reference's
+ * arithmetic); read by hfg_erfc_phi, hfg_compute_rs_tei and their device counterparts */
+void hfg_set_erfc_binomial_mode(int mode);
+/* the device versions of the three functions above (hip/special_dev.h), one launch: out[i] = i_L(a[i]) (which 0), k_L(a[i]) (1)
+ * or Phi_L(a[i], b[i]) (2); a, b, out are host arrays of n entries (b is read for which 2 only) */
+int hfg_rs_special_dev(hfg_ctx *ctx, int which, int L, const double *a, const double *b, int64_t n, double *out);
 void hfg_chebyshev_rule(int n, double *x, double *w);                                /* chebyshev.cpp:22 */
 void hfg_lobatto_nodes(int n, double *x);                                            /* lobatto.cpp:588 */
 

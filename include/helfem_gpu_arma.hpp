@@ -246,6 +246,15 @@ class TwoDBasis : public BasisBase<Mat> {
     check(hfg_compute_rs_tei(this->b_, 2, mu));
     this->uploaded_ = false;
   }
+  /// the same tables built on the device of the basis' context (hfg_compute_rs_tei_dev)
+  void compute_yukawa(double lambda, bool device) {
+    check(device ? hfg_compute_rs_tei_dev(this->context(), this->b_, 1, lambda) : hfg_compute_rs_tei(this->b_, 1, lambda));
+    this->uploaded_ = false;
+  }
+  void compute_erfc(double mu, bool device) {
+    check(device ? hfg_compute_rs_tei_dev(this->context(), this->b_, 2, mu) : hfg_compute_rs_tei(this->b_, 2, mu));
+    this->uploaded_ = false;
+  }
   Mat rs_exchange(const Mat &P) const { return this->two_body(hfg_rs_exchange, P, "rs_exchange"); }
 };
 }  // namespace atomic
