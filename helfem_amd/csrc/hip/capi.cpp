@@ -167,11 +167,7 @@ int hfg_ctx_destroy(hfg_ctx *c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  eig_release(c);
-  dc_release(c);
-  stsel_release(c);
-  trd_release(c);
-  trdp_release(c);
+  c->work.drop_all();
   for (auto &kv : c->prof)
     for (auto &ev : kv.second.pending) {
       (void)hipEventDestroy(ev.first);
@@ -290,17 +286,8 @@ int hfg_angular_basis(int lmax, int mmax, int *lval, int *mval, int *nang) {
 int hfg_basis_destroy(hfg_basis *b) {
   HFG_TRY
   if (!b) return 0;
-  if (b->dev) {
-    fock_release(b->dev);
-    exchange_release(b->dev);
-    exchange_lr_release(b->dev);
-    delete b->dev;
-  }
-  if (b->dev_rs) {
-    exchange_release(b->dev_rs);
-    exchange_lr_release(b->dev_rs);
-    delete b->dev_rs;
-  }
+  delete b->dev;
+  delete b->dev_rs;
   delete b;
   HFG_CATCH
 }
@@ -713,19 +700,7 @@ void hfg_lobatto_nodes(int n, double *x) {
 
 int hfg_basis_upload(hfg_ctx *ctx, hfg_basis *b, int ldft, int mdft) {
   HFG_TRY
-  if (b->dev) {
-    fock_release(b->dev);
-    exchange_release(b->dev);
-    exchange_lr_release(b->dev);
-  }
-  upload_tables(ctx, b, ldft, mdft);
-  if (b->dev_rs) {
-    exchange_release(b->dev_rs);
-    exchange_lr_release(b->dev_rs);
-    delete b->dev_rs;
-    b->dev_rs = nullptr;
-  }
-  if (b->kind == 1 && b->ab.rs_kind) upload_rs_tables(ctx, b);
+  upload_basis_tables(ctx, b, ldft, mdft, b->kind == 1 && b->ab.rs_kind);
   HFG_CATCH
 }
 

@@ -12,6 +12,7 @@
 #include "../host/atomic_basis.h"
 #include "../host/diatomic_basis.h"
 #include "../host/tuning.h"
+#include "workspace_owner.h"
 
 namespace hfg {
 using helfem::TrdMode, helfem::tuning;  // the HELFEM_* switches (host/tuning.h)
@@ -109,6 +110,7 @@ struct hfg_ctx {
   hfg::DevBuf<double> ws[8];
   double *pinned = nullptr;
   size_t pinned_bytes = 0;
+  hfg::WorkspaceOwner<hfg::WS_CTX_SLOTS> work;  // the eigensolver stages' workspaces (workspace_owner.h)
 
   void *pinned_buf(size_t bytes);
   hipEvent_t get_event();

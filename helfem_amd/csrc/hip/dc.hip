@@ -852,7 +852,7 @@ __global__ __launch_bounds__(256) void k_dgemm_tasks(const GemmTask *__restrict_
 // -------------------------------------------------------------------------------------------------
 // host driver
 // -------------------------------------------------------------------------------------------------
-struct DCWork {
+struct DCWork : Workspace {
   DevBuf<double> prep_scratch;  // work arrays of k_dc_prepare for merges too large for LDS
   DevBuf<double> d2[DC_MAXB], Qb[DC_MAXB], U[DC_MAXB], Qg[DC_MAXB], Qn[DC_MAXB];
   DevBuf<double> vec[DC_MAXB];  // 9 double vectors of length n
@@ -868,14 +868,6 @@ struct DCWork {
   std::vector<int> level_maxp;  // largest parent range of the level's nodes
   int nleaves = 0;
 };
-static std::map<hfg_ctx *, DCWork *> g_dc;
-void dc_release(hfg_ctx *ctx) {
-  auto it = g_dc.find(ctx);
-  if (it != g_dc.end()) {
-    delete it->second;
-    g_dc.erase(it);
-  }
-}
 
 static int build_tree(int blk, int lo, int hi, int depth, int plo, int phi, std::vector<std::vector<DCNode> > &byheight) {
   DCNode nd;
@@ -904,14 +896,7 @@ static int build_tree(int blk, int lo, int hi, int depth, int plo, int phi, std:
 /// d[blk] (ascending) and the eigenvectors in Z[blk] (n x n, ld n).  d, e are overwritten.
 void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, double *const *e, double *const *Z) {
   if (nblk > DC_MAXB) throw std::logic_error("tridiag_dc_batch: too many blocks");
-  DCWork *wp;
-  auto it = g_dc.find(ctx);
-  if (it == g_dc.end()) {
-    wp = new DCWork();
-    g_dc[ctx] = wp;
-  } else
-    wp = it->second;
-  DCWork &w = *wp;
+  DCWork &w = ctx->work.get<DCWork>(WS_DC);
   hipStream_t s = ctx->stream;
   std::vector<int> key(ns, ns + nblk);
   if (key != w.key) {
@@ -1070,17 +1055,16 @@ void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, d
 /// the status word that dc_status reads (4 ints), for the other solver of the tridiagonal stage (stsel.hip); the caller
 /// clears it on the stream before its kernels
 int *dc_status_word(hfg_ctx *ctx) {
-  auto it = g_dc.find(ctx);
-  if (it == g_dc.end()) it = g_dc.emplace(ctx, new DCWork()).first;
-  it->second->status.resize(4);
-  return it->second->status.p;
+  DCWork &w = ctx->work.get<DCWork>(WS_DC);
+  w.status.resize(4);
+  return w.status.p;
 }
 
 int dc_status(hfg_ctx *ctx) {
-  auto it = g_dc.find(ctx);
-  if (it == g_dc.end()) return 0;
+  const DCWork *w = ctx->work.find<DCWork>(WS_DC);
+  if (!w) return 0;
   int st = 0;
-  HFG_HIP_CHECK(hipMemcpyAsync(&st, it->second->status.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HFG_HIP_CHECK(hipMemcpyAsync(&st, w->status.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HFG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return st;
 }

@@ -627,7 +627,7 @@ __global__ __launch_bounds__(64) void k_bt_T(EigBatch b, double *const *__restri
   for (int c = 0; c < BT_KB; c++) Tp[(size_t)c * BT_KB + t] = sT[t][c];
 }
 
-struct EigWork {
+struct EigWork : Workspace {
   GemmHow full_how;  // how this batch's full products are launched (split2: two half-K workgroups per tile)
   std::vector<int64_t> asm_rows;  // eig_assemble_dev: the index list whose device copy is asm_rows_dev
   DevBuf<long long> asm_rows_dev;
@@ -653,21 +653,7 @@ struct EigWork {
   int sup_N = 0;
   std::vector<int64_t> sup_ptr, sup_idx;
 };
-static std::map<hfg_ctx *, EigWork *> g_work;
-static EigWork &work_for(hfg_ctx *ctx) {
-  auto it = g_work.find(ctx);
-  if (it != g_work.end()) return *it->second;
-  EigWork *w = new EigWork();
-  g_work[ctx] = w;
-  return *w;
-}
-void eig_release(hfg_ctx *ctx) {
-  auto it = g_work.find(ctx);
-  if (it != g_work.end()) {
-    delete it->second;
-    g_work.erase(it);
-  }
-}
+static EigWork &work_for(hfg_ctx *ctx) { return ctx->work.get<EigWork>(WS_EIG); }
 
 /// Eigen-decomposition of nblk symmetric matrices already in w.A[blk] (n x n); eigenvalues end up in
 /// w.d[blk] (unsorted), eigenvectors in w.Z[blk].
@@ -1237,11 +1223,10 @@ size_t eig_block_buf_size(int nblk, const int64_t *blk_ptr) {
 static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
                                  const int64_t *blk_idx, double *const *dBlockBufs, int nev = 0);
 static int eig_num_cus(hfg_ctx *ctx) {
-  static int ncu = 0;
-  if (!ncu) {
+  static const int ncu = [&] {  // once per process, under the guard of the static's initialisation
     hipDeviceProp_t prop;
-    ncu = (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
+    return (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+  }();
   return ncu;
 }
 void eig_blocks_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,

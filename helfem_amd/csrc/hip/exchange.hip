@@ -210,27 +210,15 @@ __global__ void k_ex_assemble(const double *__restrict__ Kc, int R, int E, int p
   }
 }
 
-struct ExAux {
+struct ExAux : Workspace {
   DevBuf<double> c0tab, c2tab, Pd, Kd, Kc, U, Rm, chan_fac;
   DevBuf<int> chanL, chanM, chan_ilm, couple, pure_idx;
   std::vector<std::vector<int> > hL, hM, hilm;
   std::vector<std::vector<double> > hfac;
   int Lp1 = 0;
 };
-static std::map<hfg_dev_tables *, ExAux *> g_ex;
 
-void exchange_release(hfg_dev_tables *t) {
-  auto it = g_ex.find(t);
-  if (it != g_ex.end()) {
-    delete it->second;
-    g_ex.erase(it);
-  }
-}
-
-static ExAux &exaux_for(hfg_ctx *ctx, hfg_dev_tables *t) {
-  auto it = g_ex.find(t);
-  if (it != g_ex.end()) return *it->second;
-  ExAux *a = new ExAux();
+static void exaux_setup(hfg_ctx *ctx, const hfg_dev_tables *t, ExAux *a) {
   const int A = t->A;
   a->Lp1 = t->Lp1;
   a->hL.resize(A);
@@ -267,10 +255,10 @@ static ExAux &exaux_for(hfg_ctx *ctx, hfg_dev_tables *t) {
   if ((int)pidx.size() != t->N) throw std::logic_error("pure index list does not match the basis size");
   a->pure_idx.upload(pidx, ctx->stream);
   HFG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  g_ex[t] = a;
-  return *a;
 }
-
+static ExAux &exaux_for(hfg_ctx *ctx, hfg_dev_tables *t) {
+  return t->work.get<ExAux>(WS_EX, [&](ExAux &a) { exaux_setup(ctx, t, &a); });
+}
 
 // rs: the range-separated kernel of TwoDBasis::rs_exchange (src/atomic/TwoDBasis.cpp:1142) through basis->dev_rs
 void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, bool rs, const double *Lknown, int rknown) {

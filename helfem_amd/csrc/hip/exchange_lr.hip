@@ -919,7 +919,7 @@ __global__ void k_exl_assemble(const double *__restrict__ Kin, const double *__r
   else K[(size_t)col * N + row] = -v;
 }
 
-struct ExLRAux {
+struct ExLRAux : Workspace {
   DevBuf<double> c0tab, c2tab, ktei, L, sgn, dinfo, Ld, V0, V2, aP, aQw, G, RB, C, Kin, Pwork, LS;
   int kM = 0, kK = 0;  // rows and columns of one exchange-ordered element table (padded, see exlr_for)
   DevBuf<int4> rbm_list;  // workgroups of k_exl_RBm: (slot, element, block pair)
@@ -945,20 +945,8 @@ struct ExLRAux {
   std::vector<int> chM0;
   int max_nch = 0;
 };
-static std::map<hfg_dev_tables *, ExLRAux *> g_exlr;
 
-void exchange_lr_release(hfg_dev_tables *t) {
-  auto it = g_exlr.find(t);
-  if (it != g_exlr.end()) {
-    delete it->second;
-    g_exlr.erase(it);
-  }
-}
-
-static ExLRAux &exlr_for(hfg_ctx *ctx, hfg_dev_tables *t) {
-  auto it = g_exlr.find(t);
-  if (it != g_exlr.end()) return *it->second;
-  ExLRAux *a = new ExLRAux();
+static void exlr_setup(hfg_ctx *ctx, const hfg_dev_tables *t, ExLRAux *a) {
   hipStream_t s = ctx->stream;
   const int A = t->A, Ntab = t->Ntab, NLM = t->NLM, Lp1 = t->Lp1;
   a->c0tab.upload(t->h_c0tab, s);
@@ -1093,8 +1081,9 @@ static ExLRAux &exlr_for(hfg_ctx *ctx, hfg_dev_tables *t) {
   hipLaunchKernelGGL(k_exl_permute_tei, dim3(t->ntt * Ntab * nper, t->p), dim3(256), 0, s, t->tei.p, Ntab, nper, t->p,
                      t->ntt, a->kM, a->kK, a->ktei.p);
   HFG_HIP_CHECK(hipStreamSynchronize(s));
-  g_exlr[t] = a;
-  return *a;
+}
+static ExLRAux &exlr_for(hfg_ctx *ctx, hfg_dev_tables *t) {
+  return t->work.get<ExLRAux>(WS_EXLR, [&](ExLRAux &a) { exlr_setup(ctx, t, &a); });
 }
 
 /// K from P through the low-rank factors.  Returns false (nothing written) when P is not reproduced by at most

@@ -1175,18 +1175,12 @@ static size_t xc_density_radial_lds(int p, int nq, int do_lapl = 0) {
   return shb;
 }
 
-struct FockAux {
+struct FockAux : Workspace {
   DevBuf<int> pure_shell, pure_n, lmpos;
   DevBuf<double> Pc, Jc, Pc2, Jc2, Paux, Y, Jaux, D0, D1, D2, D3, V, Fo, GA, GB, GC, GL, partial, scal;
 };
 
-static std::map<hfg_dev_tables *, FockAux *> g_aux;
-
-static FockAux &aux_for(hfg_ctx *ctx, hfg_basis *basis) {
-  hfg_dev_tables *t = basis->dev;
-  auto it = g_aux.find(t);
-  if (it != g_aux.end()) return *it->second;
-  FockAux *a = new FockAux();
+static void aux_setup(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux *a) {
   std::vector<int> ps(t->N), pn(t->N);
   {
     size_t k = 0;
@@ -1207,16 +1201,10 @@ static FockAux &aux_for(hfg_ctx *ctx, hfg_basis *basis) {
   }
   a->lmpos.upload(lmpos, ctx->stream);
   HFG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  g_aux[t] = a;
-  return *a;
 }
-
-void fock_release(hfg_dev_tables *t) {
-  auto it = g_aux.find(t);
-  if (it != g_aux.end()) {
-    delete it->second;
-    g_aux.erase(it);
-  }
+static FockAux &aux_for(hfg_ctx *ctx, hfg_basis *basis) {
+  hfg_dev_tables *t = basis->dev;
+  return t->work.get<FockAux>(WS_FOCK, [&](FockAux &a) { aux_setup(ctx, t, &a); });
 }
 
 static hfg_dev_tables *tables_of(hfg_ctx *ctx, hfg_basis *basis) {

@@ -570,12 +570,11 @@ void gemm_worklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, in
 /// HELFEM_GEMM_TILE = 64 / 128 forces one.
 bool gemm_prefers_128(hfg_ctx *ctx, long tiles128) {
   if (tuning().gemm_tile) return tuning().gemm_tile == 128;
-  static int slots = 0;
-  if (!slots) {
+  static const int slots = [&] {  // once per process, under the guard of the static's initialisation
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    slots = 2 * ncu;
-  }
+    return 2 * ncu;
+  }();
   const long rounds = (tiles128 + slots - 1) / slots;
   return tiles128 >= slots / 2 && (double)tiles128 >= 0.85 * (double)(rounds * slots);
 }

@@ -2,7 +2,7 @@
 // under tests/gpu_probe/), declared once, grouped by the file that defines it.  Default arguments live here and nowhere
 // else.  The defining file includes this header too, so a definition that drifts from its declaration shows up as an
 // ambiguous call or a missing-prototype warning (tests/test_internal_header_cpu.py).  Not a public header: the C ABI is
-// include/helfem_gpu.h.  (set_error is declared in common.h; upload_tables and upload_rs_tables in tables.h.)
+// include/helfem_gpu.h.  (set_error is declared in common.h; upload_basis_tables in tables.h.)
 #pragma once
 #include "common.h"
 #include "tables.h"
@@ -52,15 +52,12 @@ void fock_compact_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, co
                       double thr);  // fock.hip
 void fock_finish_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const double *dH0, const int *dBlockId,
                      double *dF);  // fock.hip
-void fock_release(hfg_dev_tables *t);  // fock.hip
 
 // exchange.hip, exchange_lr.hip
 void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, bool rs = false, const double *Lknown = nullptr,
                   int rknown = 0);  // exchange.hip
-void exchange_release(hfg_dev_tables *t);  // exchange.hip
 bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, double *dK, const double *Lknown,
                           int rknown);  // exchange_lr.hip
-void exchange_lr_release(hfg_dev_tables *t);  // exchange_lr.hip
 
 // tei_dev.hip
 void compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis);  // tei_dev.hip
@@ -89,25 +86,20 @@ int64_t eig_sel_count(int nblk, const int64_t *blk_ptr, int64_t nev);  // eig.hi
 void eig_sym_sel_dev(hfg_ctx *ctx, int n, const double *dA, int nev, double *dE, double *dC);  // eig.hip
 void eig_gsym_sub_sel_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
                           const int64_t *blk_idx, int nev, double *dE, double *dC);  // eig.hip
-void eig_release(hfg_ctx *ctx);  // eig.hip
 
 // dc.hip, stsel.hip, trd.hip, trdp.hip: the stages of the eigensolver
 void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, double *const *e, double *const *Z);  // dc.hip
 int dc_status(hfg_ctx *ctx);  // dc.hip
 int *dc_status_word(hfg_ctx *ctx);  // dc.hip
-void dc_release(hfg_ctx *ctx);  // dc.hip
 void tridiag_sel_batch(hfg_ctx *ctx, int nblk, const int *ns, const int *nev, double *const *d, double *const *e, double *const *W,
                        double *const *Z);  // stsel.hip
-void stsel_release(hfg_ctx *ctx);  // stsel.hip
 void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *A, double *const *d, double *const *e,
                           double *const *tau);  // trd.hip
 void trd_measure_gemv(hfg_ctx *ctx, double *ms, int64_t *launches);  // trd.hip
-void trd_release(hfg_ctx *ctx);  // trd.hip
 bool tridiagonalize_takes_chain(int nblk, const int *ns);  // trdp.hip
 void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *const *A, double *const *d, double *const *e,
                                double *const *tau, std::vector<char> &done);  // trdp.hip
 void trdp_check_status(hfg_ctx *ctx);  // trdp.hip
-void trdp_release(hfg_ctx *ctx);  // trdp.hip
 
 // misc.hip
 void form_sinvh_dev(hfg_ctx *ctx, int N, const double *dS, bool chol, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,

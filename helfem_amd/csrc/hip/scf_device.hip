@@ -544,19 +544,7 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
         hb->rs_on_device = false;
       }
     }
-    if (hb->dev) {
-      fock_release(hb->dev);
-      exchange_release(hb->dev);
-      exchange_lr_release(hb->dev);
-    }
-    upload_tables(ctx, hb, ldft, mdft);
-    if (hb->dev_rs) {
-      exchange_release(hb->dev_rs);
-      exchange_lr_release(hb->dev_rs);
-      delete hb->dev_rs;
-      hb->dev_rs = nullptr;
-    }
-    if (opt.omega != 0.0) upload_rs_tables(ctx, hb);
+    upload_basis_tables(ctx, hb, ldft, mdft, opt.omega != 0.0);
     if (verbose) printf("Done in %.6f\n", wall() - t0);
   };
   // guess (main.cpp:650-712): core Hamiltonian, or T + the model potential of the screened nuclei by quadrature on the

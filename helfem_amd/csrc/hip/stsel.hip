@@ -334,30 +334,16 @@ __global__ __launch_bounds__(64) void k_stsel_vectors(StselBatch b, int *__restr
   }
 }
 
-struct StselWork {
+struct StselWork : Workspace {
   DevBuf<double> work[STSEL_MAXB];
 };
-static std::map<hfg_ctx *, StselWork *> g_stsel;
-void stsel_release(hfg_ctx *ctx) {
-  auto it = g_stsel.find(ctx);
-  if (it != g_stsel.end()) {
-    delete it->second;
-    g_stsel.erase(it);
-  }
-}
 
 /// The lowest nev[blk] eigenpairs of nblk symmetric tridiagonal matrices (d[blk], e[blk]; not overwritten): eigenvalues
 /// ascending in W[blk], eigenvectors in Z[blk] (n x nev, ld n).  Queued on the context's stream.
 void tridiag_sel_batch(hfg_ctx *ctx, int nblk, const int *ns, const int *nev, double *const *d, double *const *e, double *const *W,
                        double *const *Z) {
   if (nblk > STSEL_MAXB) throw std::logic_error("tridiag_sel_batch: too many blocks");
-  StselWork *wp;
-  auto it = g_stsel.find(ctx);
-  if (it == g_stsel.end()) {
-    wp = new StselWork();
-    g_stsel[ctx] = wp;
-  } else
-    wp = it->second;
+  StselWork *wp = &ctx->work.get<StselWork>(WS_STSEL);
   hipStream_t s = ctx->stream;
   StselBatch b;
   int nmax = 0, nevmax = 0;

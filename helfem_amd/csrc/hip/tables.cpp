@@ -170,26 +170,33 @@ BasisView view_of(const hfg_basis *basis, bool rs = false) {
 
 static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_dev_tables *t, int ldft, int mdft);
 
-void upload_tables(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft) {
+static void upload_tables(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft) {
   if (!basis->have_tei()) throw std::logic_error("Primitive teis have not been computed!\n");
   const BasisView b = view_of(basis);
   HFG_HIP_CHECK(hipSetDevice(ctx->device));
-  if (basis->dev) delete basis->dev;
+  delete basis->dev;
   hfg_dev_tables *t = new hfg_dev_tables();
   basis->dev = t;
   basis->dev_device = ctx->device;
   fill_tables(ctx, basis, b, t, ldft, mdft);
 }
 
-void upload_rs_tables(hfg_ctx *ctx, hfg_basis *basis) {
+static void upload_rs_tables(hfg_ctx *ctx, hfg_basis *basis) {
   const BasisView b = view_of(basis, true);
   HFG_HIP_CHECK(hipSetDevice(ctx->device));
-  if (basis->dev_rs) delete basis->dev_rs;
+  delete basis->dev_rs;
   hfg_dev_tables *t = new hfg_dev_tables();
   basis->dev_rs = t;
   if (basis->dev && basis->dev_device != ctx->device) throw std::logic_error("basis tables live on a different device\n");
   basis->dev_device = ctx->device;
   fill_tables(ctx, basis, b, t, 0, 0);
+}
+
+void upload_basis_tables(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft, bool with_rs) {
+  upload_tables(ctx, basis, ldft, mdft);
+  delete basis->dev_rs;
+  basis->dev_rs = nullptr;
+  if (with_rs) upload_rs_tables(ctx, basis);
 }
 
 static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_dev_tables *t, int ldft, int mdft) {

@@ -70,11 +70,14 @@ struct hfg_dev_tables {
   std::vector<int> h_LM_L, h_LM_M, h_LM_ilm, h_grp_off, h_shell_l, h_shell_m, h_shell_skip, h_lm_tab;
   std::vector<double> h_LM_fac;
   std::vector<double> h_c0tab, h_c2tab;  // [A][A][Lp1] coupling of the ordered shell pair with L
+
+  // workspaces of the builds that read these tables (workspace_owner.h); last member, so they go before the tables do
+  hfg::WorkspaceOwner<hfg::WS_TABLE_SLOTS> work;
 };
 
 namespace hfg {
-/// build (or rebuild) the device tables of basis on the context's device
-void upload_tables(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft);
-/// build (or rebuild) basis->dev_rs from the host tables of compute_yukawa / compute_erfc
-void upload_rs_tables(hfg_ctx *ctx, hfg_basis *basis);
+/// build (or rebuild) basis->dev on the context's device and drop basis->dev_rs; with_rs: rebuild dev_rs too, from the
+/// range-separated tables of compute_yukawa / compute_erfc / compute_rs_tei_dev.  The old table sets take their
+/// workspaces with them.
+void upload_basis_tables(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft, bool with_rs);
 }  // namespace hfg

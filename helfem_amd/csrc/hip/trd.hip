@@ -1173,7 +1173,7 @@ static void trdf_launch(hipStream_t s, const TrdBatch *db, int nblk, int nmax, i
   else hipLaunchKernelGGL(k_trdf<1024>, dim3(grid, nblk), dim3(1024), 0, s, db, i, c, sweep);
 }
 
-struct TrdWork {
+struct TrdWork : Workspace {
   DevBuf<double> V[TB_MAXB], col[TB_MAXB], normp[TB_MAXB], pp[TB_MAXB], dots[TB_MAXB], cpart[TB_MAXB];
   DevBuf<double> fx[TB_MAXB], fpp[TB_MAXB], fdots[TB_MAXB], fxn2[TB_MAXB], fcp[TB_MAXB];
   DevBuf<GemmTask> ptasks;  // panel updates of the fused variant, [panel][block]
@@ -1183,14 +1183,6 @@ struct TrdWork {
   DevBuf<TrdBatch> desc;
   std::vector<int> last_ns;  // sizes of the last batch (for the measurement replay)
 };
-static std::map<hfg_ctx *, TrdWork *> g_trd;
-void trd_release(hfg_ctx *ctx) {
-  auto it = g_trd.find(ctx);
-  if (it != g_trd.end()) {
-    delete it->second;
-    g_trd.erase(it);
-  }
-}
 
 static thread_local bool g_in_chain_fallback = false;  // the chain below is running on what the persistent path left
 /// A[blk] (n x n, ld n, full symmetric storage) -> d, e, tau and the Householder vectors below the subdiagonal
@@ -1205,8 +1197,7 @@ void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *
     int ndone = 0;
     for (char c : done) ndone += c ? 1 : 0;
     if (ndone > 0) {
-      auto itp = g_trd.find(ctx);
-      if (itp != g_trd.end()) itp->second->last_ns.clear();
+      if (TrdWork *wc = ctx->work.find<TrdWork>(WS_TRD)) wc->last_ns.clear();
       if (ndone == nblk) return;
       // the matrices the persistent path left (order beyond its register tiles, a refused launch) go through the chain
       std::vector<int> ns2;
@@ -1230,14 +1221,7 @@ void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *
       return;
     }
   }
-  TrdWork *wp;
-  auto it = g_trd.find(ctx);
-  if (it == g_trd.end()) {
-    wp = new TrdWork();
-    g_trd[ctx] = wp;
-  } else
-    wp = it->second;
-  TrdWork &w = *wp;
+  TrdWork &w = ctx->work.get<TrdWork>(WS_TRD);
   TrdBatch b{};
   int nmax = 0;
   for (int i = 0; i < nblk; i++) {
@@ -1363,7 +1347,7 @@ void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *
     hipLaunchKernelGGL(k_trd_tail_reg, dim3(nblk), dim3(TR_NTH), 0, s, db, j_tail);
   } else if (j_tail < nmax) {
     const size_t sht = (size_t)(TT_MAX * TT_LD + 2 * TT_MAX + TT_CG * TT_MAX + 32) * sizeof(double);
-    static bool attr_set = false;
+    static thread_local bool attr_set = false;  // per thread, so per context and device
     if (!attr_set) {
       HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_trd_tail, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sht));
       attr_set = true;
@@ -1381,9 +1365,9 @@ void tridiagonalize_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *
 void trd_measure_gemv(hfg_ctx *ctx, double *ms, int64_t *launches) {
   *ms = 0.0;
   *launches = 0;
-  auto it = g_trd.find(ctx);
-  if (it == g_trd.end() || it->second->last_ns.empty()) throw std::logic_error("no tridiagonalisation has run on this context");
-  TrdWork &w = *it->second;
+  TrdWork *wp = ctx->work.find<TrdWork>(WS_TRD);
+  if (!wp || wp->last_ns.empty()) throw std::logic_error("no tridiagonalisation has run on this context");
+  TrdWork &w = *wp;
   const int nblk = (int)w.last_ns.size();
   int nmax = 0;
   for (int n : w.last_ns) nmax = std::max(nmax, n);

@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 namespace hfg {
@@ -544,7 +545,7 @@ __global__ __launch_bounds__(TP_NT) void k_trdp(const TrdpDesc *__restrict__ dp)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-struct TrdpWork {
+struct TrdpWork : Workspace {
   DevBuf<unsigned long long> ring;  // status block (16 words) + the exchange rings of all matrices
   DevBuf<unsigned long long> stamps;
   DevBuf<TrdpDesc> desc;
@@ -555,23 +556,16 @@ struct TrdpWork {
   int ncu = 0;
   std::vector<int> last_ns;
   int last_R = 0, last_U = 0, last_grid = 0, last_nmax = 0;
-};
-static std::map<hfg_ctx *, TrdpWork *> g_trdp;
-
-void trdp_release(hfg_ctx *ctx) {
-  auto it = g_trdp.find(ctx);
-  if (it != g_trdp.end()) {
-    if (it->second->h_status) (void)hipHostFree(it->second->h_status);
-    delete it->second;
-    g_trdp.erase(it);
+  ~TrdpWork() {
+    if (h_status) (void)hipHostFree(h_status);
   }
-}
+};
 
 /// throws when the last persistent launch of this context ended through a spin limit (call after a synchronisation)
 void trdp_check_status(hfg_ctx *ctx) {
-  auto it = g_trdp.find(ctx);
-  if (it == g_trdp.end() || !it->second->pending) return;
-  TrdpWork &w = *it->second;
+  TrdpWork *wp = ctx->work.find<TrdpWork>(WS_TRDP);
+  if (!wp || !wp->pending) return;
+  TrdpWork &w = *wp;
   w.pending = false;
   bool bad = false;
   for (int q = 0; q < TP_MAXLAUNCH; q++) {
@@ -690,17 +684,11 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
   done.assign(nblk, 0);
   if (tuning().trd_mode != TrdMode::persistent) return;
   if (nblk < 1 || nblk > TP_MAXB) return;
-  TrdpWork *wp;
-  auto it = g_trdp.find(ctx);
-  if (it == g_trdp.end()) {
-    wp = new TrdpWork();
-    g_trdp[ctx] = wp;
-    HFG_HIP_CHECK(hipDeviceGetAttribute(&wp->ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    HFG_HIP_CHECK(hipHostMalloc((void **)&wp->h_status, TP_MAXLAUNCH * sizeof(unsigned long long), hipHostMallocDefault));
-    for (int i = 0; i < TP_MAXLAUNCH; i++) wp->h_status[i] = ~0ull;
-  } else
-    wp = it->second;
-  TrdpWork &w = *wp;
+  TrdpWork &w = ctx->work.get<TrdpWork>(WS_TRDP, [&](TrdpWork &nw) {
+    HFG_HIP_CHECK(hipDeviceGetAttribute(&nw.ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    HFG_HIP_CHECK(hipHostMalloc((void **)&nw.h_status, TP_MAXLAUNCH * sizeof(unsigned long long), hipHostMallocDefault));
+    for (int i = 0; i < TP_MAXLAUNCH; i++) nw.h_status[i] = ~0ull;
+  });
   if (w.pending) {
     // the previous launches' status words were copied back on this stream; they are only READ when the stream says so
     if (hipStreamQuery(ctx->stream) == hipSuccess) trdp_check_status(ctx);
@@ -866,7 +854,7 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
     hipError_t err;
     {
       // HIP events around this launch alone on the launch stream (bench.py: roofline), for the family and per tile shape
-      static std::map<std::pair<int, int>, std::string> shape_names;
+      static thread_local std::map<std::pair<int, int>, std::string> shape_names;
       std::string &nm = shape_names[std::make_pair(L.sh.R, L.sh.U)];
       if (nm.empty()) nm = "k_trdp<" + std::to_string(L.sh.R) + ", " + std::to_string(L.sh.U) + ">";
       ProfScope pk(ctx, "k_trdp");
@@ -880,11 +868,10 @@ void tridiagonalize_persistent(hfg_ctx *ctx, int nblk, const int *ns, double *co
       for (int i : L.idx) first = first && !touched[i];
       if (!first)  // a later phase: the matrices are half reduced, there is nothing to fall back to
         throw std::runtime_error(std::string("persistent tridiagonalisation: cooperative launch refused in a later phase: ") + hipGetErrorString(err));
-      static bool told = false;
-      if (!told) {
+      static std::atomic<bool> told(false);
+      if (!told.exchange(true)) {
         fprintf(stderr, "helfem_amd: cooperative launch of the persistent tridiagonalisation refused (%s): grid %d; using the launch chain\n",
                 hipGetErrorString(err), L.sh.grid);
-        told = true;
       }
       for (int i : L.idx) failed[i] = 1;  // the chain takes these matrices
       continue;
