@@ -271,6 +271,10 @@ void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, 
   // fast path for the low-rank densities of SCF runs (exchange_lr.hip); HELFEM_EXCHANGE=general forces the
   // general kernels below, which take any symmetric P
   if (!helfem::tuning_live().exchange_general && exchange_lowrank_dev(ctx, t, dP, dK, Lknown, rknown)) return;  // (read at every call)
+  // k_ex_radial: one thread per entry of a p x p block, a workgroup holds 1024
+  if (t->p * t->p > 1024)
+    throw std::runtime_error("exchange: the general kernels take at most 32 nodes per element, the basis has " +
+                             std::to_string(t->p) + "\n");
   ExAux &a = exaux_for(ctx, t);
   hipStream_t s = ctx->stream;
   const int A = t->A, R = t->R, E = t->E, p = t->p, Nd = t->Nd, N = t->N, Nlm = t->Ntab, ntt = t->ntt;

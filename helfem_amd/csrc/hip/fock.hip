@@ -231,14 +231,14 @@ __global__ void k_coulomb_radial(const double *__restrict__ Paux, const double *
     }
   }
   __syncthreads();
-  if (threadIdx.x < 4 * E) {
+  // (strided: 4 * E exceeds the workgroup from E = 17 at up to 8 nodes, E = 65 at 14 and more)
+  for (int k = threadIdx.x; k < 4 * E; k += blockDim.x) {
     double v = 0.0;
-    for (int w = 0; w < nwave; w++) v += red[threadIdx.x * nwave + w];
-    sc[threadIdx.x] = fac * v;
+    for (int w = 0; w < nwave; w++) v += red[k * nwave + w];
+    sc[k] = fac * v;
   }
   __syncthreads();
-  if (threadIdx.x < E) {
-    int e = threadIdx.x;
+  for (int e = threadIdx.x; e < E; e += blockDim.x) {
     // contributions to element e from jel>e use "big" of jel, from jel<e use "small" of jel
     double sb = 0.0, ss = 0.0;
     for (int jel = e + 1; jel < E; jel++) sb += sc[1 * E + jel] - sc[3 * E + jel];  // jbig0 - jbig2
