@@ -11,6 +11,7 @@ read like the reference's own code:
     basis.overlap()/kinetic()/nuclear()               same
     basis.compute_tei(exchange)        basis.cpp:1166  same
     basis.coulomb(P) / exchange(P)     basis.cpp:1359  same (numpy in / numpy out)
+    (no counterpart)                                   basis.coulomb_batch(Ps) / coulomb_energy_matrix(Ps)
     dftgrid::DFTGrid(&basis,ldft,mdft).eval_Fxc(...)  DFTGrid(basis,ldft,mdft).eval_Fxc(x_func,c_func,P,thr)
     scf::eig_gsym / eig_gsym_sub / form_density       scf.eig_gsym / scf.eig_gsym_sub / scf.form_density
 
@@ -143,6 +144,9 @@ def lib():
                                       c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_double]
         L.hfg_xc_fock_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]
+        L.hfg_coulomb_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p]
+        L.hfg_coulomb_energy_matrix.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p]
+        L.hfg_coulomb_batch_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
         L.hfg_profile_get.argtypes = [ctypes.c_void_p, ctypes.c_char_p, c_double_p, c_i64_p]
         L.hfg_measure_kernel.argtypes = [ctypes.c_void_p, ctypes.c_char_p, c_double_p, c_i64_p]
         L.hfg_profile_names.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
@@ -401,6 +405,55 @@ class TwoDBasis(object):
         K = np.zeros_like(P, order="F")
         _check(lib().hfg_exchange(ctx.h, self.h, _p(P), _p(K)))
         return K
+
+    def _batch(self, Ps, ctx):
+        """the context of a batched call (uploading to it when the tables are nowhere yet) and the densities in the layout
+        of hfg_coulomb_batch: row b holds P_b column by column"""
+        if ctx is not None and self._uploaded is None:
+            self.upload(ctx=ctx)
+        ctx = ctx or self._ensure()
+        N = self.Nbf()
+        Ps = [np.asarray(P, dtype=np.float64) for P in Ps]
+        if any(P.shape != (N, N) for P in Ps):
+            raise ValueError("coulomb_batch: every density is an Nbf x Nbf matrix")
+        buf = np.empty((len(Ps), N * N))
+        for b, P in enumerate(Ps):
+            buf[b] = P.ravel(order="F")
+        return ctx, buf
+
+    def coulomb_batch(self, Ps, ctx=None):
+        """J[P_b] for every density of Ps (a sequence of symmetric Nbf x Nbf matrices, or an array (nP, Nbf, Nbf)) with the
+        in-element tables read once for the batch (hfg_coulomb_batch).  Returns an array (nP, Nbf, Nbf): out[b] = coulomb(Ps[b])."""
+        ctx, buf = self._batch(Ps, ctx)
+        N, out = self.Nbf(), np.zeros_like(buf)
+        _check(lib().hfg_coulomb_batch(ctx.h, self.h, len(buf), _p(buf), _p(out)))
+        return out.reshape(len(buf), N, N).transpose(0, 2, 1)
+
+    def coulomb_energy_matrix(self, Ps, ctx=None):
+        """W[a, b] = tr(P_a J[P_b]) for the densities of Ps, formed on the device (hfg_coulomb_energy_matrix); symmetric by
+        the symmetry of the integrals, not symmetrised"""
+        ctx, buf = self._batch(Ps, ctx)
+        W = np.zeros((len(buf), len(buf)), order="F")
+        _check(lib().hfg_coulomb_energy_matrix(ctx.h, self.h, len(buf), _p(buf), _p(W)))
+        return W
+
+    def coulomb_batch_torch(self, dP, out=None, ctx=None):
+        """hfg_coulomb_batch_devptr on torch tensors in HBM: dP holds nP densities of Nbf x Nbf, one after the other, each
+        column-major (float64, contiguous, any shape of nP * Nbf * Nbf elements).  The build is enqueued on the context's
+        stream, honours its shard and is not waited for; returns `out` (a new tensor like dP when None)."""
+        import torch
+        if ctx is not None and self._uploaded is None:
+            self.upload(ctx=ctx)
+        ctx = ctx or self._ensure()
+        N2 = self.Nbf() ** 2
+        if out is None:
+            out = torch.empty_like(dP)
+        for t in (dP, out):
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() % N2 or t.numel() != dP.numel():
+                raise ValueError("coulomb_batch_torch: contiguous float64 device tensors of nP * Nbf * Nbf elements")
+        _check(lib().hfg_coulomb_batch_devptr(ctx.h, self.h, dP.numel() // N2, ctypes.c_void_p(dP.data_ptr()),
+                                              ctypes.c_void_p(out.data_ptr())))
+        return out
 
     def model_potential(self, p1, p2=None):
         """TwoDGrid::model_potential(p1, p2) / atomic TwoDBasis::model_potential(p1): p = (kind, Z[, d[, H]]) with kind

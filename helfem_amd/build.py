@@ -105,9 +105,10 @@ def build_cli(verbose=True, force=False):
 
 
 def build_adapter_test(verbose=True):
-    """tests/cpp/adapter_test and tests/cpp/eigsel_adapter_test: call the hot path through include/helfem_gpu_arma.hpp (built
-    next to the library; the GPU box runs them from tests/test_gpu_adapter.py and tests/test_gpu_eigsel_adapter.py)"""
-    for name in ("adapter_test", "eigsel_adapter_test"):
+    """tests/cpp/adapter_test, eigsel_adapter_test and coulomb_batch_adapter_test: call the hot path through
+    include/helfem_gpu_arma.hpp (built next to the library; the GPU box runs them from tests/test_gpu_adapter.py,
+    tests/test_gpu_eigsel_adapter.py and tests/test_gpu_coulomb_batch.py)"""
+    for name in ("adapter_test", "eigsel_adapter_test", "coulomb_batch_adapter_test"):
         _build_adapter_program(name, verbose)
 
 

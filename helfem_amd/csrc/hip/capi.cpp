@@ -709,6 +709,19 @@ int hfg_coulomb_dev(hfg_ctx *ctx, hfg_basis *b, const double *dP, double *dJ) {
   HFG_TRY coulomb_dev(ctx, b, dP, dJ);
   HFG_CATCH
 }
+// the refusals shared by the three batched Coulomb entries; false: nothing to do (nP == 0)
+static bool coulomb_batch_args(const char *who, hfg_ctx *ctx, hfg_basis *b, int64_t nP, const void *in, const void *out) {
+  if (nP < 0) throw std::logic_error(std::string(who) + ": negative number of densities\n");
+  if (!ctx || !b) throw std::logic_error(std::string(who) + ": null context or basis\n");
+  if (nP == 0) return false;
+  if (!in || !out) throw std::logic_error(std::string(who) + ": null matrix pointer\n");
+  return true;
+}
+int hfg_coulomb_batch_devptr(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *dP, double *dJ) {
+  HFG_TRY
+  if (coulomb_batch_args("hfg_coulomb_batch_devptr", ctx, b, nP, dP, dJ)) coulomb_batch_dev(ctx, b, nP, dP, dJ);
+  HFG_CATCH
+}
 int hfg_exchange_dev(hfg_ctx *ctx, hfg_basis *b, const double *dP, double *dK) {
   HFG_TRY exchange_dev(ctx, b, dP, dK);
   HFG_CATCH
@@ -798,6 +811,29 @@ int hfg_coulomb(hfg_ctx *ctx, hfg_basis *b, const double *P, double *J) {
   double *dP = st.up(P, N * N), *dJ = st.alloc(N * N);
   coulomb_dev(ctx, b, dP, dJ);
   st.down(J, dJ, N * N);
+  st.sync();
+  HFG_CATCH
+}
+int hfg_coulomb_batch(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *P, double *J) {
+  HFG_TRY
+  if (!coulomb_batch_args("hfg_coulomb_batch", ctx, b, nP, P, J)) return 0;
+  FullShard full(ctx);
+  size_t n = b->Nbf() * b->Nbf() * (size_t)nP;
+  Stage st(ctx);
+  double *dP = st.up(P, n), *dJ = st.alloc(n);
+  coulomb_batch_dev(ctx, b, nP, dP, dJ);
+  st.down(J, dJ, n);
+  st.sync();
+  HFG_CATCH
+}
+int hfg_coulomb_energy_matrix(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *P, double *W) {
+  HFG_TRY
+  if (!coulomb_batch_args("hfg_coulomb_energy_matrix", ctx, b, nP, P, W)) return 0;
+  FullShard full(ctx);
+  Stage st(ctx);
+  double *dP = st.up(P, b->Nbf() * b->Nbf() * (size_t)nP), *dW = st.alloc((size_t)nP * nP);
+  coulomb_energy_matrix_dev(ctx, b, nP, dP, dW);
+  st.down(W, dW, (size_t)nP * nP);
   st.sync();
   HFG_CATCH
 }

@@ -191,10 +191,12 @@ __global__ void k_coulomb_tei(const double *__restrict__ tei, const double *__re
 // K2c per (L,M): disjoint (cross-element) part via the trace scalars + in-element part (basis.cpp:1424-1494).
 //     full = 1: prolate kernel with the four P0/P2/Q0/Q2 and 00/02/20/22 tables; full = 0: spherical kernel
 //     r_<^L/r_>^{L+1} with P0/Q0 and 00 only (atomic TwoDBasis.cpp:884-936), disj then holds [P0][Q0].
-__global__ void k_coulomb_radial(const double *__restrict__ Paux, const double *__restrict__ Y,
-                                 const double *__restrict__ disj, const int *__restrict__ LM_ilm,
-                                 const int *__restrict__ LM_tab, const double *__restrict__ LM_fac, int Ntab, int NLM,
-                                 int E, int p, int full, int rank, int nranks, double *__restrict__ Jaux) {
+//     (the body is shared with k_coulomb_radial_batch, which runs it once per density of a batch)
+__device__ __forceinline__ void coulomb_radial_body(const double *__restrict__ Paux, const double *__restrict__ Y,
+                                                    const double *__restrict__ disj, const int *__restrict__ LM_ilm,
+                                                    const int *__restrict__ LM_tab, const double *__restrict__ LM_fac, int Ntab,
+                                                    int NLM, int E, int p, int full, int rank, int nranks,
+                                                    double *__restrict__ Jaux) {
   extern __shared__ double sh[];  // red[4*E*nwave], sc[4*E], big[E], small[E]
   int iLM = blockIdx.x;
   if (LM_ilm[iLM] % nranks != rank) return;
@@ -264,6 +266,12 @@ __global__ void k_coulomb_radial(const double *__restrict__ Paux, const double *
       Jaux[((size_t)(1 * NLM + iLM) * E + e) * pp + t] = j2;
     }
 }
+__global__ void k_coulomb_radial(const double *__restrict__ Paux, const double *__restrict__ Y,
+                                 const double *__restrict__ disj, const int *__restrict__ LM_ilm,
+                                 const int *__restrict__ LM_tab, const double *__restrict__ LM_fac, int Ntab, int NLM,
+                                 int E, int p, int full, int rank, int nranks, double *__restrict__ Jaux) {
+  coulomb_radial_body(Paux, Y, disj, LM_ilm, LM_tab, LM_fac, Ntab, NLM, E, p, full, rank, nranks, Jaux);
+}
 
 // K3 bra expansion (basis.cpp:1498-1527): Jc[i][j][e][:] = sum_L c0(j,i,L) Jaux0[iLM] + c2(j,i,L) Jaux2[iLM]
 __global__ void k_coulomb_bra(const double *__restrict__ Jaux, int A, int E, int pp, int NLM,
@@ -301,6 +309,284 @@ __global__ void k_coulomb_bra(const double *__restrict__ Jaux, int A, int E, int
     }
     Jc[((size_t)ij * E + e) * pp + t] = acc;
   }
+}
+
+// -------------------------------------------------------------------------------------------------
+// Coulomb for a batch of densities (hfg_coulomb_batch, DESIGN 3.1 "Batched J")
+// -------------------------------------------------------------------------------------------------
+// Every buffer of the single build gains a leading density index with the stride the caller names: Pc[b][x][y][e][j][i],
+// Paux[b][0/2][iLM][e][t], Y[b][tt][iLM][e][t], Jaux[b][0/2][iLM][e][t].  Same sums and the same order of additions per
+// density as the kernels above; the in-element tables are read once for all densities of a pass.
+constexpr int CB_DB = 4;  // densities per thread of the batched ket and bra kernels: one read of a coupling entry serves them all
+
+// K1 for nb densities: blockIdx.z takes CB_DB of them
+__global__ void k_coulomb_ket_batch(const double *__restrict__ Pc, size_t sPc, int nb, int A, int E, int pp,
+                                    const int *__restrict__ lm_off, const int *__restrict__ lm_x, const int *__restrict__ lm_y,
+                                    const double *__restrict__ lm_c0, const double *__restrict__ lm_c2, int NLM,
+                                    const int *__restrict__ LM_ilm, int rank, int nranks, double *__restrict__ Paux, size_t sPaux) {
+  const int iLM = blockIdx.x, e = blockIdx.y, b0 = blockIdx.z * CB_DB;
+  if (LM_ilm[iLM] % nranks != rank) return;
+  const int beg = lm_off[iLM], end = lm_off[iLM + 1];
+  for (int t = threadIdx.x; t < pp; t += blockDim.x) {
+    double a0[CB_DB], a2[CB_DB];
+#pragma unroll
+    for (int u = 0; u < CB_DB; u++) a0[u] = a2[u] = 0.0;
+#pragma unroll 2
+    for (int k = beg; k < end; k++) {
+      const size_t o = ((size_t)(lm_x[k] * A + lm_y[k]) * E + e) * pp + t;
+      const double c0 = lm_c0[k], c2 = lm_c2[k];
+#pragma unroll
+      for (int u = 0; u < CB_DB; u++) {
+        const double v = (b0 + u < nb) ? Pc[(size_t)(b0 + u) * sPc + o] : 0.0;
+        a0[u] += c0 * v;
+        a2[u] += c2 * v;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < CB_DB; u++)
+      if (b0 + u < nb) {
+        double *out = Paux + (size_t)(b0 + u) * sPaux;
+        out[((size_t)(0 * NLM + iLM) * E + e) * pp + t] = a0[u];
+        out[((size_t)(1 * NLM + iLM) * E + e) * pp + t] = a2[u];
+      }
+  }
+}
+
+// K2b for a batch, small column counts: Y[pp x ncol] = tei[pp x pp] * X[pp x ncol] with the columns (sign s, density b) ->
+//     s * nb + b of the +M channel and, where it exists, of its -M partner; NC >= ncol accumulators per thread (one row
+//     of Y each), X in LDS as X[c][NC] so that all lanes read one address.  One pass over the table for all columns.
+template <int NC>
+__global__ void k_coulomb_tei_cols(const double *__restrict__ tei, const double *__restrict__ Paux, size_t sPaux, int nb, int Ntab,
+                                   int NLM, int E, int pp, const int *__restrict__ lmpos, const int *__restrict__ lm_tab, int rank,
+                                   int nranks, double *__restrict__ Y, size_t sY) {
+  extern __shared__ double sh[];  // X[pp][NC]
+  const int ilm = blockIdx.x / E, e = blockIdx.x % E;
+  if (ilm % nranks != rank) return;
+  const int tt = blockIdx.y;
+  const int iLMp = lmpos[2 * ilm], iLMm = lmpos[2 * ilm + 1];
+  const int which = (tt & 1);
+  const int ncol = (iLMm >= 0 ? 2 : 1) * nb;  // host: ncol <= 2 nb <= NC
+  for (int idx = threadIdx.x; idx < pp * NC; idx += blockDim.x) {
+    const int j = idx / pp, c = idx - j * pp;
+    double v = 0.0;
+    if (j < ncol) {
+      const int sg = (j >= nb) ? 1 : 0, b = j - sg * nb, iLM = sg ? iLMm : iLMp;
+      if (iLM >= 0) v = Paux[(size_t)b * sPaux + ((size_t)(which * NLM + iLM) * E + e) * pp + c];
+    }
+    sh[c * NC + j] = v;
+  }
+  __syncthreads();
+  const double *T = tei + (((size_t)tt * Ntab + lm_tab[ilm]) * E + e) * (size_t)pp * pp;
+  for (int r = threadIdx.x; r < pp; r += blockDim.x) {
+    double y[NC];
+#pragma unroll
+    for (int j = 0; j < NC; j++) y[j] = 0.0;
+#pragma unroll 4
+    for (int c = 0; c < pp; c++) {
+      const double v = T[(size_t)c * pp + r];
+#pragma unroll
+      for (int j = 0; j < NC; j++) y[j] += v * sh[c * NC + j];
+    }
+#pragma unroll
+    for (int j = 0; j < NC; j++)
+      if (j < ncol) {
+        const int sg = (j >= nb) ? 1 : 0, b = j - sg * nb, iLM = sg ? iLMm : iLMp;
+        if (iLM >= 0) Y[(size_t)b * sY + ((size_t)(tt * NLM + iLM) * E + e) * pp + r] = y[j];
+      }
+  }
+}
+
+// K2b for a batch on the matrix cores: the same product with up to 16 NT columns, v_mfma_f64_16x16x4_f64 (operand maps:
+//     hip/gemm.hip).  Issued as Y^T = X^T T^T: the a-operand is X^T from LDS (lane l: column l & 15 of the tile, table
+//     column c = k0 + (l >> 4)), the b-operand comes straight from the table in HBM (lane l: T[c][row l & 15], 16
+//     consecutive doubles per 16 lanes; every table entry is loaded by exactly one lane of one wave, once), and result
+//     register r of lane l is Y[row l & 15][column (l >> 4) + 4 r] of the tile: a store writes 16 consecutive rows of four
+//     columns.  X sits in LDS as X[c][16 NT], the columns padded with zeros there (never in the table) and, for even NT,
+//     the 16-column halves swapped in odd rows so that the two rows a half-wave reads fall into different banks.  Four
+//     waves; a wave owns four row tiles (64 rows of Y) for the whole K loop and keeps their 4 x NT result tiles in registers.
+//     Rows beyond pp read the last row again and are not stored; the K tail (pp % 4 columns) is one guarded step.
+typedef double cb_d4 __attribute__((ext_vector_type(4)));
+template <int NT>
+__global__ __launch_bounds__(256) void k_coulomb_tei_mfma(const double *__restrict__ tei, const double *__restrict__ Paux, size_t sPaux,
+                                                          int nb, int Ntab, int NLM, int E, int pp, const int *__restrict__ lmpos,
+                                                          const int *__restrict__ lm_tab, int rank, int nranks,
+                                                          double *__restrict__ Y, size_t sY) {
+  extern __shared__ double sh[];  // X[cpad][16 NT]
+  constexpr int NP = 16 * NT, RT = 4;
+  const int ilm = blockIdx.x / E, e = blockIdx.x % E;
+  if (ilm % nranks != rank) return;
+  const int tt = blockIdx.y;
+  const int iLMp = lmpos[2 * ilm], iLMm = lmpos[2 * ilm + 1];
+  const int which = (tt & 1);
+  const int ncol = (iLMm >= 0 ? 2 : 1) * nb;  // host: ncol <= 2 nb <= NP
+  const int cpad = (pp + 3) & ~3;
+  // 32 lanes along a column of X (contiguous in Paux), eight columns at a time, eight loads in flight per thread
+  for (int j = threadIdx.x >> 5; j < NP; j += 8) {
+    const double *src = nullptr;
+    if (j < ncol) {
+      const int sg = (j >= nb) ? 1 : 0, b = j - sg * nb, iLM = sg ? iLMm : iLMp;
+      if (iLM >= 0) src = Paux + (size_t)b * sPaux + ((size_t)(which * NLM + iLM) * E + e) * pp;
+    }
+    for (int c0 = threadIdx.x & 31; c0 < cpad; c0 += 256) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) v[u] = (src && c0 + 32 * u < pp) ? src[c0 + 32 * u] : 0.0;
+#pragma unroll
+      for (int u = 0; u < 8; u++) {
+        const int c = c0 + 32 * u;
+        if (c < cpad) sh[c * NP + (j ^ ((NT % 2 == 0) ? ((c & 1) << 4) : 0))] = v[u];
+      }
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
+  const int nrt = (pp + 15) / 16, kfull = pp & ~3;
+  const double *T = tei + (((size_t)tt * Ntab + lm_tab[ilm]) * E + e) * (size_t)pp * pp;
+  for (int rt0 = wave * RT; rt0 < nrt; rt0 += 4 * RT) {
+    cb_d4 acc[RT][NT];
+    int roff[RT];
+#pragma unroll
+    for (int i = 0; i < RT; i++) {
+      roff[i] = min((rt0 + i) * 16 + l15, pp - 1);
+#pragma unroll
+      for (int j = 0; j < NT; j++) acc[i][j] = cb_d4{0.0, 0.0, 0.0, 0.0};
+    }
+#pragma unroll 4
+    for (int k0 = 0; k0 < kfull; k0 += 4) {
+      const int c = k0 + l4;
+      const double *Tc = T + (size_t)c * pp;
+      const double *Xc = sh + c * NP;
+      const int sw = (NT % 2 == 0) ? ((c & 1) << 4) : 0;
+      double tb[RT], xa[NT];
+#pragma unroll
+      for (int i = 0; i < RT; i++) tb[i] = Tc[roff[i]];
+#pragma unroll
+      for (int j = 0; j < NT; j++) xa[j] = Xc[(j * 16 + l15) ^ sw];
+#pragma unroll
+      for (int i = 0; i < RT; i++)
+#pragma unroll
+        for (int j = 0; j < NT; j++) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[j], tb[i], acc[i][j], 0, 0, 0);
+    }
+    if (kfull < pp) {
+      const int c = kfull + l4;  // < cpad: the rows of X from pp on hold zeros; the table has no such column
+      const double *Tc = T + (size_t)min(c, pp - 1) * pp;
+      const double *Xc = sh + c * NP;
+      const int sw = (NT % 2 == 0) ? ((c & 1) << 4) : 0;
+#pragma unroll
+      for (int i = 0; i < RT; i++) {
+        const double tb = (c < pp) ? Tc[roff[i]] : 0.0;
+#pragma unroll
+        for (int j = 0; j < NT; j++)
+          acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(Xc[(j * 16 + l15) ^ sw], tb, acc[i][j], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < RT; i++) {
+      const int row = (rt0 + i) * 16 + l15;
+      if (row >= pp) continue;
+#pragma unroll
+      for (int j = 0; j < NT; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int col = j * 16 + l4 + 4 * r;
+          if (col >= ncol) continue;
+          const int sg = (col >= nb) ? 1 : 0, b = col - sg * nb, iLM = sg ? iLMm : iLMp;
+          if (iLM >= 0) Y[(size_t)b * sY + ((size_t)(tt * NLM + iLM) * E + e) * pp + row] = acc[i][j][r];
+        }
+    }
+  }
+}
+
+// K2c for a batch: the single-density body once per (channel, density); the LDS scalars are per workgroup, so per density
+__global__ void k_coulomb_radial_batch(const double *__restrict__ Paux, size_t sPaux, const double *__restrict__ Y, size_t sY,
+                                       const double *__restrict__ disj, const int *__restrict__ LM_ilm,
+                                       const int *__restrict__ LM_tab, const double *__restrict__ LM_fac, int Ntab, int NLM, int E,
+                                       int p, int full, int rank, int nranks, double *__restrict__ Jaux, size_t sJaux) {
+  const size_t b = blockIdx.y;
+  coulomb_radial_body(Paux + b * sPaux, Y + b * sY, disj, LM_ilm, LM_tab, LM_fac, Ntab, NLM, E, p, full, rank, nranks,
+                      Jaux + b * sJaux);
+}
+
+// K3 for nb densities: blockIdx.z takes CB_DB of them
+__global__ void k_coulomb_bra_batch(const double *__restrict__ Jaux, size_t sJaux, int nb, int A, int E, int pp, int NLM,
+                                    const int *__restrict__ pair_off, const int *__restrict__ ent_iLM,
+                                    const double *__restrict__ ent_c0, const double *__restrict__ ent_c2,
+                                    const int *__restrict__ LM_ilm, int rank, int nranks, double *__restrict__ Jc, size_t sJc) {
+  const int ij = blockIdx.x, e = blockIdx.y, b0 = blockIdx.z * CB_DB;
+  const int iang = ij / A, jang = ij % A;
+  const int pr = jang * A + iang;
+  const int beg = pair_off[pr], end = pair_off[pr + 1];
+  for (int t = threadIdx.x; t < pp; t += blockDim.x) {
+    double acc[CB_DB];
+#pragma unroll
+    for (int u = 0; u < CB_DB; u++) acc[u] = 0.0;
+    for (int k = beg; k < end; k++) {
+      const int iLM = ent_iLM[k];
+      if (LM_ilm[iLM] % nranks != rank) continue;
+      const double c0 = ent_c0[k], c2 = ent_c2[k];
+      const size_t o0 = ((size_t)(0 * NLM + iLM) * E + e) * pp + t, o2 = ((size_t)(1 * NLM + iLM) * E + e) * pp + t;
+#pragma unroll
+      for (int u = 0; u < CB_DB; u++)
+        if (b0 + u < nb) {
+          const double *J = Jaux + (size_t)(b0 + u) * sJaux;
+          acc[u] += c0 * J[o0] + c2 * J[o2];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < CB_DB; u++)
+      if (b0 + u < nb) Jc[(size_t)(b0 + u) * sJc + ((size_t)ij * E + e) * pp + t] = acc[u];
+  }
+}
+
+// W[a][b0 + b] = sum over the compact entries of Pc[a] * Jc[b] = tr(P_a J[P_b]) (both block-banded: the compact layout holds
+//     every entry of J and the entries of P that meet them, each once).  Stage 1: workgroup (slice, a tile, b tile) sums
+//     a 4 x 4 tile over its slice of the entries in a fixed order; stage 2 adds the slices in order.  No atomics.
+constexpr int CB_WT = 4, CB_SLICE = 8192;
+__global__ __launch_bounds__(256) void k_coulomb_energy_part(const double *__restrict__ Pc, int nP, const double *__restrict__ Jc, int nb,
+                                                             size_t nc, double *__restrict__ part /* [slice][nP][nb] */) {
+  __shared__ double red[4][CB_WT * CB_WT];
+  const int a0 = blockIdx.y * CB_WT, b0 = blockIdx.z * CB_WT;
+  const size_t beg = (size_t)blockIdx.x * CB_SLICE, end = min(nc, beg + CB_SLICE);
+  double acc[CB_WT][CB_WT];
+#pragma unroll
+  for (int i = 0; i < CB_WT; i++)
+#pragma unroll
+    for (int j = 0; j < CB_WT; j++) acc[i][j] = 0.0;
+  for (size_t k = beg + threadIdx.x; k < end; k += blockDim.x) {
+    double pv[CB_WT], jv[CB_WT];
+#pragma unroll
+    for (int i = 0; i < CB_WT; i++) pv[i] = (a0 + i < nP) ? Pc[(size_t)(a0 + i) * nc + k] : 0.0;
+#pragma unroll
+    for (int j = 0; j < CB_WT; j++) jv[j] = (b0 + j < nb) ? Jc[(size_t)(b0 + j) * nc + k] : 0.0;
+#pragma unroll
+    for (int i = 0; i < CB_WT; i++)
+#pragma unroll
+      for (int j = 0; j < CB_WT; j++) acc[i][j] += pv[i] * jv[j];
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < CB_WT; i++)
+#pragma unroll
+    for (int j = 0; j < CB_WT; j++) {
+      double v = acc[i][j];
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+      if (lane == 0) red[wave][i * CB_WT + j] = v;
+    }
+  __syncthreads();
+  if (threadIdx.x < CB_WT * CB_WT) {
+    const int i = threadIdx.x / CB_WT, j = threadIdx.x % CB_WT;
+    if (a0 + i < nP && b0 + j < nb)
+      part[((size_t)blockIdx.x * nP + (a0 + i)) * nb + (b0 + j)] =
+          (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  }
+}
+__global__ void k_coulomb_energy_sum(const double *__restrict__ part, int nslice, int nP, int nb, int b0, double *__restrict__ W) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // a * nb + b
+  if (idx >= nP * nb) return;
+  double v = 0.0;
+  for (int s = 0; s < nslice; s++) v += part[(size_t)s * nP * nb + idx];
+  const int a = idx / nb, b = idx % nb;
+  W[(size_t)(b0 + b) * nP + a] = v;  // column-major nP x nP: W(a, b)
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1262,6 +1548,124 @@ void coulomb_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dJ) {
   gather_compact(ctx, basis, dP, a.Pc.p);
   coulomb_compact(ctx, basis, a.Pc.p, a.Jc.p);
   scatter_dense(ctx, basis, a.Jc.p, dJ);
+  HFG_HIP_CHECK(hipGetLastError());
+}
+
+// ---- J for a batch of densities -------------------------------------------------------------------------------------
+struct CoulombBatchAux : Workspace {
+  DevBuf<double> Pc, Jc, Paux, Y, Jaux, part;  // grown to the largest pass seen
+};
+static CoulombBatchAux &batch_aux_for(hfg_basis *basis) { return basis->dev->work.get<CoulombBatchAux>(WS_COULOMB_BATCH); }
+
+constexpr int CB_MAX_NT = 4;  // column tiles of k_coulomb_tei_mfma at most: 16 result registers of 4 doubles per lane
+
+// Densities per pass over the in-element tables.  k_coulomb_tei_mfma keeps the X panel of a pass, round_up4(p^2) rows of 16
+// columns per column tile, in LDS: as many tiles as fit 64 KB (two workgroups per CU), four at most; where not even one
+// fits (p >= 23), as many as fit the 160 KB of a CU.  A tile holds the +M and -M columns of eight densities.
+static int coulomb_batch_chunk(const hfg_dev_tables *t) {
+  const size_t tile = (size_t)((t->p * t->p + 3) & ~3) * 16 * sizeof(double);
+  int nt = (int)std::min<size_t>(CB_MAX_NT, (64 * 1024) / tile);
+  if (nt == 0) nt = (int)std::min<size_t>(CB_MAX_NT, (160 * 1024) / tile);
+  if (nt == 0) throw std::runtime_error("elements of more than 35 nodes: the batched Coulomb kernel's LDS panel does not fit\n");
+  const int forced = helfem::tuning_live().coulomb_batch_chunk;
+  return forced > 0 ? std::min(forced, 8 * nt) : 8 * nt;
+}
+
+template <int NC>
+static void launch_tei_cols(hfg_ctx *ctx, const hfg_dev_tables *t, const FockAux &a, CoulombBatchAux &w, int nb, size_t nbk, int bs) {
+  const int pp = t->p * t->p;
+  hipLaunchKernelGGL(k_coulomb_tei_cols<NC>, dim3(t->Nlm * t->E, t->ntt), dim3(bs), (size_t)pp * NC * sizeof(double), ctx->stream,
+                     t->tei.p, w.Paux.p, 2 * nbk, nb, t->Ntab, t->NLM, t->E, pp, a.lmpos.p, t->lm_tab.p, ctx->shard_rank,
+                     ctx->shard_n, w.Y.p, 4 * nbk);
+}
+template <int NT>
+static void launch_tei_mfma(hfg_ctx *ctx, const hfg_dev_tables *t, const FockAux &a, CoulombBatchAux &w, int nb, size_t nbk) {
+  const int pp = t->p * t->p;
+  const size_t shb = (size_t)((pp + 3) & ~3) * 16 * NT * sizeof(double);
+  if (shb > 64 * 1024)
+    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_coulomb_tei_mfma<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
+  hipLaunchKernelGGL(k_coulomb_tei_mfma<NT>, dim3(t->Nlm * t->E, t->ntt), dim3(256), shb, ctx->stream, t->tei.p, w.Paux.p, 2 * nbk,
+                     nb, t->Ntab, t->NLM, t->E, pp, a.lmpos.p, t->lm_tab.p, ctx->shard_rank, ctx->shard_n, w.Y.p, 4 * nbk);
+}
+
+// J (compact) from P (compact) for the nb <= coulomb_batch_chunk densities of one pass, both with the stride of one
+// compact matrix.  One density goes through the kernels of the single build.
+static void coulomb_batch_compact(hfg_ctx *ctx, hfg_basis *basis, int nb, const double *dPc, double *dJc) {
+  if (nb == 1) return coulomb_compact(ctx, basis, dPc, dJc);
+  hfg_dev_tables *t = tables_of(ctx, basis);
+  FockAux &a = aux_for(ctx, basis);
+  CoulombBatchAux &w = batch_aux_for(basis);
+  const int pp = t->p * t->p;
+  const size_t nc = (size_t)t->A * t->A * t->E * pp, nbk = (size_t)t->NLM * t->E * pp;
+  w.Paux.resize(nb * 2 * nbk);
+  w.Y.resize(nb * 4 * nbk);
+  w.Jaux.resize(nb * 2 * nbk);
+  const int bs = std::min(256, round_up64(pp));
+  const unsigned zg = (nb + CB_DB - 1) / CB_DB;
+  hipLaunchKernelGGL(k_coulomb_ket_batch, dim3(t->NLM, t->E, zg), dim3(bs), 0, ctx->stream, dPc, nc, nb, t->A, t->E, pp, t->lm_off.p,
+                     t->lm_x.p, t->lm_y.p, t->lm_c0.p, t->lm_c2.p, t->NLM, t->LM_ilm.p, ctx->shard_rank, ctx->shard_n, w.Paux.p,
+                     2 * nbk);
+  // n = 2 nb columns (+M and -M of every density): matrix cores from n = 16 on, register-blocked FMAs below
+  {
+    ProfScope ps(ctx, "coulomb_batch_tei");  // the pass over the tables alone (tools/coulomb_batch_time.py)
+    if (nb <= 2) launch_tei_cols<4>(ctx, t, a, w, nb, nbk, bs);
+    else if (nb <= 4) launch_tei_cols<8>(ctx, t, a, w, nb, nbk, bs);
+    else if (nb <= 7) launch_tei_cols<14>(ctx, t, a, w, nb, nbk, bs);
+    else if (nb <= 8) launch_tei_mfma<1>(ctx, t, a, w, nb, nbk);
+    else if (nb <= 16) launch_tei_mfma<2>(ctx, t, a, w, nb, nbk);
+    else if (nb <= 24) launch_tei_mfma<3>(ctx, t, a, w, nb, nbk);
+    else if (nb <= 8 * CB_MAX_NT) launch_tei_mfma<4>(ctx, t, a, w, nb, nbk);
+    else throw std::logic_error("coulomb_batch_compact: pass larger than coulomb_batch_chunk\n");
+  }
+  const int nwave = bs / 64;
+  const size_t shb = (size_t)(4 * t->E * nwave + 4 * t->E + 2 * t->E) * sizeof(double);
+  hipLaunchKernelGGL(k_coulomb_radial_batch, dim3(t->NLM, nb), dim3(bs), shb, ctx->stream, w.Paux.p, 2 * nbk, w.Y.p, 4 * nbk, t->disj.p,
+                     t->LM_ilm.p, t->LM_tab.p, t->LM_fac.p, t->Ntab, t->NLM, t->E, t->p, t->ntt == 4 ? 1 : 0, ctx->shard_rank,
+                     ctx->shard_n, w.Jaux.p, 2 * nbk);
+  hipLaunchKernelGGL(k_coulomb_bra_batch, dim3(t->A * t->A, t->E, zg), dim3(bs), 0, ctx->stream, w.Jaux.p, 2 * nbk, nb, t->A, t->E, pp,
+                     t->NLM, t->pair_off.p, t->ent_iLM.p, t->ent_c0.p, t->ent_c2.p, t->LM_ilm.p, ctx->shard_rank, ctx->shard_n, dJc, nc);
+  HFG_HIP_CHECK(hipGetLastError());
+}
+
+void coulomb_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dJ) {
+  if (nP <= 0) return;
+  hfg_dev_tables *t = tables_of(ctx, basis);
+  CoulombBatchAux &w = batch_aux_for(basis);
+  const size_t nc = (size_t)t->A * t->A * t->E * t->p * t->p, N2 = (size_t)t->N * t->N;
+  const int64_t chunk = coulomb_batch_chunk(t);
+  ProfScope ps(ctx, "coulomb_batch");
+  for (int64_t b0 = 0; b0 < nP; b0 += chunk) {
+    const int nb = (int)std::min(chunk, nP - b0);
+    w.Pc.resize(nb * nc);
+    w.Jc.resize(nb * nc);
+    for (int b = 0; b < nb; b++) gather_compact(ctx, basis, dP + (size_t)(b0 + b) * N2, w.Pc.p + b * nc);
+    coulomb_batch_compact(ctx, basis, nb, w.Pc.p, w.Jc.p);
+    for (int b = 0; b < nb; b++) scatter_dense(ctx, basis, w.Jc.p + b * nc, dJ + (size_t)(b0 + b) * N2);
+  }
+  HFG_HIP_CHECK(hipGetLastError());
+}
+
+// W(a, b) = tr(P_a J[P_b]), nP x nP column-major in HBM, from the compact P and J; not symmetrised
+void coulomb_energy_matrix_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dW) {
+  if (nP <= 0) return;
+  hfg_dev_tables *t = tables_of(ctx, basis);
+  CoulombBatchAux &w = batch_aux_for(basis);
+  const size_t nc = (size_t)t->A * t->A * t->E * t->p * t->p, N2 = (size_t)t->N * t->N;
+  const int64_t chunk = coulomb_batch_chunk(t);
+  const unsigned nslice = (unsigned)((nc + CB_SLICE - 1) / CB_SLICE);
+  ProfScope ps(ctx, "coulomb_batch");
+  w.Pc.resize(nP * nc);  // every P stays: each meets every J
+  w.Jc.resize(std::min(chunk, nP) * nc);
+  w.part.resize((size_t)nslice * nP * std::min(chunk, nP));
+  for (int64_t b = 0; b < nP; b++) gather_compact(ctx, basis, dP + (size_t)b * N2, w.Pc.p + b * nc);
+  for (int64_t b0 = 0; b0 < nP; b0 += chunk) {
+    const int nb = (int)std::min(chunk, nP - b0);
+    coulomb_batch_compact(ctx, basis, nb, w.Pc.p + b0 * nc, w.Jc.p);
+    hipLaunchKernelGGL(k_coulomb_energy_part, dim3(nslice, (unsigned)((nP + CB_WT - 1) / CB_WT), (nb + CB_WT - 1) / CB_WT), dim3(256), 0,
+                       ctx->stream, w.Pc.p, (int)nP, w.Jc.p, nb, nc, w.part.p);
+    hipLaunchKernelGGL(k_coulomb_energy_sum, dim3((unsigned)((nP * nb + 255) / 256)), dim3(256), 0, ctx->stream, w.part.p, (int)nslice,
+                       (int)nP, nb, (int)b0, dW);
+  }
   HFG_HIP_CHECK(hipGetLastError());
 }
 

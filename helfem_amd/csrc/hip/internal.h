@@ -35,6 +35,9 @@ void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha,
 
 // fock.hip
 void coulomb_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dJ);  // fock.hip
+// nP densities, N x N each and one after the other, in one pass over the in-element tables per chunk (hfg_coulomb_batch_devptr)
+void coulomb_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dJ);  // fock.hip
+void coulomb_energy_matrix_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dW);  // fock.hip
 void set_xc_params(hfg_ctx *ctx, int x_func, const double *x_pars, int nx, int c_func, const double *c_pars, int nc);  // fock.hip
 void xc_eval_host(int id, int nspin, size_t np, const double *rho, const double *sigma, const double *lapl, const double *tau,
                   double *exc, double *vrho, double *vsigma, double *vlapl, double *vtau, double thr);  // fock.hip

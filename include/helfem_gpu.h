@@ -202,6 +202,13 @@ int hfg_basis_upload(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft);
 /* ---- per-iteration hot path, host-pointer API (drop-in for the arma::mat signatures) -------- */
 /* arma::mat TwoDBasis::coulomb(const arma::mat & P) const            basis.h:247, basis.cpp:1359 */
 int hfg_coulomb(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *J);
+/* J for nP densities in one pass over the in-element tables (per chunk of densities, DESIGN 3.1 "Batched J"): P and J
+ * hold nP matrices of N x N, column-major, one after the other (density index last); J_b = hfg_coulomb(P_b), each P_b
+ * symmetric.  nP = 0 does nothing and returns 0; nP < 0, a null pointer and a basis without uploaded tables are errors. */
+int hfg_coulomb_batch(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *P, double *J);
+/* W (nP x nP, column-major): W(a, b) = tr(P_a J[P_b]), summed on the device over the element-diagonal blocks, which are
+ * all that J has and all of P that meets them.  Symmetric by the symmetry of the integrals; not symmetrised. */
+int hfg_coulomb_energy_matrix(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *P, double *W);
 /* arma::mat TwoDBasis::exchange(const arma::mat & P) const           basis.h:249, basis.cpp:1532 */
 int hfg_exchange(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *K);
 /* arma::mat atomic::basis::TwoDBasis::rs_exchange(const arma::mat & P) const   TwoDBasis.h:184, TwoDBasis.cpp:1142 */
@@ -309,6 +316,10 @@ int hfg_gemm(hfg_ctx *ctx, int transA, int transB, int64_t m, int64_t n, int64_t
 
 /* ---- device-resident API (pointers into HBM, asynchronous on the context's stream) ---------- */
 int hfg_coulomb_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dJ);
+/* hfg_coulomb_batch on device pointers, honouring the context's shard like hfg_coulomb_dev (the partial J's of the ranks
+ * sum to the whole).  Deliberately not named *_dev: the entries of that name are exactly the plan of
+ * tests/stream_order_worker.py; this entry's stream ordering is tested in tests/test_gpu_coulomb_batch.py. */
+int hfg_coulomb_batch_devptr(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dJ);
 int hfg_exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK);
 int hfg_rs_exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK);
 /* TwoDBasis::exchange(Pa) as the SCF driver calls it (src/diatomic/main.cpp:822, src/atomic/main.cpp:767): the caller has
@@ -479,7 +490,7 @@ int hfg_chk_read_diatomic_basis(hfg_chk *chk, int lpad, hfg_basis **basis);
 /* ---- measurement --------------------------------------------------------------------------- */
 /* When enabled, every kernel family is bracketed by hipEvents on the context's stream; the
  * accumulated device time (ms) and launch count per family can be read back after a synchronize.
- * names: "coulomb", "xc", "exchange" (the full-range build; "exchange_yukawa" / "exchange_erfc": the screened build of
+ * names: "coulomb", "coulomb_batch" (the batched build; "coulomb_batch_tei": its pass over the tables), "xc", "exchange" (the full-range build; "exchange_yukawa" / "exchange_erfc": the screened build of
  * hfg_rs_exchange and of the range-separated hybrids), "eig_reduce", "eig_tridiag", "eig_tridiag_solve",
  * "eig_backtransform", "gemm", "density", "scatter". */
 int hfg_profile_enable(hfg_ctx *ctx, int on);

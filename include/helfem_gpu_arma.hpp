@@ -7,6 +7,7 @@
 //   void TwoDBasis::compute_tei(bool exchange)          src/diatomic/basis.h:205        same
 //   arma::mat TwoDBasis::coulomb(const arma::mat &P)    src/diatomic/basis.h:247        same
 //   arma::mat TwoDBasis::exchange(const arma::mat &P)   src/diatomic/basis.h:249        same
+//   (no counterpart: J for a batch of densities)                                        std::vector<Mat> coulomb(const std::vector<Mat> &)
 //   arma::mat TwoDBasis::overlap/kinetic/nuclear()      src/diatomic/basis.h:227-233    same
 //   std::vector<arma::uvec> TwoDBasis::get_sym_idx(int) src/diatomic/basis.h:303        same (std::vector<std::vector<unsigned long long>>)
 //   void DFTGrid::eval_Fxc(x_func, x_pars, c_func, c_pars, P, H, Exc, Nel, Ekin, thr)             dftgrid.h:179   same
@@ -32,6 +33,7 @@
 #pragma once
 #include "helfem_gpu.h"
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -115,6 +117,21 @@ class BasisBase {
   Mat nuclear() const { return one_body(hfg_basis_nuclear); }
   /// TwoDBasis::coulomb (basis.cpp:1359): throws std::logic_error before compute_tei, like the reference
   Mat coulomb(const Mat &P) const { return two_body(hfg_coulomb, P, "coulomb"); }
+  /// J of every density of a batch in one pass over the in-element tables (hfg_coulomb_batch): out[b] = coulomb(P[b])
+  std::vector<Mat> coulomb(const std::vector<Mat> &P) const {
+    for (const Mat &Pb : P) detail::need_square(Pb, N_, "coulomb");
+    if (!uploaded_) upload(lang_, mang_);
+    const size_t n2 = N_ * N_;
+    std::vector<double> in(P.size() * n2), res(P.size() * n2);
+    for (size_t b = 0; b < P.size(); b++) std::copy(detail::data_of(P[b], 0), detail::data_of(P[b], 0) + n2, in.begin() + b * n2);
+    check(hfg_coulomb_batch(ctx_->handle(), b_, (int64_t)P.size(), in.data(), res.data()));
+    std::vector<Mat> out;
+    for (size_t b = 0; b < P.size(); b++) {
+      out.push_back(Mat(N_, N_));
+      std::copy(res.begin() + b * n2, res.begin() + (b + 1) * n2, detail::data_of(out.back(), 0));
+    }
+    return out;
+  }
   /// TwoDBasis::exchange (basis.cpp:1532)
   Mat exchange(const Mat &P) const { return two_body(hfg_exchange, P, "exchange"); }
   /// TwoDBasis::get_sym_idx (basis.cpp:561 / atomic TwoDBasis.cpp:202)
