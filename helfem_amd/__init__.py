@@ -147,6 +147,13 @@ def lib():
         L.hfg_coulomb_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p]
         L.hfg_coulomb_energy_matrix.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p]
         L.hfg_coulomb_batch_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+        L.hfg_fock_compact_pol_size.restype = ctypes.c_int64
+        L.hfg_fock_compact_pol_size.argtypes = [ctypes.c_void_p]
+        L.hfg_fock_compact_pol_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]
+        L.hfg_fock_finish_pol_devptr.argtypes = [ctypes.c_void_p] * 7
+        L.hfg_eig_gsym_sub_pair_devptr.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_int, c_i64_p, c_i64_p] + [ctypes.c_void_p] * 4
         L.hfg_profile_get.argtypes = [ctypes.c_void_p, ctypes.c_char_p, c_double_p, c_i64_p]
         L.hfg_measure_kernel.argtypes = [ctypes.c_void_p, ctypes.c_char_p, c_double_p, c_i64_p]
         L.hfg_profile_names.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
@@ -1057,10 +1064,28 @@ class DeviceSCFStep(object):
 
     def __init__(self, basis, x_func, c_func, ldft, mdft, nocc, symmetry=1, device=0, rank=0, nranks=1,
                  dens_thr=1e-12, kfrac=0.0, device_tei=False, fock_shard="auto"):
+        self.nocc = int(nocc)
+        self._setup(basis, x_func, c_func, ldft, mdft, symmetry, device, rank, nranks, dens_thr, kfrac, device_tei, fock_shard)
+        f64 = dict(dtype=self.torch.float64, device=self.dev)
+        L, N = lib(), self.N
+        self.Fc = self.torch.zeros(int(L.hfg_fock_compact_size(basis.h)), **f64)
+        self.scal = self.torch.zeros(3, **f64)
+        self.F = self.torch.zeros(N * N, **f64)
+        self.E = self.torch.zeros(N, **f64)
+        self.C = self.torch.zeros(N * N, **f64)
+        self.P = self.torch.zeros(N * N, **f64)
+        nb = int(L.hfg_eig_block_buf_size(len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p)))
+        self.blockbuf = self.torch.zeros(nb, **f64)
+        if self.kfrac != 0.0:
+            self.K = self.torch.zeros(N * N, **f64)
+            self.Pa = self.torch.zeros(N * N, **f64)
+
+    def _setup(self, basis, x_func, c_func, ldft, mdft, symmetry, device, rank, nranks, dens_thr, kfrac, device_tei, fock_shard):
+        """what the restricted and the unrestricted step share: context, shard, tables, symmetry blocks and their declaration"""
         import torch
         self.torch = torch
         self.basis = basis
-        self.x_func, self.c_func, self.nocc, self.thr = int(x_func), int(c_func), int(nocc), float(dens_thr)
+        self.x_func, self.c_func, self.thr = int(x_func), int(c_func), float(dens_thr)
         self.dev = torch.device("cuda", device)
         torch.cuda.set_device(self.dev)
         self.ctx = Context(device, stream=torch.cuda.current_stream(self.dev).cuda_stream)
@@ -1083,29 +1108,18 @@ class DeviceSCFStep(object):
         self.N = N
         self.blocks = basis.get_sym_idx(symmetry)
         self.blk_ptr, self.blk_idx = scf._blocks(self.blocks)
-        f64 = dict(dtype=torch.float64, device=self.dev)
         blockid = np.zeros(N, dtype=np.int32)
         for ib, b in enumerate(self.blocks):
             blockid[b] = ib
         self.blockid = torch.from_numpy(blockid).to(self.dev)
         # fock_finish masks F with these blocks: the build need not compute the shell pairs outside them
         self.ctx.set_fock_blocks(basis, self.blockid.data_ptr())
-        self.Fc = torch.zeros(int(L.hfg_fock_compact_size(basis.h)), **f64)
-        self.scal = torch.zeros(3, **f64)
-        self.F = torch.zeros(N * N, **f64)
-        self.E = torch.zeros(N, **f64)
-        self.C = torch.zeros(N * N, **f64)
-        self.P = torch.zeros(N * N, **f64)
-        nb = int(L.hfg_eig_block_buf_size(len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p)))
-        self.blockbuf = torch.zeros(nb, **f64)
         self.H0 = None
         self.Sinvh = None
         # hybrid functionals: F += kfrac K[Pa] (main.cpp:820-877); K is dense, its shards (output shells j % n == rank) sum
         self.kfrac = float(kfrac)
         self.have_C = False
         if self.kfrac != 0.0:
-            self.K = torch.zeros(N * N, **f64)
-            self.Pa = torch.zeros(N * N, **f64)
             L.hfg_exchange_occ_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                ctypes.c_void_p]
             L.hfg_exchange_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -1190,3 +1204,128 @@ class DeviceSCFStep(object):
 
     def numpy(self, t, shape):
         return t.cpu().numpy().reshape(shape, order="F")
+
+
+class DeviceUSCFStep(DeviceSCFStep):
+    """DeviceSCFStep for an unrestricted iteration (the unrestricted branch of main.cpp:808-900 and 934-971, without DIIS):
+
+        (Pa, Pb) --(J[Pa + Pb] + XC_a | XC_b, compact, sharded)--> all-reduce --> Fa, Fb --(eig blocks of both spins)-->
+        (Ea, Ca), (Eb, Cb) --> Pa' = Ca_occ Ca_occ^T, Pb' likewise
+
+    nocc = (nela, nelb) orbitals per spin; nelb = 0 (one-electron systems) leaves Pb and K[Pb] zero.  Context, shard policy,
+    symmetry blocks and their declaration (set_fock_blocks) are the restricted step's.
+    """
+
+    def __init__(self, basis, x_func, c_func, ldft, mdft, nocc, symmetry=1, device=0, rank=0, nranks=1,
+                 dens_thr=1e-12, kfrac=0.0, device_tei=False, fock_shard="auto"):
+        self.nela, self.nelb = int(nocc[0]), int(nocc[1])
+        if self.nela < 1 or self.nelb < 0:
+            raise ValueError("DeviceUSCFStep: nocc = (nela >= 1, nelb >= 0)")
+        self._setup(basis, x_func, c_func, ldft, mdft, symmetry, device, rank, nranks, dens_thr, kfrac, device_tei, fock_shard)
+        t, N, L = self.torch, self.N, lib()
+        f64 = dict(dtype=t.float64, device=self.dev)
+        self.nc = int(L.hfg_fock_compact_size(basis.h))
+        self.Fc = t.zeros(int(L.hfg_fock_compact_pol_size(basis.h)), **f64)
+        self.scal = t.zeros(3, **f64)
+        for name in ("Pa", "Pb", "Fa", "Fb", "Ca", "Cb"):
+            setattr(self, name, t.zeros(N * N, **f64))
+        self.Ea, self.Eb = t.zeros(N, **f64), t.zeros(N, **f64)
+        if self.nranks > 1:  # the blocks of each spin, solved by their owners
+            nb = int(L.hfg_eig_block_buf_size(len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p)))
+            self.blockbuf_a, self.blockbuf_b = t.zeros(nb, **f64), t.zeros(nb, **f64)
+        if self.kfrac != 0.0:  # one buffer, so that one all-reduce serves both spins
+            self.K = t.zeros(2 * N * N, **f64)
+            self.Ka, self.Kb = self.K[:N * N], self.K[N * N:]
+
+    def _spins(self):
+        return ((self.Pa, self.Fa, self.Ea, self.Ca, self.nela), (self.Pb, self.Fb, self.Eb, self.Cb, self.nelb))
+
+    def set_density(self, Pa, Pb, Ca=None, Cb=None):
+        """spin densities P_s = C_s,occ C_s,occ^T; Ca, Cb (optional, both or neither): the orbitals they were formed from,
+        handed to the exact exchange as their factors"""
+        as_dev = lambda M: self.torch.from_numpy(np.asfortranarray(M).ravel(order="F").copy())
+        self.Pa.copy_(as_dev(Pa))
+        self.Pb.copy_(as_dev(Pb))
+        self.have_C = Ca is not None and (Cb is not None or self.nelb == 0)
+        if self.have_C:
+            self.Ca[:self.N * self.nela].copy_(as_dev(Ca[:, :self.nela]))
+            if self.nelb:
+                self.Cb[:self.N * self.nelb].copy_(as_dev(Cb[:, :self.nelb]))
+
+    def exchange(self):
+        """K[Pa] and K[Pb] (basis.exchange of main.cpp:822-829) into self.Ka, self.Kb"""
+        for (P, _, _, C, nocc), K in zip(self._spins(), (self.Ka, self.Kb)):
+            if nocc == 0:
+                K.zero_()
+            elif self.have_C:
+                _check(lib().hfg_exchange_occ_dev(self.ctx.h, self.basis.h, self._ptr(P), self._ptr(C), ctypes.c_int64(nocc),
+                                                  self._ptr(K)))
+            else:
+                _check(lib().hfg_exchange_dev(self.ctx.h, self.basis.h, self._ptr(P), self._ptr(K)))
+
+    def fock_partial(self):
+        _check(lib().hfg_fock_compact_pol_devptr(self.ctx.h, self.basis.h, self.x_func, self.c_func, self._ptr(self.Pa),
+                                                 self._ptr(self.Pb), self._ptr(self.Fc), self._ptr(self.scal), self.thr))
+
+    def fock_finish(self):
+        _check(lib().hfg_fock_finish_pol_devptr(self.ctx.h, self.basis.h, self._ptr(self.Fc), self._ptr(self.H0),
+                                                self._ptr(self.blockid), self._ptr(self.Fa), self._ptr(self.Fb)))
+
+    def eig_pair(self):
+        """both spins' blocks in one batch (one rank)"""
+        _check(lib().hfg_eig_gsym_sub_pair_devptr(self.ctx.h, ctypes.c_int64(self.N), self._ptr(self.Fa), self._ptr(self.Fb),
+                                                  self._ptr(self.Sinvh), len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p),
+                                                  self.blk_idx.ctypes.data_as(c_i64_p), self._ptr(self.Ea), self._ptr(self.Ca),
+                                                  self._ptr(self.Eb), self._ptr(self.Cb)))
+
+    def eig_partial(self):
+        for (_, F, _, _, _), buf in zip(self._spins(), (self.blockbuf_a, self.blockbuf_b)):
+            _check(lib().hfg_eig_blocks_dev(self.ctx.h, ctypes.c_int64(self.N), self._ptr(F), self._ptr(self.Sinvh),
+                                            len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p),
+                                            self.blk_idx.ctypes.data_as(c_i64_p), self._ptr(buf)))
+
+    def eig_finish(self):
+        for (_, _, E, C, _), buf in zip(self._spins(), (self.blockbuf_a, self.blockbuf_b)):
+            _check(lib().hfg_eig_assemble_dev(self.ctx.h, ctypes.c_int64(self.N), len(self.blocks),
+                                              self.blk_ptr.ctypes.data_as(c_i64_p), self.blk_idx.ctypes.data_as(c_i64_p),
+                                              self._ptr(buf), self._ptr(E), self._ptr(C)))
+
+    def density(self):
+        for P, _, _, C, nocc in self._spins():
+            if nocc == 0:
+                P.zero_()
+                continue
+            _check(lib().hfg_form_density_dev(self.ctx.h, ctypes.c_int64(self.N), ctypes.c_int64(self.N), self._ptr(C),
+                                              ctypes.c_int64(nocc), self._ptr(P)))
+
+    def step(self, allreduce=None, exchange_blocks=None):
+        """one iteration, with the restricted step's policy for allreduce and exchange_blocks; one rank solves the blocks of
+        both spins in one batch"""
+        shard_fock = self.nranks > 1 and self.fock_shard == "always"
+        if self.nranks > 1 and not shard_fock:
+            self.ctx.set_shard(0, 1)  # every rank builds the whole J + XC: no collective
+        self.fock_partial()
+        if self.nranks > 1 and not shard_fock:
+            self.ctx.set_shard(self.rank, self.nranks)
+        if allreduce is not None and (shard_fock or self.nranks == 1):
+            allreduce(self.Fc)
+            allreduce(self.scal)
+        self.fock_finish()
+        if self.kfrac != 0.0:
+            self.exchange()
+            if allreduce is not None:
+                allreduce(self.K)
+            self.Fa.add_(self.Ka, alpha=self.kfrac)
+            self.Fb.add_(self.Kb, alpha=self.kfrac)
+        if self.nranks == 1:
+            self.eig_pair()
+        else:
+            self.eig_partial()
+            for buf in (self.blockbuf_a, self.blockbuf_b):
+                if exchange_blocks is not None:
+                    exchange_blocks(buf, len(self.blocks))
+                elif allreduce is not None:
+                    allreduce(buf)
+            self.eig_finish()
+        self.density()
+        self.have_C = True  # Ca, Cb now hold the orbitals the densities were formed from

@@ -784,6 +784,33 @@ int hfg_fock_finish_dev(hfg_ctx *ctx, hfg_basis *b, const double *dFc, const dou
   HFG_TRY fock_finish_dev(ctx, b, dFc, dH0, dBlockId, dF);
   HFG_CATCH
 }
+int64_t hfg_fock_compact_pol_size(hfg_basis *b) { return 2 * (int64_t)fock_compact_size(b); }
+int hfg_fock_compact_pol_devptr(hfg_ctx *ctx, hfg_basis *b, int x_func, int c_func, const double *dPa, const double *dPb,
+                                double *dFc, double *dScal, double thr) {
+  HFG_TRY
+  if (!ctx || !b) throw std::logic_error("hfg_fock_compact_pol_devptr: null context or basis\n");
+  if (!dPa || !dPb || !dFc || !dScal) throw std::logic_error("hfg_fock_compact_pol_devptr: null device pointer\n");
+  fock_compact_pol_dev(ctx, b, x_func, c_func, dPa, dPb, dFc, dScal, thr);
+  HFG_CATCH
+}
+int hfg_fock_finish_pol_devptr(hfg_ctx *ctx, hfg_basis *b, const double *dFc, const double *dH0, const int *dBlockId,
+                               double *dFa, double *dFb) {
+  HFG_TRY
+  if (!ctx || !b) throw std::logic_error("hfg_fock_finish_pol_devptr: null context or basis\n");
+  if (!dFc || !dFa || !dFb) throw std::logic_error("hfg_fock_finish_pol_devptr: null device pointer\n");
+  fock_finish_pol_dev(ctx, b, dFc, dH0, dBlockId, dFa, dFb);
+  HFG_CATCH
+}
+int hfg_eig_gsym_sub_pair_devptr(hfg_ctx *ctx, int64_t N, const double *dFa, const double *dFb, const double *dSinvh, int nblk,
+                                 const int64_t *blk_ptr, const int64_t *blk_idx, double *dEa, double *dCa, double *dEb,
+                                 double *dCb) {
+  HFG_TRY
+  if (!ctx) throw std::logic_error("hfg_eig_gsym_sub_pair_devptr: null context\n");
+  if (!dFa || !dFb || !dSinvh || !blk_ptr || !blk_idx || !dEa || !dCa || !dEb || !dCb)
+    throw std::logic_error("hfg_eig_gsym_sub_pair_devptr: null pointer\n");
+  eig_gsym_sub_pair_dev(ctx, (int)N, dFa, dFb, dSinvh, nblk, blk_ptr, blk_idx, dEa, dCa, dEb, dCb);
+  HFG_CATCH
+}
 int hfg_ctx_set_fock_blocks(hfg_ctx *ctx, hfg_basis *b, const int *blockid_dev) {
   HFG_TRY
   if (!ctx || !b) throw std::logic_error("hfg_ctx_set_fock_blocks: null context or basis");

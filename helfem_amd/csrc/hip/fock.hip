@@ -143,6 +143,93 @@ __global__ void k_add_inplace(double *__restrict__ a, const double *__restrict__
   for (; i < n; i += stride) a[i] += b[i];
 }
 
+// The gather of an unrestricted build: both spins in one pass, each as k_gather_compact gives it, with their sum
+// Xt = Pa + Pb (the one add that the dense sum in front of coulomb_dev makes) and on[blk] = the block of EITHER spin holds
+// something other than zeros -- a superset of what Xt alone would flag, so a skipped entry still only multiplies zeros
+__global__ void k_gather_compact_pol(const double *__restrict__ Pa, const double *__restrict__ Pb, int N, int A, int R, int E,
+                                     int p, const int *__restrict__ shell_off, const int *__restrict__ shell_skip,
+                                     double *__restrict__ Xa, double *__restrict__ Xb, double *__restrict__ Xt,
+                                     int *__restrict__ on) {
+  int blk = blockIdx.x;  // (x*A+y)*E+e
+  int e = blk % E;
+  int xy = blk / E;
+  int y = xy % A, x = xy / A;
+  int pp = p * p;
+  int live = 0;
+  for (int t = threadIdx.x; t < pp; t += blockDim.x) {
+    int i = t % p, j = t / p;
+    int ni = e * (p - 1) + i, nj = e * (p - 1) + j;
+    double va = 0.0, vb = 0.0;
+    bool ok = (ni < R) && (nj < R) && !(shell_skip[x] && ni == 0) && !(shell_skip[y] && nj == 0);
+    if (ok) {
+      size_t o = (size_t)(shell_off[y] + nj) * N + (shell_off[x] + ni);
+      va = Pa[o];
+      vb = Pb[o];
+    }
+    size_t c = (size_t)blk * pp + t;
+    Xa[c] = va;
+    Xb[c] = vb;
+    Xt[c] = va + vb;
+    live |= (va != 0.0) | (vb != 0.0);  // true for a NaN in either spin
+  }
+  if (on) {
+    live = __syncthreads_or(live);
+    if (threadIdx.x == 0) on[blk] = live;
+  }
+}
+
+// Fc[0 : nc] = J + XC_a, Fc[nc : 2 nc] = J + XC_b; J arrives in the second slab and is read once
+__global__ void k_fock_combine_pol(double *__restrict__ Fc, const double *__restrict__ Xa, const double *__restrict__ Xb,
+                                   size_t nc) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < nc; i += stride) {
+    double j = Fc[nc + i];
+    Fc[i] = j + Xa[i];
+    Fc[nc + i] = j + Xb[i];
+  }
+}
+
+// k_fock_finish for the two slabs of an unrestricted build: H0, the block ids and the index maps are read once, and each
+// spin is summed in the order of k_fock_finish
+__global__ void k_fock_finish_pol(const double *__restrict__ Xc, size_t nc, const double *__restrict__ H0,
+                                  const int *__restrict__ blockid, int N, int A, int R, int E, int p,
+                                  const int *__restrict__ pure_shell, const int *__restrict__ pure_n,
+                                  double *__restrict__ outa, double *__restrict__ outb) {
+  int row = blockIdx.x * 64 + (threadIdx.x & 63);
+  int col = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= N || col >= N) return;
+  size_t o = (size_t)col * N + row;
+  if (blockid && blockid[row] != blockid[col]) {
+    outa[o] = 0.0;
+    outb[o] = 0.0;
+    return;
+  }
+  int x = pure_shell[row], n = pure_n[row];
+  int y = pure_shell[col], m = pure_n[col];
+  int pm = p - 1, pp = p * p;
+  int e1 = n / pm, f1 = m / pm;
+  double va = H0 ? H0[o] : 0.0, vb = va;
+  const double *base = Xc + (size_t)(x * A + y) * E * pp;
+  for (int ce = 0; ce < 2; ce++) {
+    int e = e1 - ce;
+    if (e < 0 || e >= E) continue;
+    int i = n - e * pm;
+    if (i < 0 || i > pm) continue;
+    for (int cf = 0; cf < 2; cf++) {
+      int f = f1 - cf;
+      if (f != e) continue;
+      int j = m - f * pm;
+      if (j < 0 || j > pm) continue;
+      size_t c = (size_t)e * pp + j * p + i;
+      va += base[c];
+      vb += base[nc + c];
+    }
+  }
+  outa[o] = va;
+  outb[o] = vb;
+}
+
 // -------------------------------------------------------------------------------------------------
 // Coulomb
 // -------------------------------------------------------------------------------------------------
@@ -1584,7 +1671,7 @@ static size_t xc_density_radial_lds(int p, int nq, int do_lapl = 0) {
 
 struct FockAux : Workspace {
   DevBuf<int> pure_shell, pure_n, lmpos;
-  DevBuf<double> Pc, Jc, Pc2, Jc2, Paux, Y, Jaux, D0, D1, D2, D3, V, Fo, GA, GB, GC, GL, partial, scal;
+  DevBuf<double> Pc, Jc, Pc2, Jc2, Pc3, Paux, Y, Jaux, D0, D1, D2, D3, V, Fo, GA, GB, GC, GL, partial, scal;
   DevBuf<int> on, gon, chan;  // density flags of the last flagged gather (FockSkip)
 };
 
@@ -1642,6 +1729,23 @@ static void gather_compact(hfg_ctx *ctx, hfg_basis *basis, const double *dP, dou
                      t->p, t->shell_off.p, t->shell_skip.p, dPc, (int *)nullptr);
 }
 
+// The flags that follow from on[] (filled by the gather just enqueued on the context's stream): the m-group flags, the
+// buffer of K1's channel flags, and the caller's output-side flags
+static void skip_flags_behind_on(hfg_ctx *ctx, hfg_dev_tables *t, FockAux &a, bool with_need, FockSkip &sk) {
+  sk.on = a.on.p;
+  sk.chan = a.chan.p;
+  if (t->have_xc) {
+    a.gon.resize((size_t)t->E * t->G * t->G);
+    hipLaunchKernelGGL(k_skip_groups, dim3(t->E, t->G * t->G), dim3(256), 0, ctx->stream, a.on.p, t->A, t->E, t->G, t->grp_off.p,
+                       t->grp_shell.p, a.gon.p);
+    sk.gon = a.gon.p;
+  }
+  if (with_need && ctx->fock_need_tables == t && ctx->fock_need_A == t->A) {
+    sk.need = ctx->fock_need.p;
+    if (t->have_xc && ctx->fock_need_G == t->G) sk.gneed = ctx->fock_gneed.p;
+  }
+}
+
 // The gather of a build that skips (HELFEM_FOCK_SKIP, read at every call): it also writes the density flags, into the
 // table set's workspace and on the context's stream, so whatever is ordered behind Pc is ordered behind the flags.  The
 // output-side flags are the context's, if hfg_ctx_set_fock_blocks gave it some for these very tables and with_need asks.
@@ -1657,18 +1761,23 @@ static FockSkip gather_compact_flagged(hfg_ctx *ctx, hfg_basis *basis, const dou
   a.chan.resize((size_t)t->NLM * t->E);
   hipLaunchKernelGGL(k_gather_compact, dim3(t->A * t->A * t->E), dim3(256), 0, ctx->stream, dP, t->N, t->A, t->R, t->E,
                      t->p, t->shell_off.p, t->shell_skip.p, dPc, a.on.p);
-  sk.on = a.on.p;
-  sk.chan = a.chan.p;
-  if (t->have_xc) {
-    a.gon.resize((size_t)t->E * t->G * t->G);
-    hipLaunchKernelGGL(k_skip_groups, dim3(t->E, t->G * t->G), dim3(256), 0, ctx->stream, a.on.p, t->A, t->E, t->G, t->grp_off.p,
-                       t->grp_shell.p, a.gon.p);
-    sk.gon = a.gon.p;
+  skip_flags_behind_on(ctx, t, a, with_need, sk);
+  return sk;
+}
+
+// gather_compact_flagged for an unrestricted build: Pa, Pb and Pa + Pb into Pc, Pc2 and Pc3, the flags of the union of the spins
+static FockSkip gather_compact_pol_flagged(hfg_ctx *ctx, hfg_basis *basis, const double *dPa, const double *dPb, bool with_need) {
+  hfg_dev_tables *t = basis->dev;
+  FockAux &a = aux_for(ctx, basis);
+  FockSkip sk;
+  const bool skip = helfem::tuning_live().fock_skip;
+  if (skip) {
+    a.on.resize((size_t)t->A * t->A * t->E);
+    a.chan.resize((size_t)t->NLM * t->E);
   }
-  if (with_need && ctx->fock_need_tables == t && ctx->fock_need_A == t->A) {
-    sk.need = ctx->fock_need.p;
-    if (t->have_xc && ctx->fock_need_G == t->G) sk.gneed = ctx->fock_gneed.p;
-  }
+  hipLaunchKernelGGL(k_gather_compact_pol, dim3(t->A * t->A * t->E), dim3(256), 0, ctx->stream, dPa, dPb, t->N, t->A, t->R, t->E,
+                     t->p, t->shell_off.p, t->shell_skip.p, a.Pc.p, a.Pc2.p, a.Pc3.p, skip ? a.on.p : (int *)nullptr);
+  if (skip) skip_flags_behind_on(ctx, t, a, with_need, sk);
   return sk;
 }
 
@@ -2070,22 +2179,30 @@ void xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const d
   HFG_HIP_CHECK(hipGetLastError());
 }
 
-// spin-polarised XC: Hc_a, Hc_b (compact) from Pc_a, Pc_b (compact); dScal = (Exc, Nel, 0)
+// dynamic LDS of k_xc_grid_pol and rowc, the theta rows that go through it per pass
+static size_t xc_grid_pol_lds(const hfg_dev_tables *t, const XCPlan &pl, int *rowc) {
+  const int npot2 = pl.do_lapl ? 12 : (pl.do_tau ? 10 : 8);  // LDS potential planes, both spins
+  *rowc = t->ntheta;
+  while ((size_t)(npot2 * *rowc * t->nphi + 3 * 4) * sizeof(double) > tuning().xc_lds_limit && *rowc > 1) *rowc = (*rowc + 1) / 2;
+  const size_t shb = (size_t)(npot2 * *rowc * t->nphi + 3 * 4) * sizeof(double);
+  if (shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the polarised grid kernel's LDS tile");
+  return shb;
+}
+
+// spin-polarised XC: Hc_a, Hc_b (compact) from Pc_a, Pc_b (compact); dScal = (Exc, Nel, 0).  sk: flags that hold for both
+// spins (gather_compact_pol_flagged); xc_fock_pol_dev passes none
 static void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPca, const double *dPcb,
-                           double *dHca, double *dHcb, double *dScal, double thr) {
+                           double *dHca, double *dHcb, double *dScal, double thr, const FockSkip &sk = FockSkip()) {
   hfg_dev_tables *t = tables_of(ctx, basis);
   const XCPlan pl = xc_plan(t, x_func, c_func, thr);
   FockAux &a = aux_for(ctx, basis);
   const int npl = pl.do_lapl ? 6 : (pl.do_tau ? 5 : 3);  // planes of V and Fo per spin
   xc_buffers(a, pl, 2 * npl);
-  for (int sp = 0; sp < 2; sp++) xc_density_stage(ctx, t, a, pl, sp ? dPcb : dPca, a.V.p + (size_t)sp * npl * pl.nv);
-  const int npot2 = pl.do_lapl ? 12 : (pl.do_tau ? 10 : 8);  // LDS potential planes, both spins
-  int rowc = t->ntheta;  // theta rows per pass through LDS
-  while ((size_t)(npot2 * rowc * t->nphi + 3 * 4) * sizeof(double) > tuning().xc_lds_limit && rowc > 1) rowc = (rowc + 1) / 2;
-  size_t shb = (size_t)(npot2 * rowc * t->nphi + 3 * 4) * sizeof(double);
-  if (shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the polarised grid kernel's LDS tile");
+  for (int sp = 0; sp < 2; sp++) xc_density_stage(ctx, t, a, pl, sp ? dPcb : dPca, a.V.p + (size_t)sp * npl * pl.nv, sk);
+  int rowc;
+  const size_t shb = xc_grid_pol_lds(t, pl, &rowc);
   launch_xc_grid(ctx, t, a, pl, k_xc_grid_pol<true>, k_xc_grid_pol<false>, shb, x_func, c_func, rowc);
-  for (int sp = 0; sp < 2; sp++) xc_fock_stage(ctx, t, a, pl, a.Fo.p + (size_t)sp * npl * pl.nv, sp ? dHcb : dHca);
+  for (int sp = 0; sp < 2; sp++) xc_fock_stage(ctx, t, a, pl, a.Fo.p + (size_t)sp * npl * pl.nv, sp ? dHcb : dHca, sk);
   hipLaunchKernelGGL(k_xc_sum_partials, dim3(1), dim3(64), 0, ctx->stream, a.partial.p, pl.NQ, dScal);
   HFG_HIP_CHECK(hipGetLastError());
 }
@@ -2236,6 +2353,84 @@ void fock_finish_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const do
   dim3 grid((t->N + 63) / 64, (t->N + 3) / 4);
   hipLaunchKernelGGL(k_fock_finish, grid, dim3(256), 0, ctx->stream, dFc, dH0, dBlockId, t->N, t->A, t->R, t->E, t->p,
                      a.pure_shell.p, a.pure_n.p, dF);
+  HFG_HIP_CHECK(hipGetLastError());
+}
+
+// fock_compact_dev for an unrestricted build: this shard's part of Fc[0 : nc] = J[Pa + Pb] + XC_a and
+// Fc[nc : 2 nc] = J[Pa + Pb] + XC_b (nc = fock_compact_size), dScal = partial (Exc, Nel, Ekin); Hartree-Fock: both slabs J
+void fock_compact_pol_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPa, const double *dPb,
+                          double *dFc, double *dScal, double thr) {
+  hfg_dev_tables *t = tables_of(ctx, basis);
+  const bool with_xc = x_func > 0 || c_func > 0;
+  if (with_xc) {  // what the XC build would refuse is refused before the first launch
+    int rowc;
+    (void)xc_grid_pol_lds(t, xc_plan(t, x_func, c_func, thr), &rowc);
+  }
+  FockAux &a = aux_for(ctx, basis);
+  const size_t nc = fock_compact_size(basis);
+  a.Pc.resize(nc);
+  a.Pc2.resize(nc);
+  a.Pc3.resize(nc);
+  double *dJc = dFc + nc;  // J goes to the second slab; k_fock_combine_pol spreads it
+  if (!with_xc) {
+    ProfScope ps(ctx, "coulomb");
+    const FockSkip sk = gather_compact_pol_flagged(ctx, basis, dPa, dPb, true);
+    coulomb_compact(ctx, basis, a.Pc3.p, dJc, sk);
+    HFG_HIP_CHECK(hipMemcpyAsync(dFc, dJc, nc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    HFG_HIP_CHECK(hipMemsetAsync(dScal, 0, 3 * sizeof(double), ctx->stream));
+    return;
+  }
+  a.Jc.resize(nc);
+  a.Jc2.resize(nc);
+  // J beside the XC kernels on the side stream, as in fock_compact_dev
+  if (tuning().fock_overlap && !ctx->avoid_side) {
+    hipStream_t main = ctx->stream, q = ctx->side();
+    const FockSkip sk = gather_compact_pol_flagged(ctx, basis, dPa, dPb, true);
+    HFG_HIP_CHECK(hipEventRecord(ctx->side_ev[0], main));
+    HFG_HIP_CHECK(hipStreamWaitEvent(q, ctx->side_ev[0], 0));
+    ctx->stream = q;
+    try {
+      ProfScope ps(ctx, "coulomb");
+      coulomb_compact(ctx, basis, a.Pc3.p, dJc, sk);
+    } catch (...) {
+      ctx->stream = main;
+      throw;
+    }
+    ctx->stream = main;
+    HFG_HIP_CHECK(hipEventRecord(ctx->side_ev[1], q));
+    ProfScope ps(ctx, "xc");
+    try {
+      xc_compact_pol(ctx, basis, x_func, c_func, a.Pc.p, a.Pc2.p, a.Jc.p, a.Jc2.p, dScal, thr, sk);
+    } catch (...) {  // J is under way into dFc: whatever the caller enqueues after the error comes behind it
+      (void)hipStreamWaitEvent(main, ctx->side_ev[1], 0);
+      throw;
+    }
+    HFG_HIP_CHECK(hipStreamWaitEvent(main, ctx->side_ev[1], 0));
+    hipLaunchKernelGGL(k_fock_combine_pol, dim3(2048), dim3(256), 0, ctx->stream, dFc, a.Jc.p, a.Jc2.p, nc);
+    HFG_HIP_CHECK(hipGetLastError());
+    return;
+  }
+  FockSkip sk;
+  {
+    ProfScope ps(ctx, "coulomb");
+    sk = gather_compact_pol_flagged(ctx, basis, dPa, dPb, true);
+    coulomb_compact(ctx, basis, a.Pc3.p, dJc, sk);
+  }
+  ProfScope ps(ctx, "xc");
+  xc_compact_pol(ctx, basis, x_func, c_func, a.Pc.p, a.Pc2.p, a.Jc.p, a.Jc2.p, dScal, thr, sk);
+  hipLaunchKernelGGL(k_fock_combine_pol, dim3(2048), dim3(256), 0, ctx->stream, dFc, a.Jc.p, a.Jc2.p, nc);
+  HFG_HIP_CHECK(hipGetLastError());
+}
+
+// fock_finish_dev for the two slabs of fock_compact_pol_dev, one launch
+void fock_finish_pol_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const double *dH0, const int *dBlockId,
+                         double *dFa, double *dFb) {
+  hfg_dev_tables *t = tables_of(ctx, basis);
+  FockAux &a = aux_for(ctx, basis);
+  ProfScope ps(ctx, "scatter");
+  dim3 grid((t->N + 63) / 64, (t->N + 3) / 4);
+  hipLaunchKernelGGL(k_fock_finish_pol, grid, dim3(256), 0, ctx->stream, dFc, fock_compact_size(basis), dH0, dBlockId, t->N, t->A,
+                     t->R, t->E, t->p, a.pure_shell.p, a.pure_n.p, dFa, dFb);
   HFG_HIP_CHECK(hipGetLastError());
 }
 

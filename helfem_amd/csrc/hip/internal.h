@@ -56,6 +56,11 @@ void fock_compact_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, co
                       double thr);  // fock.hip
 void fock_finish_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const double *dH0, const int *dBlockId,
                      double *dF);  // fock.hip
+// the unrestricted fused build: two slabs of fock_compact_size() doubles, J[Pa + Pb] + XC_a then J[Pa + Pb] + XC_b
+void fock_compact_pol_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPa, const double *dPb,
+                          double *dFc, double *dScal, double thr);  // fock.hip
+void fock_finish_pol_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const double *dH0, const int *dBlockId,
+                         double *dFa, double *dFb);  // fock.hip
 
 // exchange.hip, exchange_lr.hip
 void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, bool rs = false, const double *Lknown = nullptr,

@@ -341,6 +341,25 @@ int hfg_fock_compact_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func,
                          double *dScal, double dens_thr);
 int hfg_fock_finish_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const double *dH0, const int *dBlockId,
                         double *dF);
+/* The fused build of an unrestricted iteration (main.cpp:808-900, unrestricted branch).  dFc holds
+ * hfg_fock_compact_pol_size() = 2 * hfg_fock_compact_size() doubles: this shard's J[Pa + Pb] + XC_a, then J[Pa + Pb] + XC_b,
+ * each in the layout of hfg_fock_compact_dev; dScal its partial (Exc, Nel, Ekin).  x_func <= 0 and c_func <= 0 (Hartree-Fock):
+ * both slabs are J and dScal is zero.  The shard, hfg_ctx_set_fock_blocks, HELFEM_FOCK_SKIP and HELFEM_FOCK_OVERLAP act as on
+ * hfg_fock_compact_dev; a shell pair is skipped on the density side only if its block is zero in BOTH spins.  After the
+ * all-reduce of dFc and dScal, hfg_fock_finish_pol_devptr forms Fa and Fb = enforce_fock_symmetry(H0 + slab) in one pass (dH0,
+ * dBlockId may be NULL), each bitwise what hfg_fock_finish_dev gives on its slab.  External functional parameters: those of
+ * the context, as for hfg_fock_compact_dev.  hfg_eig_gsym_sub_pair_devptr is hfg_eig_gsym_sub_pair on device pointers
+ * (blk_ptr and blk_idx stay host pointers; one device, whatever the shard).  A null pointer is status 1.
+ * Deliberately not named *_dev, like hfg_coulomb_batch_devptr: the entries of that name are exactly the plan of
+ * tests/stream_order_worker.py; the stream ordering of these three is tested in tests/test_gpu_fock_pol.py. */
+int64_t hfg_fock_compact_pol_size(hfg_basis *basis); /* needs no device */
+int hfg_fock_compact_pol_devptr(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPa, const double *dPb,
+                                double *dFc, double *dScal /* 3 */, double dens_thr);
+int hfg_fock_finish_pol_devptr(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, const double *dH0, const int *dBlockId,
+                               double *dFa, double *dFb);
+int hfg_eig_gsym_sub_pair_devptr(hfg_ctx *ctx, int64_t N, const double *dFa, const double *dFb, const double *dSinvh, int nblk,
+                                 const int64_t *blk_ptr, const int64_t *blk_idx, double *dEa, double *dCa, double *dEb,
+                                 double *dCb);
 /* Which entries of the compact buffer the caller reads.  blockid_dev: the device array hfg_fock_finish_dev takes as
  * dBlockId (symmetry block of every basis function), or NULL to clear.  A set-up call (it synchronises the device and
  * copies the array to the host): from it the context derives the shell pairs (x, y) in which some function of x and some
