@@ -147,6 +147,13 @@ def lib():
         L.hfg_coulomb_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p]
         L.hfg_coulomb_energy_matrix.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p]
         L.hfg_coulomb_batch_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+        for name in ("hfg_exchange_batch", "hfg_rs_exchange_batch"):
+            getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p]
+        for name in ("hfg_exchange_batch_devptr", "hfg_rs_exchange_batch_devptr"):
+            getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+        L.hfg_exchange_occ_batch_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                    c_i64_p, ctypes.c_int64, ctypes.c_void_p]
+        L.hfg_exchange_batch_plan.argtypes = [ctypes.c_int64, c_int_p, ctypes.c_int, c_int_p, c_int_p]
         L.hfg_fock_compact_pol_size.restype = ctypes.c_int64
         L.hfg_fock_compact_pol_size.argtypes = [ctypes.c_void_p]
         L.hfg_fock_compact_pol_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -469,6 +476,31 @@ class TwoDBasis(object):
                                               ctypes.c_void_p(out.data_ptr())))
         return out
 
+    def exchange_batch(self, Ps, ctx=None, _entry="hfg_exchange_batch"):
+        """K[P_b] for every density of Ps (as coulomb_batch takes them) with the exchange-ordered element tables read once
+        per chunk of densities (hfg_exchange_batch).  Returns an array (nP, Nbf, Nbf): out[b] is bitwise exchange(Ps[b])."""
+        ctx, buf = self._batch(Ps, ctx)
+        N, out = self.Nbf(), np.zeros_like(buf)
+        _check(getattr(lib(), _entry)(ctx.h, self.h, len(buf), _p(buf), _p(out)))
+        return out.reshape(len(buf), N, N).transpose(0, 2, 1)
+
+    def exchange_batch_torch(self, dP, out=None, ctx=None, rs=False):
+        """hfg_exchange_batch_devptr (rs: hfg_rs_exchange_batch_devptr) on torch tensors in HBM, laid out and checked as
+        coulomb_batch_torch does.  The build is enqueued on the context's stream and honours its shard; returns `out`."""
+        import torch
+        if ctx is not None and self._uploaded is None:
+            self.upload(ctx=ctx)
+        ctx = ctx or self._ensure()
+        N2 = self.Nbf() ** 2
+        if out is None:
+            out = torch.empty_like(dP)
+        for t in (dP, out):
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() % N2 or t.numel() != dP.numel():
+                raise ValueError("exchange_batch_torch: contiguous float64 device tensors of nP * Nbf * Nbf elements")
+        f = lib().hfg_rs_exchange_batch_devptr if rs else lib().hfg_exchange_batch_devptr
+        _check(f(ctx.h, self.h, dP.numel() // N2, ctypes.c_void_p(dP.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+        return out
+
     def model_potential(self, p1, p2=None):
         """TwoDGrid::model_potential(p1, p2) / atomic TwoDBasis::model_potential(p1): p = (kind, Z[, d[, H]]) with kind
         0 point nucleus, 1 GSZ (screening length d), 3 Thomas-Fermi.  The diatomic form needs upload(ldft, mdft)."""
@@ -589,6 +621,11 @@ class AtomicTwoDBasis(TwoDBasis):
         device=True, on the GPU of ctx (hfg_compute_rs_tei_dev)"""
         self._compute_rs(2, mu, device, ctx)
 
+    def rs_exchange_batch(self, Ps, ctx=None):
+        """rs_exchange(P_b) for every density of Ps in one pass over the range-separated tables per chunk (hfg_rs_exchange_batch;
+        an erfc basis loops over the single build inside the entry)"""
+        return self.exchange_batch(Ps, ctx=ctx, _entry="hfg_rs_exchange_batch")
+
     def rs_exchange(self, P):
         """TwoDBasis::rs_exchange (src/atomic/TwoDBasis.cpp:1142) on the GPU"""
         ctx = self._ensure()
@@ -596,6 +633,16 @@ class AtomicTwoDBasis(TwoDBasis):
         K = np.zeros_like(P, order="F")
         _check(lib().hfg_rs_exchange(ctx.h, self.h, _p(P), _p(K)))
         return K
+
+
+def exchange_batch_plan(ranks, max_members=0):
+    """chunks of a batched exchange build (hfg_exchange_batch_plan, no device): (chunk_of, nchunks) for the ranks of the
+    batch's densities; chunk_of[b] = -1 for a zero matrix.  max_members = 0: HELFEM_EXCHANGE_BATCH_CHUNK's value."""
+    r = np.ascontiguousarray(ranks, dtype=np.int32)
+    out = np.full(len(r), -2, dtype=np.int32)
+    n = ctypes.c_int(0)
+    _check(lib().hfg_exchange_batch_plan(len(r), r.ctypes.data_as(c_int_p), int(max_members), out.ctypes.data_as(c_int_p), ctypes.byref(n)))
+    return out.tolist(), n.value
 
 
 class DFTGrid(object):
@@ -1233,9 +1280,16 @@ class DeviceUSCFStep(DeviceSCFStep):
         if self.nranks > 1:  # the blocks of each spin, solved by their owners
             nb = int(L.hfg_eig_block_buf_size(len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p)))
             self.blockbuf_a, self.blockbuf_b = t.zeros(nb, **f64), t.zeros(nb, **f64)
+        self.kbatch = False
         if self.kfrac != 0.0:  # one buffer, so that one all-reduce serves both spins
             self.K = t.zeros(2 * N * N, **f64)
             self.Ka, self.Kb = self.K[:N * N], self.K[N * N:]
+            # HELFEM_USCF_KBATCH=1 (off by default): both spins through one batched exchange build, from staging buffers
+            # that hold (Pa, Pb) and (Ca, Cb) one after the other
+            self.kbatch = {r["name"]: r["value"] for r in tuning_table()}["HELFEM_USCF_KBATCH"] == "on"
+            if self.kbatch:
+                self.Pab, self.Cab = t.zeros(2 * N * N, **f64), t.zeros(2 * N * N, **f64)
+                self._nocc = np.array([self.nela, self.nelb], dtype=np.int64)
 
     def _spins(self):
         return ((self.Pa, self.Fa, self.Ea, self.Ca, self.nela), (self.Pb, self.Fb, self.Eb, self.Cb, self.nelb))
@@ -1254,6 +1308,18 @@ class DeviceUSCFStep(DeviceSCFStep):
 
     def exchange(self):
         """K[Pa] and K[Pb] (basis.exchange of main.cpp:822-829) into self.Ka, self.Kb"""
+        if self.kbatch:
+            N2 = self.N * self.N
+            self.Pab[:N2].copy_(self.Pa)
+            self.Pab[N2:].copy_(self.Pb)
+            if self.have_C:
+                self.Cab[:N2].copy_(self.Ca)
+                self.Cab[N2:].copy_(self.Cb)
+                _check(lib().hfg_exchange_occ_batch_devptr(self.ctx.h, self.basis.h, 2, self._ptr(self.Pab), self._ptr(self.Cab),
+                                                           self._nocc.ctypes.data_as(c_i64_p), self.N, self._ptr(self.K)))
+            else:
+                _check(lib().hfg_exchange_batch_devptr(self.ctx.h, self.basis.h, 2, self._ptr(self.Pab), self._ptr(self.K)))
+            return
         for (P, _, _, C, nocc), K in zip(self._spins(), (self.Ka, self.Kb)):
             if nocc == 0:
                 K.zero_()

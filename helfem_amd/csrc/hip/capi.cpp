@@ -4,6 +4,7 @@
 #include "../host/checkpoint.h"
 #include "../host/diis.h"
 #include "../host/dftfuncs.h"
+#include "../host/exchange_batch_plan.h"
 #include "../host/fock_need.h"
 #include <cstring>
 #include <memory>
@@ -737,6 +738,37 @@ int hfg_rs_exchange_dev(hfg_ctx *ctx, hfg_basis *b, const double *dP, double *dK
   HFG_TRY exchange_dev(ctx, b, dP, dK, true);
   HFG_CATCH
 }
+// the batched exchange entries: the refusals of the batched Coulomb entries
+int hfg_exchange_batch_devptr(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *dP, double *dK) {
+  HFG_TRY
+  if (coulomb_batch_args("hfg_exchange_batch_devptr", ctx, b, nP, dP, dK)) exchange_batch_dev(ctx, b, nP, dP, dK);
+  HFG_CATCH
+}
+int hfg_rs_exchange_batch_devptr(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *dP, double *dK) {
+  HFG_TRY
+  if (coulomb_batch_args("hfg_rs_exchange_batch_devptr", ctx, b, nP, dP, dK)) exchange_batch_dev(ctx, b, nP, dP, dK, true);
+  HFG_CATCH
+}
+int hfg_exchange_occ_batch_devptr(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *dP, const double *dC, const int64_t *nocc,
+                                  int64_t ldc_cols, double *dK) {
+  HFG_TRY
+  if (!coulomb_batch_args("hfg_exchange_occ_batch_devptr", ctx, b, nP, dP, dK)) return 0;
+  if (!dC || !nocc) throw std::logic_error("hfg_exchange_occ_batch_devptr: null pointer to the occupied orbitals or their counts\n");
+  for (int64_t i = 0; i < nP; i++)
+    if (nocc[i] < 0 || nocc[i] > ldc_cols)
+      throw std::logic_error("hfg_exchange_occ_batch_devptr: a count of occupied orbitals outside 0 ... ldc_cols\n");
+  exchange_batch_dev(ctx, b, nP, dP, dK, false, dC, nocc, ldc_cols);
+  HFG_CATCH
+}
+int hfg_exchange_batch_plan(int64_t nP, const int *ranks, int max_members, int *chunk_of, int *nchunks) {
+  HFG_TRY
+  if (nP < 0) throw std::logic_error("hfg_exchange_batch_plan: negative number of densities\n");
+  if (nP > 0 && (!ranks || !chunk_of)) throw std::logic_error("hfg_exchange_batch_plan: null pointer\n");
+  if (max_members < 0) throw std::logic_error("hfg_exchange_batch_plan: negative chunk size\n");
+  const int n = helfem::exchange_batch_plan((long)nP, ranks, max_members ? max_members : helfem::tuning_live().exchange_batch_chunk, chunk_of);
+  if (nchunks) *nchunks = n;
+  HFG_CATCH
+}
 int hfg_xc_fock_dev(hfg_ctx *ctx, hfg_basis *b, int x_func, int c_func, const double *dP, double *dH, double *dScal,
                     double thr) {
   HFG_TRY xc_fock_dev(ctx, b, x_func, c_func, dP, dH, dScal, thr);
@@ -898,6 +930,24 @@ int hfg_rs_exchange(hfg_ctx *ctx, hfg_basis *b, const double *P, double *K) {
   st.down(K, dK, N * N);
   st.sync();
   HFG_CATCH
+}
+static int exchange_batch_host(const char *who, hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *P, double *K, bool rs) {
+  HFG_TRY
+  if (!coulomb_batch_args(who, ctx, b, nP, P, K)) return 0;
+  FullShard full(ctx);
+  size_t n = b->Nbf() * b->Nbf() * (size_t)nP;
+  Stage st(ctx);
+  double *dP = st.up(P, n), *dK = st.alloc(n);
+  exchange_batch_dev(ctx, b, nP, dP, dK, rs);
+  st.down(K, dK, n);
+  st.sync();
+  HFG_CATCH
+}
+int hfg_exchange_batch(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *P, double *K) {
+  return exchange_batch_host("hfg_exchange_batch", ctx, b, nP, P, K, false);
+}
+int hfg_rs_exchange_batch(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *P, double *K) {
+  return exchange_batch_host("hfg_rs_exchange_batch", ctx, b, nP, P, K, true);
 }
 int hfg_model_potential(hfg_ctx *ctx, hfg_basis *b, const hfg_model_pot *p1, const hfg_model_pot *p2, double *H) {
   HFG_TRY

@@ -19,6 +19,7 @@
 // verified (max |P - L S L^T|); if it does not reproduce P to 1e-13 within HFG_EXL_RMAX columns the caller falls
 // back to the general kernels of exchange.hip.  Same sums as the reference, different association order.
 #include "internal.h"
+#include "../host/exchange_batch_plan.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -303,6 +304,10 @@ __global__ void k_exl_alpha_gen(const double *__restrict__ V0, const double *__r
 // from L2 per output took 1.5 ms at Nbf = 4230: 268 000 workgroups of 75 active threads.)
 constexpr int EXL_AG = 4;
 constexpr int EXL_AP = 16;  // p at most
+// BATCH (exchange_batch_dev): r columns are the concatenated factors of several densities, column o belongs to density
+// bcol[o], whose columns are boff[b] .. boff[b + 1]; the output columns are density-major, NLM boff[b] + (channel, factor of
+// b): every density's block of aP / aQw has the layout of its single build, so the products never pair two densities
+template <bool BATCH = false>
 __global__ __launch_bounds__(512) void k_exl_alpha(const double *__restrict__ V0, const double *__restrict__ V2,
                                                    const double *__restrict__ disj, const int *__restrict__ LM_tab,
                                                    const int *__restrict__ LM_ilm, const double *__restrict__ LM_fac,
@@ -310,11 +315,17 @@ __global__ __launch_bounds__(512) void k_exl_alpha(const double *__restrict__ V0
                                                    int Ntab, int two, int rank, int nranks, const int *__restrict__ ch_perm,
                                                    const int *__restrict__ sh_perm, const int *__restrict__ ch_q,
                                                    const int *__restrict__ sh_lo, const int *__restrict__ sh_hi,
-                                                   double *__restrict__ aP, double *__restrict__ aQw) {
+                                                   double *__restrict__ aP, double *__restrict__ aQw,
+                                                   const int *__restrict__ bcol = nullptr, const int *__restrict__ boff = nullptr,
+                                                   int NLM = 0) {
   extern __shared__ double xs[];  // this column of V0 (and of V2)
   const int col = blockIdx.x;
   const int c = col / r, o = col % r;
-  const size_t colp = (size_t)(ch_perm ? ch_perm[c] : c) * r + o;  // output column: channels M-major
+  size_t colp = (size_t)(ch_perm ? ch_perm[c] : c) * r + o;  // output column: channels M-major
+  if constexpr (BATCH) {
+    const int o0 = boff[bcol[o]], rb = boff[bcol[o] + 1] - o0;
+    colp = (size_t)NLM * o0 + (size_t)(ch_perm ? ch_perm[c] : c) * rb + (o - o0);
+  }
   const int tab = LM_tab[c];
   const int pp = p * p;
   // multi-GPU: the (L,M) channels of the cross-element part are dealt out over the ranks
@@ -625,13 +636,17 @@ __global__ __launch_bounds__(512) void k_exl_RB4(const double *__restrict__ V0, 
 // instructions that use them.  512 threads = 8 waves of 4 x 2 tiles (types: wave & 1 for k, (wave >> 1) & 1 for j; j
 // shells 2 (wave >> 2) + {0, 1}); without the second table type (atomic basis) 8 waves of 1 x 2 tiles.
 typedef double exl_d4 __attribute__((ext_vector_type(4)));
-template <bool TWO>
+// BATCH (exchange_batch_dev): V holds the r concatenated factor columns of nB densities; a workgroup (list entry y =
+// element + 65536 density) sums over the columns boff[b] .. boff[b + 1] of its density b alone and writes that density's pair
+// columns behind those of the densities before it: column (e nB + b) npair + pair of the slot's B operand.
+template <bool TWO, bool BATCH = false>
 __global__ __launch_bounds__(512) void k_exl_RBm(const double *__restrict__ V0, const double *__restrict__ V2,
                                                  const int *__restrict__ tab_ch_off, const int *__restrict__ tab_ch,
                                                  const double *__restrict__ LM_fac, const double *__restrict__ sgn,
                                                  const int *__restrict__ S_off, const int *__restrict__ S_list,
                                                  const long long *__restrict__ rb_off, const int4 *__restrict__ wlist, int nwg,
-                                                 int Nd, int R, int E, int p, int r, int Kld, double *__restrict__ RB) {
+                                                 int Nd, int R, int E, int p, int r, int Kld, double *__restrict__ RB,
+                                                 const int *__restrict__ boff = nullptr, int nB = 1) {
   // workgroup list (slot, element, block pair), slot-major: consecutive workgroup ids go round the 8 XCDs, so every XCD
   // takes one contiguous eighth of the list -- the blocks of a (slot, element) share their shells' columns of V in ONE L2
   int id = blockIdx.x;
@@ -640,9 +655,11 @@ __global__ __launch_bounds__(512) void k_exl_RBm(const double *__restrict__ V0, 
     id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + id / 8;
   }
   const int4 wd = wlist[id];
-  const int tau = wd.x, e = wd.y, bj = wd.z, bk = wd.w;  // bj <= bk
+  const int tau = wd.x, e = BATCH ? (wd.y & 65535) : wd.y, bj = wd.z, bk = wd.w;  // bj <= bk
+  const int bd = BATCH ? (wd.y >> 16) : 0;                                         // density, its first column, its rank
+  const int o0 = BATCH ? boff[bd] : 0, rb = BATCH ? boff[bd + 1] - o0 : r;
   const int ns = S_off[tau + 1] - S_off[tau];
-  const int c0 = tab_ch_off[tau], nco = (tab_ch_off[tau + 1] - c0) * r;
+  const int c0 = tab_ch_off[tau], nco = (tab_ch_off[tau + 1] - c0) * rb;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, l4 = lane >> 4;
   constexpr int NR = TWO ? 4 : 1, NC = 2;
   const int t2 = TWO ? (wave & 1) : 0, t1 = TWO ? ((wave >> 1) & 1) : 0;
@@ -674,7 +691,7 @@ __global__ __launch_bounds__(512) void k_exl_RBm(const double *__restrict__ V0, 
   for (int cl = threadIdx.x; cl < 4 * nsteps; cl += blockDim.x) {
     double2 v = {0.0, 0.0};
     if (cl < nco) {
-      const int c = tab_ch[c0 + cl / r], o = cl % r;
+      const int c = tab_ch[c0 + cl / rb], o = o0 + cl % rb;
       v.x = __longlong_as_double((long long)(((size_t)c * r + o) * Nd));
       v.y = LM_fac[c] * sgn[o];
     }
@@ -722,7 +739,7 @@ __global__ __launch_bounds__(512) void k_exl_RBm(const double *__restrict__ V0, 
     for (int j = 0; j < NC; j++) {
       const int pk = EXL_SB * bk + b0 + i, pj = EXL_SB * bj + a0 + j;
       if (pj > pk || pk >= ns) continue;  // only pj <= pk is stored (K is symmetric)
-      double *col = RB + rb_off[tau] + ((size_t)e * npair + (size_t)pk * (pk + 1) / 2 + pj) * Kld;
+      double *col = RB + rb_off[tau] + (((size_t)e * nB + bd) * npair + (size_t)pk * (pk + 1) / 2 + pj) * Kld;
       if (q == 0 && lane < Kld - Kt) col[Kt + lane] = 0.0;  // rows Kt .. Kld of the column: padding of the GEMM's k steps
       if (l15 >= p) continue;
       double *out = col + q * pp + l15;
@@ -833,9 +850,12 @@ __global__ void k_exl_reduce_pair(const double *__restrict__ C, const long long 
 
 // Kin[(j,k)][e][(a + p b)] = sum over the table slots that contain both shells of C_tau,e[(a b),(pj,pk)]; the GEMMs
 // only cover pj <= pk, the other half is the transpose
+// BATCH: grid.z = density b of nB; its columns of a slot's C follow those of the densities before it (k_exl_RBm), its Kin
+// the Kin of the densities before it
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_exl_reduce(const double *__restrict__ C, const long long *__restrict__ c_off,
                                                     const int *__restrict__ S_off, const int *__restrict__ pos, int A, int E, int p,
-                                                    int Ntab, double *__restrict__ Kin) {
+                                                    int Ntab, double *__restrict__ Kin, int nB = 1) {
   // the slots' block offsets for this (j, k, e) first (one thread per slot), then the sums with four loads in flight: the
   // rolled loop over the slots paid the index loads and the load of C one after the other, 126 times
   __shared__ long long soff[1024];  // offset of the block, -1: no contribution; bit 62: transposed
@@ -843,6 +863,8 @@ __global__ __launch_bounds__(256) void k_exl_reduce(const double *__restrict__ C
   const int j = jk / A, k = jk % A;
   const int pp = p * p;
   constexpr long long TR = 1ll << 62;
+  const int bd = BATCH ? blockIdx.z : 0;
+  if constexpr (BATCH) Kin += (size_t)bd * A * A * E * pp;
   for (int t0 = 0; t0 < Ntab; t0 += 1024) {
     const int nt = min(1024, Ntab - t0);
     if (t0) __syncthreads();
@@ -854,8 +876,9 @@ __global__ __launch_bounds__(256) void k_exl_reduce(const double *__restrict__ C
         if (pj >= 0 && pk >= 0) {
           const int ns = S_off[tau + 1] - S_off[tau];
           const size_t npair = (size_t)ns * (ns + 1) / 2;
-          if (pj <= pk) o = c_off[tau] + (long long)(((size_t)e * npair + (size_t)pk * (pk + 1) / 2 + pj) * pp);
-          else o = (c_off[tau] + (long long)(((size_t)e * npair + (size_t)pj * (pj + 1) / 2 + pk) * pp)) | TR;
+          const size_t col0 = BATCH ? ((size_t)e * nB + bd) * npair : (size_t)e * npair;
+          if (pj <= pk) o = c_off[tau] + (long long)((col0 + (size_t)pk * (pk + 1) / 2 + pj) * pp);
+          else o = (c_off[tau] + (long long)((col0 + (size_t)pj * (pj + 1) / 2 + pk) * pp)) | TR;
         }
       }
       soff[u] = o;
@@ -1196,11 +1219,11 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
     // threads: (element, group, row) -- as many groups of shells as fit into 512 threads, EXL_AG at most
     const int per = E * p, ng = std::max(1, std::min(EXL_AG, 512 / per));
     if (alds > 64 * 1024)
-      HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_exl_alpha, hipFuncAttributeMaxDynamicSharedMemorySize, (int)alds));
-    hipLaunchKernelGGL(k_exl_alpha, dim3((unsigned)ncol), dim3(ng * per), alds, s, a.V0.p, two ? a.V2.p : a.V0.p, t->disj.p, t->LM_tab.p,
+      HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_exl_alpha<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)alds));
+    hipLaunchKernelGGL(k_exl_alpha<false>, dim3((unsigned)ncol), dim3(ng * per), alds, s, a.V0.p, two ? a.V2.p : a.V0.p, t->disj.p, t->LM_tab.p,
                        t->LM_ilm.p, t->LM_fac.p, sgrp, Nd, R, A, E, p, r, Ntab, two, ctx->shard_rank, ctx->shard_n,
                        grouped ? a.ch_perm.p : nullptr, grouped ? a.sh_perm.p : nullptr, a.ch_q.p, a.sh_lo.p, a.sh_hi.p, a.aP.p,
-                       a.aQw.p);
+                       a.aQw.p, nullptr, nullptr, 0);
   }
   }
   // ---- cross-element part: G_ef = aQw_e aP_f^T for e > f (the other half of K is its transpose) ----
@@ -1369,13 +1392,13 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
           const size_t shm = (size_t)((a.max_nch * r + 3) / 4 * 4) * sizeof(double2);
           if (a.rbm_n > 0) {
             if (two)
-              hipLaunchKernelGGL(k_exl_RBm<true>, dim3(a.rbm_n), dim3(512), shm, s, a.V0.p, a.V2.p, a.tab_ch_off.p, a.tab_ch.p,
+              hipLaunchKernelGGL((k_exl_RBm<true, false>), dim3(a.rbm_n), dim3(512), shm, s, a.V0.p, a.V2.p, a.tab_ch_off.p, a.tab_ch.p,
                                  t->LM_fac.p, sgrp, a.S_off.p, a.S_list.p, a.rb_off.p, a.rbm_list.p, a.rbm_n, Nd, R, E, p, r, Kld,
-                                 a.RB.p);
+                                 a.RB.p, nullptr, 1);
             else
-              hipLaunchKernelGGL(k_exl_RBm<false>, dim3(a.rbm_n), dim3(512), shm, s, a.V0.p, a.V2.p, a.tab_ch_off.p, a.tab_ch.p,
+              hipLaunchKernelGGL((k_exl_RBm<false, false>), dim3(a.rbm_n), dim3(512), shm, s, a.V0.p, a.V2.p, a.tab_ch_off.p, a.tab_ch.p,
                                  t->LM_fac.p, sgrp, a.S_off.p, a.S_list.p, a.rb_off.p, a.rbm_list.p, a.rbm_n, Nd, R, E, p, r, Kld,
-                                 a.RB.p);
+                                 a.RB.p, nullptr, 1);
           }
         } else if (rb_one || p > 16)
           hipLaunchKernelGGL(k_exl_RB, dim3(max_ns * (max_ns + 1) / 2, E, nz), dim3(256), shb, s, a.V0.p, a.V2.p, a.tab_ch_off.p,
@@ -1424,8 +1447,8 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
     hipLaunchKernelGGL(k_exl_reduce_pair, dim3(A * A, E * (E + 1) / 2), dim3(256), 0, s, a.C.p, a.c_off.p, a.S_off.p, a.pos.p,
                        A, E, p, Ntab, a.Kin.p, a.G.p);
   else
-    hipLaunchKernelGGL(k_exl_reduce, dim3(A * A, E), dim3(256), 0, s, a.C.p, a.c_off.p, a.S_off.p, a.pos.p, A, E, p, Ntab,
-                       a.Kin.p);
+    hipLaunchKernelGGL(k_exl_reduce<false>, dim3(A * A, E), dim3(256), 0, s, a.C.p, a.c_off.p, a.S_off.p, a.pos.p, A, E, p, Ntab,
+                       a.Kin.p, 1);
   dim3 grid((N + 63) / 64, (N + 3) / 4);
   hipLaunchKernelGGL(k_exl_assemble, grid, dim3(256), 0, s, a.Kin.p, a.G.p, N, A, E, p, a.pure_shell.p, a.pure_n.p,
                      grouped ? a.sh_perm.p : nullptr, dK, accumulate);
@@ -1433,6 +1456,362 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   HFG_HIP_CHECK(hipStreamSynchronize(s));  // host task list and offsets live on this stack frame
   }  // factor groups
   return true;
+}
+
+// ---- K for a batch of densities (hfg_exchange_batch_devptr, DESIGN 3.3 "Batched K") --------------------------------------
+// The stages that are linear in the factors (expand, V, alpha) run once per chunk on the concatenated factor columns of
+// its members; the stages that pair factors carry a density index: k_exl_RBm<.., true> writes every density's pair columns
+// side by side into the B operand of a (slot, element), so that ONE GEMM per (slot, element) reads the element table for
+// the whole chunk, and the cross-element products are one task per (density, m-block pair, element pair).  Every sum is
+// formed in the order of the single build, with the single build's tiles: K_b is bitwise hfg_exchange(P_b).
+struct ExLBatchAux : Workspace {
+  DevBuf<double> Lall, sgnall, dinfo, Lcat, sgncat, G, Kin;  // grown to the largest batch and chunk seen
+  DevBuf<int> info, boff, bcol;
+  DevBuf<int4> rbm_list;
+  DevBuf<int2> gwl, cwl;
+  DevBuf<long long> rb_off, c_off;
+  DevBuf<GemmTask> tasks, ctasks;
+  // host sources of the asynchronous uploads: alive until the synchronisation at the end of the chunk
+  std::vector<int> h_boff, h_bcol, h_info;
+  std::vector<double> h_dinfo;
+  std::vector<int4> h_rbm;
+  std::vector<int2> h_gwl, h_cwl;
+  std::vector<long long> h_rb_off, h_c_off;
+  std::vector<GemmTask> h_tasks, h_csplit, h_cplain, h_ctasks;
+  long rbm_key = -1;  // (shard, densities) the list of k_exl_RBm's workgroups was made for
+};
+
+/// the table sets whose batches run the batched stages: those whose single build takes the matrix-core RB kernel and the
+/// fast alpha kernel.  The others (erfc pair tables, more than 16 nodes per element, the checkers of HELFEM_EXL_RB) loop
+/// over the single build inside the batched entry.
+static bool exl_batch_takes(const hfg_dev_tables *t, const ExLRAux &a) {
+  if (t->N > 1024 * EXL_QMAX || t->pair_tei || t->p > EXL_AP || t->E * t->p > 512) return false;
+  if (tuning().exl_rb == 1 || tuning().exl_rb == 4) return false;
+  if ((size_t)(t->ntt == 4 ? 2 : 1) * t->Nd * sizeof(double) > 150 * 1024) return false;
+  for (const ExLRAux::MRun &run : a.runs)
+    if (run.nj > 256) return false;
+  return true;
+}
+
+/// one chunk: nB >= 2 densities of ranks rk[b] >= 1 (64 in all at most) with factors Lp[b] (N x rk[b]) and signs sp[b]
+/// (null: all +1), K_b into dKp[b]
+static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, ExLBatchAux &w, int nB, const int *rk,
+                                 const double *const *Lp, const double *const *sp, double *const *dKp) {
+  const int A = t->A, R = t->R, E = t->E, p = t->p, Nd = t->Nd, N = t->N, NLM = t->NLM, Ntab = t->Ntab, ntt = t->ntt;
+  hipStream_t s = ctx->stream;
+  const int two = (ntt == 4) ? 1 : 0;
+  const int pp = p * p;
+  if (E > 65535 || nB > 32767) throw std::logic_error("exchange_batch_chunk: element or density index beyond the work list's fields\n");
+
+  // ---- the chunk's factor columns, one density after the other ----
+  w.h_boff.assign(nB + 1, 0);
+  int rmax = 0;
+  for (int b = 0; b < nB; b++) {
+    w.h_boff[b + 1] = w.h_boff[b] + rk[b];
+    rmax = std::max(rmax, rk[b]);
+  }
+  const int rT = w.h_boff[nB];
+  if (rT > EXL_RMAX) throw std::logic_error("exchange_batch_chunk: more than EXL_RMAX factor columns\n");
+  w.h_bcol.resize(rT);
+  w.Lcat.resize((size_t)N * rT);
+  w.sgncat.resize(rT);
+  for (int b = 0; b < nB; b++) {
+    for (int o = w.h_boff[b]; o < w.h_boff[b + 1]; o++) w.h_bcol[o] = b;
+    HFG_HIP_CHECK(hipMemcpyAsync(w.Lcat.p + (size_t)w.h_boff[b] * N, Lp[b], sizeof(double) * (size_t)N * rk[b], hipMemcpyDeviceToDevice, s));
+    HFG_HIP_CHECK(hipMemcpyAsync(w.sgncat.p + w.h_boff[b], sp[b] ? sp[b] : a.ones.p, sizeof(double) * (size_t)rk[b], hipMemcpyDeviceToDevice, s));
+  }
+  w.boff.upload(w.h_boff, s);
+  w.bcol.upload(w.h_bcol, s);
+
+  // ---- angular stage, once for all columns ----
+  const size_t ncol = (size_t)NLM * rT;
+  const size_t Na = (size_t)A * E * p, Ap = (size_t)A * p;
+  const size_t nG = std::max<size_t>((size_t)E * (E - 1) / 2 * Ap * Ap, 1);
+  a.Ld.resize((size_t)Nd * rT);
+  a.V0.resize(ncol * Nd);
+  if (two) a.V2.resize(ncol * Nd);
+  a.aP.resize(ncol * Na);
+  a.aQw.resize(ncol * Na);
+  w.G.resize(nG * nB);
+  hipLaunchKernelGGL(k_exl_expand, dim3((Nd + 255) / 256, rT), dim3(256), 0, s, w.Lcat.p, N, Nd, R, rT, t->shell_off.p, t->shell_skip.p,
+                     a.Ld.p);
+  hipLaunchKernelGGL(k_exl_V, dim3(NLM, A), dim3(256), 0, s, a.Ld.p, Nd, R, A, rT, a.LM_L.p, a.LM_M.p, t->shell_m.p, a.c0tab.p,
+                     a.c2tab.p, t->Lp1, two, a.V0.p, a.V2.p);
+  const bool grouped = a.cross_ok && tuning().exl_mgroups;
+  {
+    const size_t alds = (size_t)(two ? 2 : 1) * Nd * sizeof(double);
+    const int per = E * p, ng = std::max(1, std::min(EXL_AG, 512 / per));
+    if (alds > 64 * 1024)
+      HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_exl_alpha<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)alds));
+    hipLaunchKernelGGL(k_exl_alpha<true>, dim3((unsigned)ncol), dim3(ng * per), alds, s, a.V0.p, two ? a.V2.p : a.V0.p, t->disj.p,
+                       t->LM_tab.p, t->LM_ilm.p, t->LM_fac.p, w.sgncat.p, Nd, R, A, E, p, rT, Ntab, two, ctx->shard_rank, ctx->shard_n,
+                       grouped ? a.ch_perm.p : nullptr, grouped ? a.sh_perm.p : nullptr, a.ch_q.p, a.sh_lo.p, a.sh_hi.p, a.aP.p,
+                       a.aQw.p, w.bcol.p, w.boff.p, NLM);
+  }
+
+  // ---- cross-element part: G_b,ef = aQw_b,e aP_b,f^T, one task per (density, m-block pair, element pair) ----
+  if (E > 1) {
+    w.h_csplit.clear();
+    w.h_cplain.clear();
+    int maxMN = 0, n1 = 0;  // largest side and number of the tasks of ONE density
+    for (int b = 0; b < nB; b++) {
+      const int r = rk[b];
+      const size_t base = (size_t)NLM * w.h_boff[b] * Na;  // this density's block of aP / aQw: the layout of its single build
+      std::vector<GemmTask> ct;
+      long tiles = 0;
+      maxMN = 0;
+      for (int e = 1; e < E; e++)
+        for (int f = 0; f < e; f++) {
+          GemmTask g;
+          g.lda = g.ldb = (int)Na;
+          g.ldc = (int)Ap;
+          g.tB = 1;
+          double *Gef = w.G.p + (size_t)b * nG + ((size_t)e * (e - 1) / 2 + f) * Ap * Ap;
+          if (!grouped) {
+            g.A = a.aQw.p + base + (size_t)e * Ap;
+            g.B = a.aP.p + base + (size_t)f * Ap;
+            g.C = Gef;
+            g.M = g.N = (int)Ap;
+            g.K = NLM * r;
+            ct.push_back(g);
+            maxMN = (int)Ap;
+            tiles += (long)((Ap + 127) / 128) * ((Ap + 127) / 128);
+            continue;
+          }
+          for (const ExLRAux::MRun &rj : a.runs)
+            for (const ExLRAux::MRun &rkk : a.runs) {
+              const int lo = std::max(rj.lo, rkk.lo), hi = std::min(rj.hi, rkk.hi);
+              if (lo > hi) continue;  // G is zeroed
+              const int k0 = a.chM0[lo], k1 = a.chM0[hi + 1];
+              g.A = a.aQw.p + base + (size_t)k0 * r * Na + (size_t)e * Ap + (size_t)rj.j0 * p;
+              g.B = a.aP.p + base + (size_t)k0 * r * Na + (size_t)f * Ap + (size_t)rkk.j0 * p;
+              g.C = Gef + (size_t)rkk.j0 * p * Ap + (size_t)rj.j0 * p;
+              g.M = rj.nj * p;
+              g.N = rkk.nj * p;
+              g.K = (k1 - k0) * r;
+              ct.push_back(g);
+              maxMN = std::max(maxMN, std::max(g.M, g.N));
+              tiles += (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
+            }
+        }
+      n1 = (int)ct.size();
+      // split K or not: the rule of the single build, on this density's own column count
+      const bool split = tuning().exl_splitk && tiles < 2048 && (size_t)NLM * r >= 512;
+      std::vector<GemmTask> &dst = split ? w.h_csplit : w.h_cplain;
+      dst.insert(dst.end(), ct.begin(), ct.end());
+    }
+    if (grouped || !w.h_csplit.empty()) HFG_HIP_CHECK(hipMemsetAsync(w.G.p, 0, sizeof(double) * nG * nB, s));
+    w.h_ctasks = w.h_csplit;
+    w.h_ctasks.insert(w.h_ctasks.end(), w.h_cplain.begin(), w.h_cplain.end());
+    w.ctasks.upload(w.h_ctasks, s);
+    const int nsplit = (int)w.h_csplit.size(), nplain = (int)w.h_cplain.size();
+    if (nsplit) {
+      const GemmTile tile = (tuning().exl_crect && grouped) ? GemmTile::T128x64 : GemmTile::T128;
+      if (tile == GemmTile::T128x64 && tuning().exl_wl) {
+        gemm_worklist(w.h_csplit, tile, true, w.h_cwl);
+        w.cwl.upload(w.h_cwl, s);
+        gemm_worklist_dev(ctx, w.ctasks.p, w.cwl.p, (int)w.h_cwl.size(), tile, true);
+      } else
+        gemm_tasklist_dev(ctx, w.ctasks.p, nsplit, maxMN, maxMN, {tile, /*acc*/ false, /*split2*/ true});
+    }
+    if (nplain) {
+      // the tiles the single build's launch of n1 tasks takes
+      const long t128 = (long)((maxMN + 127) / 128) * ((maxMN + 127) / 128);
+      const GemmTile tile = (n1 <= 65535 && !gemm_prefers_128(ctx, (long)n1 * t128)) ? GemmTile::T64 : GemmTile::T128;
+      gemm_tasklist_dev(ctx, w.ctasks.p + nsplit, nplain, maxMN, maxMN, {tile});
+    }
+  }
+
+  // ---- in-element part: one GEMM per (table slot, element) over the pair columns of ALL densities ----
+  const int Kt = ntt * pp, Kld = a.kK;
+  w.h_rb_off.assign(Ntab, -1);
+  w.h_c_off.assign(Ntab, -1);
+  w.h_tasks.clear();
+  size_t rb_tot = 0, c_tot = 0;
+  int maxN1 = 0;  // longest pair list of one density
+  for (int tau = 0; tau < Ntab; tau++) {
+    const int ns = a.hS_off[tau + 1] - a.hS_off[tau];
+    if (ns == 0 || (tau % ctx->shard_n) != ctx->shard_rank) continue;
+    const size_t npair = (size_t)ns * (ns + 1) / 2;
+    w.h_rb_off[tau] = (long long)rb_tot;
+    w.h_c_off[tau] = (long long)c_tot;
+    rb_tot += (size_t)E * nB * npair * Kld;
+    c_tot += (size_t)E * nB * npair * pp;
+    maxN1 = std::max(maxN1, (int)npair);
+  }
+  a.RB.resize(rb_tot + 128 * (size_t)Kld);  // slack: the GEMM may read up to the edge of its last column tile
+  a.C.resize(std::max<size_t>(c_tot, 1));
+  double pairs1 = 0.0;  // pair columns of one density over all tasks
+  for (int tau = 0; tau < Ntab; tau++) {
+    if (w.h_rb_off[tau] < 0) continue;
+    const int ns = a.hS_off[tau + 1] - a.hS_off[tau];
+    const size_t npair = (size_t)ns * (ns + 1) / 2;
+    for (int e = 0; e < E; e++) {
+      GemmTask g;
+      g.A = a.ktei.p + ((size_t)tau * E + e) * (size_t)a.kM * a.kK;
+      g.B = a.RB.p + w.h_rb_off[tau] + (size_t)e * nB * npair * Kld;
+      g.C = a.C.p + w.h_c_off[tau] + (size_t)e * nB * npair * pp;
+      g.M = pp;
+      g.N = (int)(nB * npair);
+      g.K = Kld;
+      g.lda = a.kM;
+      g.ldb = Kld;
+      g.ldc = pp;
+      g.over = 3;  // the table's rows are padded to whole tiles; RB has slack behind its last column
+      w.h_tasks.push_back(g);
+      pairs1 += (double)npair;
+    }
+  }
+  w.rb_off.upload(w.h_rb_off, s);
+  w.c_off.upload(w.h_c_off, s);
+  w.Kin.resize((size_t)nB * A * A * E * pp);
+  if (!w.h_tasks.empty()) {
+    w.tasks.upload(w.h_tasks, s);
+    // workgroups of the RB kernel: (slot, element and density, block pair), slot-major; they depend on the tables, the
+    // shard and the number of densities only (the ranks are read from boff)
+    const long key = ((long)ctx->shard_rank * 65536 + ctx->shard_n) * 65536 + nB;
+    if (w.rbm_key != key) {
+      w.h_rbm.clear();
+      for (int tau = 0; tau < Ntab; tau++) {
+        if (w.h_rb_off[tau] < 0) continue;
+        const int nbk = (a.hS_off[tau + 1] - a.hS_off[tau] + EXL_SB - 1) / EXL_SB;
+        for (int e = 0; e < E; e++)
+          for (int b = 0; b < nB; b++)
+            for (int bk = 0; bk < nbk; bk++)
+              for (int bj = 0; bj <= bk; bj++) w.h_rbm.push_back(make_int4(tau, e + 65536 * b, bj, bk));
+      }
+      w.rbm_list.upload(w.h_rbm, s);
+      w.rbm_key = key;
+    }
+    const int nwg = (int)w.h_rbm.size();
+    const size_t shm = (size_t)((a.max_nch * rmax + 3) / 4 * 4) * sizeof(double2);
+    if (nwg > 0) {
+      if (two)
+        hipLaunchKernelGGL((k_exl_RBm<true, true>), dim3(nwg), dim3(512), shm, s, a.V0.p, a.V2.p, a.tab_ch_off.p, a.tab_ch.p, t->LM_fac.p,
+                           w.sgncat.p, a.S_off.p, a.S_list.p, w.rb_off.p, w.rbm_list.p, nwg, Nd, R, E, p, rT, Kld, a.RB.p, w.boff.p, nB);
+      else
+        hipLaunchKernelGGL((k_exl_RBm<false, true>), dim3(nwg), dim3(512), shm, s, a.V0.p, a.V2.p, a.tab_ch_off.p, a.tab_ch.p, t->LM_fac.p,
+                           w.sgncat.p, a.S_off.p, a.S_list.p, w.rb_off.p, w.rbm_list.p, nwg, Nd, R, E, p, rT, Kld, a.RB.p, w.boff.p, nB);
+    }
+    // tiles: the single build's rule on the pair lists of ONE density, so that every column is summed by the kernel its
+    // single build uses
+    const int rect_env = tuning().exl_rect;
+    const bool rect_tiles = rect_env >= 0 ? rect_env != 0 : (pairs1 < 1500.0 * (double)w.h_tasks.size());
+    ProfScope pgemm(ctx, "exl_batch_element_gemm");
+    if (ctx->profiling) {  // useful work in GFLOP, as "exl_element_gemm_gflop" of the single build
+      double gf = 0.0;
+      for (const GemmTask &q : w.h_tasks) gf += 2.0 * (double)pp * (double)q.N * (double)Kt * 1e-9;
+      ctx->prof["exl_batch_element_gemm_gflop"].ms += gf;
+      ctx->prof["exl_batch_element_gemm_gflop"].launches += 1;
+    }
+    if (tuning().exl_wl) {
+      const int tile_mode = rect_env >= 0 ? rect_env : (rect_tiles ? 2 : 0);
+      const GemmTile tile = tile_mode == 2 ? GemmTile::T64 : tile_mode == 1 ? GemmTile::T128x64 : GemmTile::T128;
+      gemm_worklist(w.h_tasks, tile, false, w.h_gwl);
+      w.gwl.upload(w.h_gwl, s);
+      gemm_worklist_dev(ctx, w.tasks.p, w.gwl.p, (int)w.h_gwl.size(), tile);
+    } else {
+      const int nt = (int)w.h_tasks.size();
+      const long t128 = (long)((pp + 127) / 128) * ((maxN1 + 127) / 128);
+      const GemmTile tile = rect_tiles ? GemmTile::T128x64
+                                       : (nt <= 65535 && !gemm_prefers_128(ctx, (long)nt * t128)) ? GemmTile::T64 : GemmTile::T128;
+      gemm_tasklist_dev(ctx, w.tasks.p, nt, pp, maxN1 * nB, {tile});
+    }
+  }
+  hipLaunchKernelGGL(k_exl_reduce<true>, dim3(A * A, E, nB), dim3(256), 0, s, a.C.p, w.c_off.p, a.S_off.p, a.pos.p, A, E, p, Ntab, w.Kin.p,
+                     nB);
+  const dim3 grid((N + 63) / 64, (N + 3) / 4);
+  for (int b = 0; b < nB; b++)
+    hipLaunchKernelGGL(k_exl_assemble, grid, dim3(256), 0, s, w.Kin.p + (size_t)b * A * A * E * pp, w.G.p + (size_t)b * nG, N, A, E, p,
+                       a.pure_shell.p, a.pure_n.p, grouped ? a.sh_perm.p : nullptr, dKp[b], 0);
+  HFG_HIP_CHECK(hipGetLastError());
+  HFG_HIP_CHECK(hipStreamSynchronize(s));  // the host lists of this chunk are overwritten by the next
+}
+
+/// nP densities (N x N each, one after the other) -> nP exchange matrices.  dC (or null): nP sets of occupied columns,
+/// N x ldc each, the first nocc[b] of set b being the factors of P_b (hfg_exchange_occ_dev); nocc is a host array.
+void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK, bool rs, const double *dC,
+                        const int64_t *nocc, int64_t ldc) {
+  if (nP <= 0) return;
+  hfg_dev_tables *t = rs ? basis->dev_rs : basis->dev;
+  if (!t || !t->have_tei) throw std::logic_error("Primitive teis have not been computed!\n");
+  if (basis->dev_device != ctx->device) throw std::logic_error("basis tables live on a different device\n");
+  const int N = t->N;
+  const size_t N2 = (size_t)N * N;
+  const bool hint = dC && nocc && tuning().exl_hint;
+  auto known = [&](int64_t b) { return hint && nocc[b] >= 0 && nocc[b] <= EXL_RMAX; };
+  auto single = [&](int64_t b) {
+    if (known(b) && nocc[b] == 0) HFG_HIP_CHECK(hipMemsetAsync(dK + b * N2, 0, sizeof(double) * N2, ctx->stream));
+    else exchange_dev(ctx, basis, dP + b * N2, dK + b * N2, rs, known(b) ? dC + (size_t)b * N * ldc : nullptr, known(b) ? (int)nocc[b] : 0);
+  };
+  ProfScope ps(ctx, "exchange_batch");
+  bool batched = nP > 1 && !helfem::tuning_live().exchange_general;
+  ExLRAux *a = nullptr;
+  if (batched) {
+    a = &exlr_for(ctx, t);
+    batched = exl_batch_takes(t, *a);
+  }
+  if (!batched) {
+    for (int64_t b = 0; b < nP; b++) single(b);
+    return;
+  }
+  ExLBatchAux &w = t->work.get<ExLBatchAux>(WS_EXLR_BATCH);
+  hipStream_t s = ctx->stream;
+
+  // ---- factorise and verify every density that comes without factors: k_exl_factor and k_exl_resid as in the single
+  // build, all queued before ONE synchronisation ----
+  std::vector<int> ranks(nP, 0);
+  w.Lall.resize((size_t)nP * N * EXL_RMAX);
+  w.sgnall.resize((size_t)nP * EXL_RMAX);
+  w.info.resize(nP);
+  w.dinfo.resize(4 * (size_t)nP);
+  w.h_info.assign(nP, 0);
+  w.h_dinfo.assign(4 * (size_t)nP, 0.0);
+  bool any = false;
+  HFG_HIP_CHECK(hipMemsetAsync(w.dinfo.p, 0, 4 * sizeof(double) * (size_t)nP, s));
+  for (int64_t b = 0; b < nP; b++) {
+    if (known(b)) continue;
+    any = true;
+    double *Lb = w.Lall.p + (size_t)b * N * EXL_RMAX, *sb = w.sgnall.p + (size_t)b * EXL_RMAX;
+    hipLaunchKernelGGL(k_exl_factor, dim3(1), dim3(1024), 0, s, dP + b * N2, N, EXL_RMAX, 1e-14, Lb, sb, w.info.p + b,
+                       w.dinfo.p + 4 * b + 2, 1);
+    hipLaunchKernelGGL(k_exl_resid, dim3((N + 255) / 256, (N + 31) / 32), dim3(256), 0, s, dP + b * N2, N, Lb, sb, w.info.p + b,
+                       w.dinfo.p + 4 * b);
+  }
+  if (any) {
+    HFG_HIP_CHECK(hipMemcpyAsync(w.h_info.data(), w.info.p, sizeof(int) * (size_t)nP, hipMemcpyDeviceToHost, s));
+    HFG_HIP_CHECK(hipMemcpyAsync(w.h_dinfo.data(), w.dinfo.p, 4 * sizeof(double) * (size_t)nP, hipMemcpyDeviceToHost, s));
+    HFG_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  for (int64_t b = 0; b < nP; b++) {
+    if (known(b)) ranks[b] = (int)nocc[b];
+    else ranks[b] = (w.h_dinfo[4 * b] <= 1e-13 * w.h_dinfo[4 * b + 1]) ? w.h_info[b] : -1;  // -1: residual groups or general kernels
+  }
+  std::vector<int> chunk_of(nP, -1);
+  const int nchunks = helfem::exchange_batch_plan((long)nP, ranks.data(), helfem::tuning_live().exchange_batch_chunk, chunk_of.data());
+
+  for (int64_t b = 0; b < nP; b++)
+    if (chunk_of[b] < 0) HFG_HIP_CHECK(hipMemsetAsync(dK + b * N2, 0, sizeof(double) * N2, s));  // the zero matrix
+  std::vector<int> rk;
+  std::vector<const double *> Lp, sp;
+  std::vector<double *> Kp;
+  for (int c = 0; c < nchunks; c++) {
+    rk.clear();
+    Lp.clear();
+    sp.clear();
+    Kp.clear();
+    int64_t first = -1;
+    for (int64_t b = 0; b < nP; b++) {
+      if (chunk_of[b] != c) continue;
+      if (first < 0) first = b;
+      rk.push_back(ranks[b]);
+      Lp.push_back(known(b) ? dC + (size_t)b * N * ldc : w.Lall.p + (size_t)b * N * EXL_RMAX);
+      sp.push_back(known(b) ? nullptr : w.sgnall.p + (size_t)b * EXL_RMAX);
+      Kp.push_back(dK + b * N2);
+    }
+    if (rk.size() == 1) single(first);  // the single build's code path (and its residual groups, its general kernels)
+    else exchange_batch_chunk(ctx, t, *a, w, (int)rk.size(), rk.data(), Lp.data(), sp.data(), Kp.data());
+  }
 }
 
 }  // namespace hfg

@@ -67,6 +67,10 @@ void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, 
                   int rknown = 0);  // exchange.hip
 bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, double *dK, const double *Lknown,
                           int rknown);  // exchange_lr.hip
+// nP densities in one pass over the exchange-ordered tables per chunk (hfg_exchange_batch_devptr); dC / nocc (host array) / ldc:
+// nP sets of occupied columns as exchange_dev's Lknown, or null
+void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK, bool rs = false,
+                        const double *dC = nullptr, const int64_t *nocc = nullptr, int64_t ldc = 0);  // exchange_lr.hip
 
 // tei_dev.hip
 void compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis);  // tei_dev.hip

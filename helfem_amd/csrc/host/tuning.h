@@ -30,6 +30,8 @@ enum class RsTei { host, dev };
   X(fock_skip, bool, true, "HELFEM_FOCK_SKIP", true, "off if 0", atoi(e) != 0, "Fock build skips shell pairs whose density block is zero and, after hfg_ctx_set_fock_blocks, pairs the caller does not read; off: every pair is computed (checker)") \
   X(xc_lds_limit, size_t, 150 * 1024, "HELFEM_XC_LDS_LIMIT", false, "int", (size_t)atol(e), "bytes of LDS the angular XC kernels plan with; smaller forces the chunked kernels (tests)") \
   X(coulomb_batch_chunk, int, 0, "HELFEM_COULOMB_BATCH_CHUNK", true, "int", std::max(0, atoi(e)), "densities per pass over the tables of the batched Coulomb build forced smaller than the LDS rule allows (tests; 0: the rule's own)") \
+  X(exchange_batch_chunk, int, 0, "HELFEM_EXCHANGE_BATCH_CHUNK", true, "int", std::max(0, atoi(e)), "densities per pass over the tables of the batched exchange build at most (tests; 0: as many as fit the 64 factor columns of a pass)") \
+  X(uscf_kbatch, bool, false, "HELFEM_USCF_KBATCH", true, "=1", atoi(e) == 1, "DeviceUSCFStep: K[Pa] and K[Pb] through one call of hfg_exchange_occ_batch_devptr; off: one call per spin") \
   X(diis_blocks, bool, true, "HELFEM_DIIS_BLOCKS", false, "off if 0", atoi(e) != 0, "DIIS error per symmetry block; off: the four dense N^3 products (checker)") \
   X(diis_lowrank, bool, true, "HELFEM_DIIS_LOWRANK", false, "off if 0", atoi(e) != 0, "blocked DIIS error from the occupied orbitals; off: per-block n^3 products from F and P (checker)") \
   X(eig_pair, bool, true, "HELFEM_EIG_PAIR", false, "off if 0", atoi(e) != 0, "both spins' Fock matrices in one batched eigensolve; off: two calls") \

@@ -213,6 +213,13 @@ int hfg_coulomb_energy_matrix(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const 
 int hfg_exchange(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *K);
 /* arma::mat atomic::basis::TwoDBasis::rs_exchange(const arma::mat & P) const   TwoDBasis.h:184, TwoDBasis.cpp:1142 */
 int hfg_rs_exchange(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *K);
+/* K for nP densities in one pass over the exchange-ordered element tables per chunk of densities (DESIGN 3.3 "Batched K"):
+ * P and K hold nP matrices of N x N, column-major, one after the other; each P_b symmetric.  K_b is bitwise hfg_exchange(P_b)
+ * (hfg_rs_exchange(P_b)): densities whose low-rank factors fit 64 columns together share a pass, a zero matrix gives an exact
+ * zero, a density of more than 64 factors or of full rank takes the single build on its own, and so does every density of an
+ * erfc basis.  nP = 0 does nothing and returns 0; nP < 0 and a null pointer are errors (status 1), as for hfg_coulomb_batch. */
+int hfg_exchange_batch(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *P, double *K);
+int hfg_rs_exchange_batch(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *P, double *K);
 /* void DFTGrid::eval_Fxc(x_func,x_pars,c_func,c_pars,P,H,Exc,Nel,Ekin,thr)   dftgrid.h:179 (restricted).
  * Functional ids are libxc's; hfg_xc_func_table() lists the ones of this build, <= 0 is none.  Of a hybrid the DFT part is
  * evaluated: the caller adds alpha K + beta K_screened of hfg_xc_exact_exchange, the screened kernel being that of
@@ -326,6 +333,23 @@ int hfg_rs_exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double
  * just formed dP = C_occ C_occ^T with scf::form_density from the nocc occupied orbitals dC (N x nocc, column-major, ld N)
  * and hands them over as the factors of dP, which saves the pivoted factorisation of dP and its verification. */
 int hfg_exchange_occ_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, const double *dC, int64_t nocc, double *dK);
+/* hfg_exchange_batch / hfg_rs_exchange_batch on device pointers, honouring the context's shard like hfg_exchange_dev (the
+ * partial K_b of the ranks sum to the whole); everything is queued on the context's stream and no argument is read after the
+ * return.  hfg_exchange_occ_batch_devptr is hfg_exchange_occ_dev for nP densities: dC holds nP sets of occupied orbitals,
+ * N x ldc_cols each (column-major, ld N), one after the other; the first nocc[b] columns of set b are the factors of P_b
+ * (nocc: HOST array of nP counts, 0 <= nocc[b] <= ldc_cols; 0 gives K_b = 0).  Deliberately not named *_dev, like
+ * hfg_coulomb_batch_devptr: the entries of that name are exactly the plan of tests/stream_order_worker.py; the stream ordering
+ * of these is tested in tests/test_gpu_exchange_batch.py (the range-separated entry is the first one's code on the other
+ * table set). */
+int hfg_exchange_batch_devptr(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK);
+int hfg_rs_exchange_batch_devptr(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK);
+int hfg_exchange_occ_batch_devptr(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, const double *dC,
+                                  const int64_t *nocc, int64_t ldc_cols, double *dK);
+/* The chunks of a batched exchange build, no device needed: ranks[b] factors of density b (0: the zero matrix, no chunk,
+ * chunk_of[b] = -1; negative or above 64: routed alone), chunk_of[b] the chunk of density b, *nchunks their number.  Chunks
+ * are runs of consecutive densities whose ranks sum to 64 at most, of max_members densities at most (0: the value of
+ * HELFEM_EXCHANGE_BATCH_CHUNK, itself 0 for no limit). */
+int hfg_exchange_batch_plan(int64_t nP, const int *ranks, int max_members, int *chunk_of, int *nchunks);
 /* dScal: 3 doubles in HBM receiving Exc, Nel, Ekin */
 int hfg_xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dH,
                     double *dScal, double dens_thr);

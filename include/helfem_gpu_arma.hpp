@@ -118,22 +118,12 @@ class BasisBase {
   /// TwoDBasis::coulomb (basis.cpp:1359): throws std::logic_error before compute_tei, like the reference
   Mat coulomb(const Mat &P) const { return two_body(hfg_coulomb, P, "coulomb"); }
   /// J of every density of a batch in one pass over the in-element tables (hfg_coulomb_batch): out[b] = coulomb(P[b])
-  std::vector<Mat> coulomb(const std::vector<Mat> &P) const {
-    for (const Mat &Pb : P) detail::need_square(Pb, N_, "coulomb");
-    if (!uploaded_) upload(lang_, mang_);
-    const size_t n2 = N_ * N_;
-    std::vector<double> in(P.size() * n2), res(P.size() * n2);
-    for (size_t b = 0; b < P.size(); b++) std::copy(detail::data_of(P[b], 0), detail::data_of(P[b], 0) + n2, in.begin() + b * n2);
-    check(hfg_coulomb_batch(ctx_->handle(), b_, (int64_t)P.size(), in.data(), res.data()));
-    std::vector<Mat> out;
-    for (size_t b = 0; b < P.size(); b++) {
-      out.push_back(Mat(N_, N_));
-      std::copy(res.begin() + b * n2, res.begin() + (b + 1) * n2, detail::data_of(out.back(), 0));
-    }
-    return out;
-  }
+  std::vector<Mat> coulomb(const std::vector<Mat> &P) const { return two_body_batch(hfg_coulomb_batch, P, "coulomb"); }
   /// TwoDBasis::exchange (basis.cpp:1532)
   Mat exchange(const Mat &P) const { return two_body(hfg_exchange, P, "exchange"); }
+  /// K of every density of a batch in one pass over the exchange-ordered tables per chunk (hfg_exchange_batch): out[b] is
+  /// bitwise exchange(P[b])
+  std::vector<Mat> exchange(const std::vector<Mat> &P) const { return two_body_batch(hfg_exchange_batch, P, "exchange"); }
   /// TwoDBasis::get_sym_idx (basis.cpp:561 / atomic TwoDBasis.cpp:202)
   std::vector<uvec> get_sym_idx(int symm) const {
     int nblk = 0;
@@ -182,6 +172,22 @@ class BasisBase {
     if (!uploaded_) upload(lang_, mang_);
     Mat out(N_, N_);
     check(fn(ctx_->handle(), b_, detail::data_of(P, 0), detail::data_of(out, 0)));
+    return out;
+  }
+  /// the batched entries: nP matrices of N x N one after the other, in and out
+  std::vector<Mat> two_body_batch(int (*fn)(hfg_ctx *, hfg_basis *, int64_t, const double *, double *), const std::vector<Mat> &P,
+                                  const char *what) const {
+    for (const Mat &Pb : P) detail::need_square(Pb, N_, what);
+    if (!uploaded_) upload(lang_, mang_);
+    const size_t n2 = N_ * N_;
+    std::vector<double> in(P.size() * n2), res(P.size() * n2);
+    for (size_t b = 0; b < P.size(); b++) std::copy(detail::data_of(P[b], 0), detail::data_of(P[b], 0) + n2, in.begin() + b * n2);
+    check(fn(ctx_->handle(), b_, (int64_t)P.size(), in.data(), res.data()));
+    std::vector<Mat> out;
+    for (size_t b = 0; b < P.size(); b++) {
+      out.push_back(Mat(N_, N_));
+      std::copy(res.begin() + b * n2, res.begin() + (b + 1) * n2, detail::data_of(out.back(), 0));
+    }
     return out;
   }
   std::shared_ptr<Context> ctx_;
@@ -273,6 +279,8 @@ class TwoDBasis : public BasisBase<Mat> {
     this->uploaded_ = false;
   }
   Mat rs_exchange(const Mat &P) const { return this->two_body(hfg_rs_exchange, P, "rs_exchange"); }
+  /// hfg_rs_exchange_batch: out[b] is bitwise rs_exchange(P[b])
+  std::vector<Mat> rs_exchange(const std::vector<Mat> &P) const { return this->two_body_batch(hfg_rs_exchange_batch, P, "rs_exchange"); }
 };
 }  // namespace atomic
 
