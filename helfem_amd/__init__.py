@@ -164,6 +164,18 @@ def lib():
         L.hfg_profile_get.argtypes = [ctypes.c_void_p, ctypes.c_char_p, c_double_p, c_i64_p]
         L.hfg_measure_kernel.argtypes = [ctypes.c_void_p, ctypes.c_char_p, c_double_p, c_i64_p]
         L.hfg_profile_names.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.hfg_diis_create.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+        L.hfg_diis_destroy.argtypes = [ctypes.c_void_p]
+        L.hfg_diis_set_metric_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+        L.hfg_diis_set_blocks.argtypes = [ctypes.c_void_p, ctypes.c_int, c_i64_p, c_i64_p]
+        L.hfg_diis_update_devptr.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                             c_double_p]
+        L.hfg_diis_solve_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int_p]
+        L.hfg_diis_size.argtypes = [ctypes.c_void_p]
+        L.hfg_diis_get.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_int64]
+        L.hfg_coulomb_dev.argtypes = [ctypes.c_void_p] * 4
         _lib = L
     return _lib
 
@@ -1100,6 +1112,119 @@ def scf_atomic(Z, lmax, mmax, nelem, nnodes, method, Q=0, nquad=0, Rmax=40.0, ig
     return r
 
 
+class DeviceDIIS(object):
+    """hfg_diis: the reference's uDIIS (update / solve_F, src/general/diis.cpp) on matrices in HBM.  Matrices are torch
+    tensors on the context's device holding N x N (Sinvh: N x n) doubles column-major, flat or two-dimensional, as the step
+    objects keep theirs; the calls are queued on the context's stream, update() synchronises it once in steady state (the
+    first use of a ring slot uploads its task list, with one more), solve() not at all."""
+
+    def __init__(self, ctx, N, nspin, order=5, diiseps=1e-2, diisthr=1e-3, mode=0):
+        self.h = None
+        self.ctx, self.N, self.nspin, self.order, self.n = ctx, int(N), int(nspin), int(order), int(N)
+        h = ctypes.c_void_p()
+        _check(lib().hfg_diis_create(ctx.h, self.N, self.nspin, self.order, float(diiseps), float(diisthr), int(mode), ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:  # (a context closed first has taken its stream with it: nothing to wait for or to free on)
+                lib().hfg_diis_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _dp(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    def _mat(self, t, cols, what):
+        if t is None:
+            return None
+        if not (t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float64" and t.numel() >= self.N * cols):
+            raise ValueError("DeviceDIIS: %s must be a contiguous float64 tensor on the device with at least %d x %d elements"
+                             % (what, self.N, cols))
+        return t
+
+    def set_metric(self, S, Sinvh):
+        """overlap S (N x N) and Sinvh (N x n); both are copied.  Empties the history and forgets the blocks"""
+        n = Sinvh.numel() // self.N
+        if n * self.N != Sinvh.numel():
+            raise ValueError("DeviceDIIS.set_metric: Sinvh is N x n")
+        _check(lib().hfg_diis_set_metric_devptr(self.h, self._dp(self._mat(S, self.N, "S")), self._dp(self._mat(Sinvh, n, "Sinvh")), n))
+        self.n = n
+
+    def set_blocks(self, m_idx):
+        """symmetry blocks (lists of basis-function indices, as scf.eig_gsym_sub takes them); None or [] removes them"""
+        ptr, idx = scf._blocks(m_idx or [])
+        _check(lib().hfg_diis_set_blocks(self.h, len(m_idx or []), ptr.ctypes.data_as(c_i64_p), idx.ctypes.data_as(c_i64_p)))
+
+    def update(self, E, Fa, Pa, Ca=None, nocca=0, Fb=None, Pb=None, Cb=None, noccb=0):
+        """new entry; returns max |err|.  Ca / Cb: the orbitals whose first nocca / noccb columns formed Pa / Pb"""
+        if self.nspin == 2 and (Fb is None or Pb is None):
+            raise ValueError("DeviceDIIS.update: nspin = 2 needs Fb and Pb")
+        if self.nspin == 1 and (Fb is not None or Pb is not None):
+            raise ValueError("DeviceDIIS.update: nspin = 1 takes one spin")
+        err = ctypes.c_double()
+        _check(lib().hfg_diis_update_devptr(self.h, float(E), self._dp(self._mat(Fa, self.N, "Fa")), self._dp(self._mat(Pa, self.N, "Pa")),
+                                            self._dp(self._mat(Ca, int(nocca), "Ca")), int(nocca) if Ca is not None else 0,
+                                            self._dp(self._mat(Fb, self.N, "Fb")), self._dp(self._mat(Pb, self.N, "Pb")),
+                                            self._dp(self._mat(Cb, int(noccb), "Cb")), int(noccb) if Cb is not None else 0,
+                                            ctypes.byref(err)))
+        return err.value
+
+    def solve(self, Fa, Fb=None):
+        """the extrapolated Fock matrices into Fa (and Fb); returns the number of old entries the extrapolation dropped"""
+        if self.nspin == 2 and Fb is None:
+            raise ValueError("DeviceDIIS.solve: nspin = 2 needs Fb")
+        dropped = ctypes.c_int()
+        _check(lib().hfg_diis_solve_devptr(self.h, self._dp(self._mat(Fa, self.N, "Fa")), self._dp(self._mat(Fb, self.N, "Fb")),
+                                           ctypes.byref(dropped)))
+        return dropped.value
+
+    @property
+    def size(self):
+        return int(lib().hfg_diis_size(self.h))
+
+    def _get(self, which, count):
+        out = np.zeros(max(count, 1))
+        _check(lib().hfg_diis_get(self.h, which, _p(out), count))
+        return out[:count]
+
+    @property
+    def B(self):
+        k = self.size
+        return self._get(0, k * k).reshape(k, k)
+
+    @property
+    def T(self):
+        k = self.size
+        return self._get(1, k * k).reshape(k, k)
+
+    @property
+    def weights(self):
+        """weights of the last solve, oldest entry first"""
+        return self._get(2, self.size)
+
+    @property
+    def error(self):
+        """error matrix of the newest entry, (nspin, n, n)"""
+        n = self.n
+        return self._get(3, self.nspin * n * n).reshape(self.nspin, n, n).transpose(0, 2, 1)
+
+
+def _refuse_out_of_scope(who, rohf, cuhf, readocc, maverage, dampfock):
+    """what the step objects' run() leaves to the drivers (hfg_scf_run)"""
+    bad = [name for name, on in (("ROHF", rohf), ("CUHF", cuhf), ("readocc", readocc is not None and int(readocc) >= 0),
+                                 ("maverage", maverage), ("dampfock", float(dampfock) != 1.0)) if on]
+    if bad:
+        raise NotImplementedError("%s.run: %s not supported by the step objects; use the SCF drivers (scf_diatomic, scf_atomic, "
+                                  "scf_run_atomic)" % (who, ", ".join(bad)))
+
+
 class DeviceSCFStep(object):
     """One SCF iteration's hot path, device resident (torch tensors are only used as HBM buffers):
 
@@ -1166,6 +1291,7 @@ class DeviceSCFStep(object):
         # hybrid functionals: F += kfrac K[Pa] (main.cpp:820-877); K is dense, its shards (output shells j % n == rank) sum
         self.kfrac = float(kfrac)
         self.have_C = False
+        self.have_density = False  # set_density() or density() has filled the density buffers
         if self.kfrac != 0.0:
             L.hfg_exchange_occ_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                ctypes.c_void_p]
@@ -1185,6 +1311,7 @@ class DeviceSCFStep(object):
         """total density P = 2 C_occ C_occ^T; C (N x >= nocc, optional): the orbitals it was formed from, which the exact
         exchange takes as the factors of P/2 (as inside the SCF loop, where the driver has just formed P from them)"""
         self.P.copy_(self.torch.from_numpy(np.asfortranarray(P).ravel(order="F").copy()))
+        self.have_density = True
         self.have_C = C is not None
         if C is not None:
             self.C[:self.N * self.nocc].copy_(self.torch.from_numpy(np.asfortranarray(C[:, :self.nocc]).ravel(order="F").copy()))
@@ -1219,6 +1346,7 @@ class DeviceSCFStep(object):
     def density(self):
         _check(lib().hfg_form_density_dev(self.ctx.h, ctypes.c_int64(self.N), ctypes.c_int64(self.N), self._ptr(self.C),
                                           ctypes.c_int64(self.nocc), self._ptr(self.P)))
+        self.have_density = True
 
     def step(self, allreduce=None, exchange_blocks=None):
         """one iteration; allreduce(tensor) sums a tensor over ranks in place (None: single GPU);
@@ -1248,6 +1376,143 @@ class DeviceSCFStep(object):
         self.eig_finish()
         self.density()
         self.have_C = True  # self.C now holds the orbitals self.P was formed from
+
+    # ---- the converging loop: main.cpp:780-995 composed from the stages above, DIIS by a DeviceDIIS --------------------
+    def _whole_shard(self, fn):
+        """fn() with the context unsharded: what every rank computes whole (J + XC under fock_shard != "always", the J of
+        the Coulomb energy)"""
+        if self.nranks > 1:
+            self.ctx.set_shard(0, 1)
+        try:
+            fn()
+        finally:
+            if self.nranks > 1:
+                self.ctx.set_shard(self.rank, self.nranks)
+
+    def _fock_stage(self, allreduce):
+        """fock_partial, collectives, fock_finish, exchange: the Fock-build half of step(), same policy"""
+        shard_fock = self.nranks > 1 and self.fock_shard == "always"
+        if shard_fock or self.nranks == 1:
+            self.fock_partial()
+            if allreduce is not None:
+                allreduce(self.Fc)
+                allreduce(self.scal)
+        else:
+            self._whole_shard(self.fock_partial)
+        self.fock_finish()
+        if self.kfrac != 0.0:
+            self.exchange()
+            if allreduce is not None:
+                allreduce(self.K)
+            self._add_exchange()
+
+    def _add_exchange(self):
+        self.F.add_(self.K, alpha=self.kfrac)
+
+    def _eig_stage(self, allreduce, exchange_blocks):
+        """eig_partial, collective, eig_finish: the eigensolve half of step()"""
+        self.eig_partial()
+        if exchange_blocks is not None:
+            exchange_blocks(self.blockbuf, len(self.blocks))
+        elif allreduce is not None:
+            allreduce(self.blockbuf)
+        self.eig_finish()
+
+    def _coulomb_energy_matrix(self, P):
+        if getattr(self, "J", None) is None:
+            self.J = self.torch.zeros(self.N * self.N, dtype=self.torch.float64, device=self.dev)
+        self._whole_shard(lambda: _check(lib().hfg_coulomb_dev(self.ctx.h, self.basis.h, self._ptr(P), self._ptr(self.J))))
+        return self.J
+
+    def _energy_terms(self):
+        """device scalars [E1, 2 Ecoul, Exx / kfrac]"""
+        t = self.torch
+        J = self._coulomb_energy_matrix(self.P)
+        terms = [t.dot(self.P, self.H0), t.dot(self.P, J)]
+        terms.append(t.dot(self.Pa, self.K) if self.kfrac != 0.0 else t.zeros((), dtype=t.float64, device=self.dev))
+        return terms
+
+    def energy(self, Enucr=0.0):
+        """energies of main.cpp:808-900 for the density of the last Fock build (fock_partial ... exchange): E1 = tr(P H0),
+        Ecoul = 1/2 tr(P J[P]) with J built whole on every rank (one extra Coulomb build: the fused build returns only
+        J + XC), Exx from the K that exchange() left, Exc = scal[0].  One read-back of four doubles."""
+        t = self.torch
+        v = t.stack(self._energy_terms() + [self.scal[0]]).cpu().numpy()
+        r = dict(E1=float(v[0]), Ecoul=0.5 * float(v[1]), Exx=self._exx_factor() * float(v[2]), Exc=float(v[3]), Enucr=float(Enucr))
+        r["Etot"] = r["E1"] + r["Ecoul"] + r["Exx"] + r["Exc"] + r["Enucr"]
+        return r
+
+    def _exx_factor(self):
+        return self.kfrac  # Exx = tr(Pa kfrac K[Pa]), Pa = P / 2, both spins
+
+    def _nspin(self):
+        return 1
+
+    def _density_stage(self):
+        """density() leaves C_occ C_occ^T in P; the Fock build takes the total density of the closed shell, twice that"""
+        self.density()
+        self.P.mul_(2.0)
+        self.have_C = True
+
+    def _core_guess(self, allreduce, exchange_blocks):
+        self.F.copy_(self.H0)
+        self._eig_stage(allreduce, exchange_blocks)
+        self._density_stage()
+
+    def _diis_update(self, diis, E):
+        if getattr(self, "Pa", None) is None:
+            self.Pa = self.torch.zeros(self.N * self.N, dtype=self.torch.float64, device=self.dev)
+        self.torch.mul(self.P, 0.5, out=self.Pa)
+        if self.have_C:
+            return diis.update(E, self.F, self.Pa, self.C, self.nocc)
+        return diis.update(E, self.F, self.Pa)
+
+    def _diis_solve(self, diis):
+        diis.solve(self.F)
+
+    def run(self, S, maxit=50, convthr=1e-7, Enucr=0.0, allreduce=None, exchange_blocks=None, diis=None, callback=None,
+            rohf=False, cuhf=False, readocc=None, maverage=False, dampfock=1.0):
+        """SCF to convergence: the loop of main.cpp:780-995 with the reference's ADIIS + CDIIS.  S: the overlap matrix (numpy,
+        N x N).  Without a density (set_density) the loop starts from the core guess, the eigenvectors of H0 from this step's
+        own eigensolver.  Per iteration: Fock build, energy, diis.update with F, P and the occupied orbitals, the driver's
+        test max |err| < convthr and |dE| < convthr; unless it holds, diis.solve into F, eigensolve, density.  allreduce and
+        exchange_blocks as in step(); every rank runs its own DeviceDIIS on identical inputs, so DIIS adds no collective.
+        diis: a DeviceDIIS with its metric set (default: order 5, this step's Sinvh and symmetry blocks); callback(it, Etot,
+        maxerr) after every iteration.  Returns the energies of energy() plus iterations, converged and the trace
+        [(Etot, maxerr), ...].  ROHF / CUHF, readocc, maverage and dampfock stay with the drivers: the keywords rohf, cuhf,
+        readocc, maverage and dampfock exist only so that a script ported from the drivers fails loudly (NotImplementedError)
+        instead of running without them; they have no other effect."""
+        _refuse_out_of_scope(type(self).__name__, rohf, cuhf, readocc, maverage, dampfock)
+        if self.H0 is None:
+            raise RuntimeError("run: set_matrices first")
+        t = self.torch
+        if diis is None:
+            diis = DeviceDIIS(self.ctx, self.N, self._nspin())
+            dS = t.from_numpy(np.asfortranarray(S, dtype=np.float64).ravel(order="F").copy()).to(self.dev)
+            diis.set_metric(dS, self.Sinvh)
+            if len(self.blocks) > 1:
+                diis.set_blocks(self.blocks)
+        if not self.have_density:
+            self._core_guess(allreduce, exchange_blocks)
+        trace, Eold, res, converged, it = [], 0.0, None, False, 0
+        for it in range(1, int(maxit) + 1):
+            self._fock_stage(allreduce)
+            res = self.energy(Enucr)
+            maxerr = self._diis_update(diis, res["Etot"])
+            dE = res["Etot"] - Eold
+            Eold = res["Etot"]
+            trace.append((res["Etot"], maxerr))
+            if callback is not None:
+                callback(it, res["Etot"], maxerr)
+            if maxerr < convthr and abs(dE) < convthr:
+                converged = True
+                break
+            self._diis_solve(diis)
+            self._eig_stage(allreduce, exchange_blocks)
+            self._density_stage()
+        res = dict(res or {})
+        res.update(iterations=it, converged=converged, trace=trace)
+        return res
 
     def numpy(self, t, shape):
         return t.cpu().numpy().reshape(shape, order="F")
@@ -1300,6 +1565,7 @@ class DeviceUSCFStep(DeviceSCFStep):
         as_dev = lambda M: self.torch.from_numpy(np.asfortranarray(M).ravel(order="F").copy())
         self.Pa.copy_(as_dev(Pa))
         self.Pb.copy_(as_dev(Pb))
+        self.have_density = True
         self.have_C = Ca is not None and (Cb is not None or self.nelb == 0)
         if self.have_C:
             self.Ca[:self.N * self.nela].copy_(as_dev(Ca[:, :self.nela]))
@@ -1363,6 +1629,7 @@ class DeviceUSCFStep(DeviceSCFStep):
                 continue
             _check(lib().hfg_form_density_dev(self.ctx.h, ctypes.c_int64(self.N), ctypes.c_int64(self.N), self._ptr(C),
                                               ctypes.c_int64(nocc), self._ptr(P)))
+        self.have_density = True
 
     def step(self, allreduce=None, exchange_blocks=None):
         """one iteration, with the restricted step's policy for allreduce and exchange_blocks; one rank solves the blocks of
@@ -1395,3 +1662,55 @@ class DeviceUSCFStep(DeviceSCFStep):
             self.eig_finish()
         self.density()
         self.have_C = True  # Ca, Cb now hold the orbitals the densities were formed from
+
+    # ---- the pieces of DeviceSCFStep.run that differ for two spins -----------------------------------------------------
+    def _add_exchange(self):
+        self.Fa.add_(self.Ka, alpha=self.kfrac)
+        self.Fb.add_(self.Kb, alpha=self.kfrac)
+
+    def _eig_stage(self, allreduce, exchange_blocks):
+        if self.nranks == 1:
+            self.eig_pair()
+            return
+        self.eig_partial()
+        for buf in (self.blockbuf_a, self.blockbuf_b):
+            if exchange_blocks is not None:
+                exchange_blocks(buf, len(self.blocks))
+            elif allreduce is not None:
+                allreduce(buf)
+        self.eig_finish()
+
+    def _energy_terms(self):
+        t = self.torch
+        if getattr(self, "Pt", None) is None:
+            self.Pt = t.zeros(self.N * self.N, dtype=t.float64, device=self.dev)
+        t.add(self.Pa, self.Pb, out=self.Pt)
+        J = self._coulomb_energy_matrix(self.Pt)
+        terms = [t.dot(self.Pt, self.H0), t.dot(self.Pt, J)]
+        terms.append(t.dot(self.Pa, self.Ka) + t.dot(self.Pb, self.Kb) if self.kfrac != 0.0
+                     else t.zeros((), dtype=t.float64, device=self.dev))
+        return terms
+
+    def _exx_factor(self):
+        return 0.5 * self.kfrac  # Exx = 1/2 (tr Pa kfrac K[Pa] + tr Pb kfrac K[Pb])
+
+    def _nspin(self):
+        return 2
+
+    def _density_stage(self):
+        self.density()
+        self.have_C = True
+
+    def _core_guess(self, allreduce, exchange_blocks):
+        self.Fa.copy_(self.H0)
+        self.Fb.copy_(self.H0)
+        self._eig_stage(allreduce, exchange_blocks)
+        self._density_stage()
+
+    def _diis_update(self, diis, E):
+        if self.have_C:
+            return diis.update(E, self.Fa, self.Pa, self.Ca, self.nela, self.Fb, self.Pb, self.Cb if self.nelb else None, self.nelb)
+        return diis.update(E, self.Fa, self.Pa, Fb=self.Fb, Pb=self.Pb)
+
+    def _diis_solve(self, diis):
+        diis.solve(self.Fa, self.Fb)

@@ -119,6 +119,36 @@ void form_sinvh_dev(hfg_ctx *ctx, int N, const double *dS, bool chol, int nblk, 
                     double *dSinvh);  // misc.hip
 void form_density_dev(hfg_ctx *ctx, int N, int ncols, const double *dC, int nocc, double *dP);  // misc.hip
 
+// diis_dev.hip: the launchers of the device-resident DIIS object (hfg_diis_*)
+constexpr int DIIS_LR_MAXCOLS = 64;  // occupied columns the low-rank error kernel takes; more go through the dense products
+constexpr int DIIS_HIST_CHUNK = 8;   // stored entries per history pass
+// err = A B^T - B A^T of order n from two n x k factors (leading dimension ld), written to out (leading dimension ldo)
+struct DiisErrTask {
+  const double *A, *B;
+  double *out;
+  int n, k, ld, ldo;
+};
+// the stored entries of one history pass: error, density and Fock matrices, all spins of an entry back to back
+struct DiisHistory {
+  const double *E[DIIS_HIST_CHUNK], *P[DIIS_HIST_CHUNK], *F[DIIS_HIST_CHUNK];
+  int n;
+};
+struct DiisComb {
+  const double *F[16];
+  double w[16];
+  int n;
+};
+size_t diis_lowrank_partials(int ntasks, int nmax);  // diis_dev.hip
+// every task's error matrix and *dMax = max |err| over all of them; dPartialMax: diis_lowrank_partials() doubles
+void diis_lowrank_error_dev(hfg_ctx *ctx, const DiisErrTask *dtasks, int ntasks, int nmax, double *dPartialMax,
+                            double *dMax);  // diis_dev.hip
+// dRes[1 + j0 + k] = Enew . E_k, dRes[1 + nhtot + j0 + k] = P_k . Fnew, dRes[1 + 2 nhtot + j0 + k] = Pnew . F_k for the h.n
+// entries of the pass; want_max: dRes[0] = max |Enew|.  dPartial: (3 DIIS_HIST_CHUNK + 1) x 1024 doubles
+void diis_history_dev(hfg_ctx *ctx, const DiisHistory &h, int j0, int nhtot, const double *dEnew, size_t elen, const double *dPnew,
+                      const double *dFnew, size_t flen, bool want_max, double *dPartial, double *dRes);  // diis_dev.hip
+// dFa = sum_k w_k F_k[0 : NN], dFb = sum_k w_k F_k[NN : 2 NN] (nspin == 2)
+void diis_extrapolate_dev(hfg_ctx *ctx, const DiisComb &c, size_t NN, int nspin, double *dFa, double *dFb);  // diis_dev.hip
+
 // scf_device.hip
 helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::scf::Options &opt, int nel, double Enucr, int symm,
                                     const std::vector<std::vector<size_t> > &dsym, int ldft, int mdft,

@@ -158,6 +158,37 @@ int hfg_compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis, int exchange);
 int hfg_diis_weights(int n, const double *B, const double *T, const double *E, double maxerr, double diiseps, double diisthr,
                      int mode, double *w, int *dropped);
 
+/* Device-resident DIIS accelerator: uDIIS::update / solve_F (src/general/diis.cpp:129-168, 392-412) on matrices that stay in
+ * HBM.  The object keeps its own copies of F, P and the error Sinvh^T (F P S - S P F) Sinvh of up to `order` (<= 16) entries;
+ * everything is queued on the context's stream, so the caller's buffers are free again when a call returns.  In steady
+ * state update synchronises the stream once (the new row of B, row and column of T and max |err|: at most 3 order + 1
+ * doubles); the first use of each ring slot, a change of nocc or of the route, and growth of a workspace add a
+ * synchronisation for the upload of that slot's task list or an allocation.  solve does not synchronise.  An update that
+ * fails empties the history.  All reductions run in a fixed order: two objects fed the same matrices give the same bits.
+ * Matrices are column-major. */
+typedef struct hfg_diis hfg_diis;
+int hfg_diis_create(hfg_ctx *ctx, int64_t N, int nspin /*1|2*/, int order, double diiseps, double diisthr,
+                    int mode /* as hfg_diis_weights: 0 mixed, 1 CDIIS, 2 ADIIS */, hfg_diis **d);
+int hfg_diis_destroy(hfg_diis *d);
+/* S (N x N) and Sinvh (N x n) in HBM; both are copied, so the caller may free them.  Empties the history and forgets the
+ * blocks. */
+int hfg_diis_set_metric_devptr(hfg_diis *d, const double *dS, const double *dSinvh, int64_t n);
+/* optional symmetry blocks (host arrays as for hfg_eig_gsym_sub): the error is then formed per block.  Needs n = N, a
+ * block-structured Sinvh and an empty history; F, P and S must be block diagonal.  nblk = 0 removes the blocks. */
+int hfg_diis_set_blocks(hfg_diis *d, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx);
+/* new entry: energy E, Fock and density matrices of each spin (nspin = 1: dFb = dPb = NULL and the one spin counts twice,
+ * as the restricted driver does); dC* / nocc*: the occupied orbitals P was formed from (P = C_o C_o^T, N x nocc), or NULL / 0.
+ * With the orbitals of every spin that has electrons and at most 64 of them per spin the error comes from products with
+ * nocc columns and the rank-nocc kernel; otherwise from the four dense products of the definition. */
+int hfg_diis_update_devptr(hfg_diis *d, double E, const double *dFa, const double *dPa, const double *dCa, int64_t nocca,
+                           const double *dFb, const double *dPb, const double *dCb, int64_t noccb, double *maxerr /* host */);
+/* extrapolated Fock matrices into dFa / dFb (may alias the inputs of the last update); dropped: entries discarded */
+int hfg_diis_solve_devptr(hfg_diis *d, double *dFa, double *dFb, int *dropped);
+int hfg_diis_size(const hfg_diis *d);
+/* test access: which 0 = B, 1 = T (size x size, row-major, oldest first), 2 = weights of the last solve (one per entry left),
+ * 3 = error matrix of the newest entry (nspin x n x n, n the columns of Sinvh; N x N when Sinvh is square) */
+int hfg_diis_get(hfg_diis *d, int which, double *out, int64_t cap);
+
 /* Read-back of the setup tables (test and diagnostic access; basis.cpp:1166-1302 fills them):
  *   hfg_basis_lm_map: the sorted (L,|M|) channel list of the constructor (basis.cpp:333-375); n in: capacity, out: count
  *   hfg_basis_get_prim: which 0-3 prim_tei00/02/20/22, 4-7 prim_ktei00/02/20/22, 8-11 disjoint_P0/P2/Q0/Q2 of channel ilm and
