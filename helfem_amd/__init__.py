@@ -1343,6 +1343,12 @@ class DeviceSCFStep(object):
                                           self.blk_ptr.ctypes.data_as(c_i64_p), self.blk_idx.ctypes.data_as(c_i64_p),
                                           self._ptr(self.blockbuf), self._ptr(self.E), self._ptr(self.C)))
 
+    def eig_whole(self):
+        """the eigensolve of one rank in one call (hfg_eig_gsym_sub_dev): no block slots between two phases"""
+        _check(lib().hfg_eig_gsym_sub_dev(self.ctx.h, ctypes.c_int64(self.N), self._ptr(self.F), self._ptr(self.Sinvh),
+                                          len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p),
+                                          self.blk_idx.ctypes.data_as(c_i64_p), self._ptr(self.E), self._ptr(self.C)))
+
     def density(self):
         _check(lib().hfg_form_density_dev(self.ctx.h, ctypes.c_int64(self.N), ctypes.c_int64(self.N), self._ptr(self.C),
                                           ctypes.c_int64(self.nocc), self._ptr(self.P)))
@@ -1368,12 +1374,7 @@ class DeviceSCFStep(object):
             if allreduce is not None:
                 allreduce(self.K)
             self.F.add_(self.K, alpha=self.kfrac)  # K of a block-diagonal density is block diagonal: no mask needed
-        self.eig_partial()
-        if exchange_blocks is not None:
-            exchange_blocks(self.blockbuf, len(self.blocks))
-        elif allreduce is not None:
-            allreduce(self.blockbuf)
-        self.eig_finish()
+        self._eig_stage(allreduce, exchange_blocks)
         self.density()
         self.have_C = True  # self.C now holds the orbitals self.P was formed from
 
@@ -1410,7 +1411,10 @@ class DeviceSCFStep(object):
         self.F.add_(self.K, alpha=self.kfrac)
 
     def _eig_stage(self, allreduce, exchange_blocks):
-        """eig_partial, collective, eig_finish: the eigensolve half of step()"""
+        """the eigensolve half of step(): one call on one rank without collectives, else eig_partial, collective, eig_finish"""
+        if self.nranks == 1 and allreduce is None and exchange_blocks is None:
+            self.eig_whole()
+            return
         self.eig_partial()
         if exchange_blocks is not None:
             exchange_blocks(self.blockbuf, len(self.blocks))

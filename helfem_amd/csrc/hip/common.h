@@ -170,8 +170,11 @@ struct GemmTask {
   // product is stored at C[:, cmap[j]].  The merges of divide and conquer (dc.hip) read the non-deflated columns of Q
   // and store every new eigenvector at its ranked place through them.
   const int *amap = nullptr, *cmap = nullptr;
+  // row map (k_dgemm_tasklist_scatter, GemmHow::scatter, only; beta == 0): element (i, j) of the product is stored at
+  // C[rmap[i], cmap[j]].  The last product of the blocked eigensolve (eig.hip) writes into the N x N eigenvector matrix through them.
+  const int64_t *rmap = nullptr;
 };
-static_assert(sizeof(GemmTask) == 96, "GemmTask is compared bytewise: keep it free of padding");
+static_assert(sizeof(GemmTask) == 104, "GemmTask is compared bytewise: keep it free of padding");
 
 struct ProfScope {
   hfg_ctx *c;

@@ -20,6 +20,7 @@
 #include "../host/eigsel_count.h"
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 
 namespace hfg {
 
@@ -52,6 +53,14 @@ __global__ void k_gather_block(const double *__restrict__ F, const double *__res
   if (i >= n) return;
   Fb[(size_t)j * n + i] = F[(size_t)rows[j] * N + rows[i]];
   Xb[(size_t)j * n + i] = S[(size_t)cols[j] * N + rows[i]];
+}
+
+// F(idx,idx) alone: X of this block is already in the context's cache (EigWork::Xc)
+__global__ void k_gather_f(const double *__restrict__ F, int N, const int64_t *__restrict__ rows, int n, double *__restrict__ Fb) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int j = blockIdx.y;
+  if (i >= n) return;
+  Fb[(size_t)j * n + i] = F[(size_t)rows[j] * N + rows[i]];
 }
 
 // column support of Sinvh on the block rows (scf_helpers.cpp:150-157): flag[c] = any(Sinvh(rows,c) != 0)
@@ -424,6 +433,12 @@ static void launch_rank(hfg_ctx *ctx, const double *E, int n, int *rank) {
   hipLaunchKernelGGL(k_rank, dim3((n + 255) / 256, RANK_SEG), dim3(256), 0, ctx->stream, E, n, rank);
 }
 
+// Eout[rank[i]] = E[i]: the eigenvalues at their ranked places (the one-call entries, whose eigenvectors the last product places)
+__global__ void k_place_values(const double *__restrict__ E, int n, const int *__restrict__ rank, double *__restrict__ Eout) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) Eout[rank[i]] = E[i];
+}
+
 // Cout(rows[i], rank[coff+j]) = Cb(i,j) ; Eout[rank[coff+j]] = Eb[j]   (rows==nullptr: identity)
 __global__ void k_scatter_cols(const double *__restrict__ Cb, int nrow, int ncol, const int64_t *__restrict__ rows,
                                const int *__restrict__ rank, int coff, const double *__restrict__ Eb, int ldc,
@@ -652,6 +667,18 @@ struct EigWork : Workspace {
   unsigned long sup_gen = 0;
   int sup_N = 0;
   std::vector<int64_t> sup_ptr, sup_idx;
+  // the blocks' X = Sinvh(rows, cols), block ib (n x n, ld n) at offset sum_{b < ib} n_b^2, gathered once while the lists above
+  // are valid (so only under hfg_ctx_fix_sinvh); xc_have[ib]: block ib has been gathered.  Cleared with the lists.
+  DevBuf<double> Xc;
+  std::vector<char> xc_have;
+  // one-call entries: the divide-and-conquer status word is copied home behind that stage and waited for through the event,
+  // so that the host returns while the last product is still running
+  int *h_status = nullptr;
+  hipEvent_t status_ev = nullptr;
+  ~EigWork() {
+    if (h_status) (void)hipHostFree(h_status);
+    if (status_ev) (void)hipEventDestroy(status_ev);
+  }
 };
 static EigWork &work_for(hfg_ctx *ctx) { return ctx->work.get<EigWork>(WS_EIG); }
 
@@ -994,8 +1021,10 @@ static bool eigsel_takes_stein(int nblk, const int *ns, const int *nev) {
   }
   return (double)want <= EIGSEL_CROSS * (double)all;
 }
+/// after_solve: queued on the main stream as soon as the eigenvalues (w.d, or w.Ws of a selected solve) are final, ahead of
+/// the back-transformation or of the wait for X Q
 static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, const double *const *foldX = nullptr,
-                          const int *nev = nullptr) {
+                          const int *nev = nullptr, const std::function<void()> &after_solve = nullptr) {
   EigBatch b;
   b.nblk = nblk;
   int nmax = 0, nzmax = 0;
@@ -1115,6 +1144,7 @@ static void eig_sym_batch(hfg_ctx *ctx, EigWork &w, int nblk, const int *ns, con
       }
     }
   }
+  if (after_solve) after_solve();
   {
     ProfScope ps(ctx, "eig_backtransform");
     if (fold) {
@@ -1221,7 +1251,8 @@ size_t eig_block_buf_size(int nblk, const int64_t *blk_ptr) {
 // tridiagonalisation is a chain of dependent launches whose length does not depend on the number of blocks in it, so two
 // spins cost about what one costs
 static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
-                                 const int64_t *blk_idx, double *const *dBlockBufs, int nev = 0);
+                                 const int64_t *blk_idx, double *const *dBlockBufs, int nev = 0, double *const *dEs = nullptr,
+                                 double *const *dCs = nullptr);
 static int eig_num_cus(hfg_ctx *ctx) {
   static const int ncu = [&] {  // once per process, under the guard of the static's initialisation
     hipDeviceProp_t prop;
@@ -1234,10 +1265,16 @@ void eig_blocks_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int
   eig_blocks_multi_dev(ctx, N, 1, &dF, dS, nblk, blk_ptr, blk_idx, &dBlockBuf);
 }
 /// nev > 0: the lowest min(nev, n_b) eigenpairs of every block only; slot ib then holds that many columns (ld n_b) and values
+/// dEs, dCs (the one-call entries on one device, nF * nblk <= MAXB; dBlockBufs is not used): no block slots.  The K =
+/// eig_sel_count eigenvalues of matrix f are ranked as soon as they are final and go to dEs[f]; the last product stores
+/// element (i, j) of block ib at row blk_idx[blk_ptr[ib] + i], column rank[koff[ib] + j] of dCs[f] (N x K, zeroed here),
+/// with the tiles and the k order of the slot path, so that E and C are bit for bit those of eig_assemble_dev.
 static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
-                                 const int64_t *blk_idx, double *const *dBlockBufs, int nev) {
+                                 const int64_t *blk_idx, double *const *dBlockBufs, int nev, double *const *dEs, double *const *dCs) {
   EigWork &w = work_for(ctx);
   hipStream_t s = ctx->stream;
+  const bool direct = dEs != nullptr;
+  if (direct && (ctx->shard_n != 1 || nF * nblk > MAXB)) throw std::logic_error("eig_blocks_multi_dev: direct path needs one rank and one batch\n");
   if (blk_ptr[nblk] != N) throw std::logic_error("Symmetry mismatch in eig_gsym_sub\n");
   // block row indices on the device
   DevBuf<double> &idxbuf = w.idx;  // raw storage for int64 rows + cols
@@ -1254,6 +1291,7 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
                       w.sup_idx.size() == (size_t)N && std::equal(w.sup_idx.begin(), w.sup_idx.end(), blk_idx);
   if (!cached) {
     w.sup_S = nullptr;
+    w.xc_have.clear();  // the gathered X blocks belong to the lists that go
     HFG_HIP_CHECK(hipMemcpyAsync(drows, blk_idx, sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
     DevBuf<int> &flag = w.ibuf2;
     flag.resize((size_t)N * nblk + 8);
@@ -1289,7 +1327,35 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
   size_t nmax = 0;
   for (int ib = 0; ib < nblk; ib++) nmax = std::max<size_t>(nmax, blk_ptr[ib + 1] - blk_ptr[ib]);
   const size_t slot = nmax * nmax + nmax;
-  for (int f = 0; f < nF; f++) HFG_HIP_CHECK(hipMemsetAsync(dBlockBufs[f], 0, sizeof(double) * slot * nblk, s));
+  // the slots of the other ranks' blocks are zero so that a sum over the ranks completes the buffer.  One rank writes every
+  // word that is read afterwards (eig_assemble_dev: n x nev columns and nev values per slot; the collectives of
+  // helfem_amd.parallel move whole buffers or whole slots and read nothing themselves), so nothing is zeroed for it --
+  // except the products' own outputs where two half-K workgroups add into them (below).
+  if (!direct && ctx->shard_n > 1)
+    for (int f = 0; f < nF; f++) HFG_HIP_CHECK(hipMemsetAsync(dBlockBufs[f], 0, sizeof(double) * slot * nblk, s));
+  // X = Sinvh(rows, cols) of every block, kept across calls while the lists above are (hfg_ctx_fix_sinvh): w.Xc
+  const bool keep_x = w.sup_S == dS && w.sup_S != nullptr;
+  std::vector<size_t> xoff(nblk + 1, 0);
+  for (int ib = 0; ib < nblk; ib++) xoff[ib + 1] = xoff[ib] + (size_t)(blk_ptr[ib + 1] - blk_ptr[ib]) * (size_t)(blk_ptr[ib + 1] - blk_ptr[ib]);
+  if (keep_x) {
+    if (w.xc_have.size() != (size_t)nblk || w.Xc.n < xoff[nblk]) {
+      w.Xc.resize(xoff[nblk]);
+      w.xc_have.assign(nblk, 0);
+    }
+  }
+  // direct: ranks and eigenvalues of matrix f at rank.p + f (N + 8), Etmp.p + f N; block ib's values start at koff[ib]
+  std::vector<int64_t> koff(nblk + 1, 0);
+  for (int ib = 0; ib < nblk; ib++) {
+    const int64_t n = blk_ptr[ib + 1] - blk_ptr[ib];
+    koff[ib + 1] = koff[ib] + (nev > 0 ? std::min<int64_t>(nev, n) : n);
+  }
+  const int K = (int)koff[nblk];
+  DevBuf<int> &rank = w.ibuf1;
+  DevBuf<double> &Etmp = ctx->ws[3];
+  if (direct) {
+    rank.resize((size_t)nF * (N + 8));
+    Etmp.resize((size_t)nF * N);
+  }
 
   // work items: (matrix, block) pairs; `mine` holds matrix * nblk + block
   std::vector<int> mine;
@@ -1312,7 +1378,7 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
     int nm = 0;
     for (int k = 0; k < nb; k++) {
       const int ib = mine[c0 + k] % nblk;
-      double *dBlockBuf = dBlockBufs[mine[c0 + k] / nblk];
+      double *dBlockBuf = direct ? nullptr : dBlockBufs[mine[c0 + k] / nblk];
       int n = (int)(blk_ptr[ib + 1] - blk_ptr[ib]);
       ns[k] = n;
       nevs[k] = nev > 0 ? std::min(nev, n) : n;
@@ -1321,7 +1387,8 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
       if (nev > 0) w.Zs[k].resize((size_t)n * nevs[k]);
       else w.Z[k].resize((size_t)n * n);
       w.Y[k].resize((size_t)n * n);
-      double *Xb = Xall.p + (size_t)k * nmax * nmax, *Fk = Fb.p + (size_t)k * nmax * nmax, *Tk = T1.p + (size_t)k * nmax * nmax;
+      double *Xb = keep_x ? w.Xc.p + xoff[ib] : Xall.p + (size_t)k * nmax * nmax;
+      double *Fk = Fb.p + (size_t)k * nmax * nmax, *Tk = T1.p + (size_t)k * nmax * nmax;
       Xptr[k] = Xb;
       GemmTask g;
       g.M = g.N = g.K = n;
@@ -1341,7 +1408,14 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
       g.A = Xb;
       g.B = nev > 0 ? w.Zs[k].p : w.Z[k].p;
       g.N = nevs[k];
-      g.C = dBlockBuf + (size_t)ib * slot;
+      if (direct) {
+        const int f = mine[c0 + k] / nblk;
+        g.C = dCs[f];
+        g.ldc = N;
+        g.rmap = drows + blk_ptr[ib];
+        g.cmap = rank.p + (size_t)f * (N + 8) + koff[ib];
+      } else
+        g.C = dBlockBuf + (size_t)ib * slot;
       gt[2 * nb + k] = g;
       g.A = w.Y[k].p;
       g.tA = 1;
@@ -1354,8 +1428,12 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
         const int ib = mine[c0 + k] % nblk;
         const double *dF = dFs[mine[c0 + k] / nblk];
         int n = ns[k];
-        hipLaunchKernelGGL(k_gather_block, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, dS, N, drows + blk_ptr[ib],
-                           dcols + blk_ptr[ib], n, Fb.p + (size_t)k * nmax * nmax, Xall.p + (size_t)k * nmax * nmax);
+        if (keep_x && w.xc_have[ib])
+          hipLaunchKernelGGL(k_gather_f, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, N, drows + blk_ptr[ib], n, Fb.p + (size_t)k * nmax * nmax);
+        else
+          hipLaunchKernelGGL(k_gather_block, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, dS, N, drows + blk_ptr[ib],
+                             dcols + blk_ptr[ib], n, Fb.p + (size_t)k * nmax * nmax, const_cast<double *>(Xptr[k]));
+        if (keep_x) w.xc_have[ib] = 1;
       }
       // two workgroups per tile (split K) when the batch's tiles would not fill the chip evenly: more than half, fewer
       // than all of the 2 x CU slots; HELFEM_GEMM_SPLITK = 0 / 1 forces it off / on
@@ -1390,30 +1468,69 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
       gemm_tasklist_dev(ctx, w.gtasks.p + nb, nb, nm, nm, low);
       gemm_mirror_lower_dev(ctx, w.gtasks.p + nb, nb, nm);  // the tridiagonalisation sweeps the full square
     }
-    eig_sym_batch(ctx, w, nb, ns.data(), Xptr, nev > 0 ? nevs.data() : nullptr);
+    // direct: everything that needs the eigenvalues alone, on the main stream between the divide-and-conquer stage and the
+    // wait for X Q (the side stream ends after that stage: the main stream would idle there)
+    std::function<void()> after_solve;
+    if (direct)
+      after_solve = [&] {
+        if (w.used_dc) {  // the status word goes home now; the host waits for this point only
+          if (!w.h_status) HFG_HIP_CHECK(hipHostMalloc((void **)&w.h_status, sizeof(int), hipHostMallocDefault));
+          if (!w.status_ev) HFG_HIP_CHECK(hipEventCreateWithFlags(&w.status_ev, hipEventDisableTiming));
+          HFG_HIP_CHECK(hipMemcpyAsync(w.h_status, dc_status_word(ctx), sizeof(int), hipMemcpyDeviceToHost, s));
+          HFG_HIP_CHECK(hipEventRecord(w.status_ev, s));
+        }
+        ProfScope ps(ctx, "scatter");
+        std::vector<const double *> csrc;
+        std::vector<double *> cdst;
+        std::vector<int> cn;
+        for (int k = 0; k < nb; k++) {
+          const int ib = mine[c0 + k] % nblk, f = mine[c0 + k] / nblk;
+          csrc.push_back(nev > 0 ? w.Ws[k].p : w.d[k].p);
+          cdst.push_back(Etmp.p + (size_t)f * N + koff[ib]);
+          cn.push_back(nevs[k]);
+        }
+        copy_slices(s, csrc, cdst, cn);
+        for (int f = 0; f < nF; f++) {
+          int *rk = rank.p + (size_t)f * (N + 8);
+          launch_rank(ctx, Etmp.p + (size_t)f * N, K, rk);
+          hipLaunchKernelGGL(k_place_values, dim3((K + 255) / 256), dim3(256), 0, s, Etmp.p + (size_t)f * N, K, rk, dEs[f]);
+          HFG_HIP_CHECK(hipMemsetAsync(dCs[f], 0, sizeof(double) * (size_t)N * K, s));  // (stream order: ahead of the product, split K adds into it)
+        }
+      };
+    eig_sym_batch(ctx, w, nb, ns.data(), Xptr, nev > 0 ? nevs.data() : nullptr, after_solve);
     {
       ProfScope ps(ctx, "eig_backtransform");
-      // the eigenvalues are final: their copy into the slots goes ahead of the last product, not behind it
-      std::vector<const double *> csrc;
-      std::vector<double *> cdst;
-      std::vector<int> cn;
-      for (int k = 0; k < nb; k++) {
-        const int ib = mine[c0 + k] % nblk;
-        double *slotp = dBlockBufs[mine[c0 + k] / nblk] + (size_t)ib * slot;
-        csrc.push_back(nev > 0 ? w.Ws[k].p : w.d[k].p);
-        cdst.push_back(slotp + nmax * nmax);
-        cn.push_back(nevs[k]);
+      if (!direct) {
+        // the eigenvalues are final: their copy into the slots goes ahead of the last product, not behind it
+        std::vector<const double *> csrc;
+        std::vector<double *> cdst;
+        std::vector<int> cn;
+        for (int k = 0; k < nb; k++) {
+          const int ib = mine[c0 + k] % nblk;
+          double *slotp = dBlockBufs[mine[c0 + k] / nblk] + (size_t)ib * slot;
+          csrc.push_back(nev > 0 ? w.Ws[k].p : w.d[k].p);
+          cdst.push_back(slotp + nmax * nmax);
+          cn.push_back(nevs[k]);
+          if (nev <= 0 && w.full_how.split2 && ctx->shard_n == 1)  // (more ranks: the whole buffer was zeroed above)
+            HFG_HIP_CHECK(hipMemsetAsync(slotp, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
+        }
+        copy_slices(s, csrc, cdst, cn);
       }
-      copy_slices(s, csrc, cdst, cn);
       {
         ProfScope pp3(ctx, "eig_products");
         const GemmTask *last = w.gtasks.p + (w.folded ? 3 : 2) * (size_t)nb;
-        if (nev > 0)  // n x nev products: small tiles, no split
-          gemm_tasklist_dev(ctx, last, nb, nm, *std::max_element(nevs.begin(), nevs.end()), {GemmTile::T64});
-        else
-          gemm_tasklist_dev(ctx, last, nb, nm, nm, w.full_how);  // (split2: the block slots were zeroed above)
+        GemmHow how = nev > 0 ? GemmHow{GemmTile::T64} : w.full_how;  // (n x nev products: small tiles, no split)
+        how.scatter = direct;  // split2: the block slots, or all of C, were zeroed above
+        gemm_tasklist_dev(ctx, last, nb, nm, nev > 0 ? *std::max_element(nevs.begin(), nevs.end()) : nm, how);
       }
     }
+    if (direct && w.used_dc) {
+      // everything is queued: the one host wait, for the status word behind the divide-and-conquer stage (the persistent
+      // tridiagonalisation's words, written before it, are home by then too)
+      HFG_HIP_CHECK(hipEventSynchronize(w.status_ev));
+      if (*w.h_status != 0) throw std::logic_error("Eigendecomposition failed!\n");
+      trdp_check_status(ctx);
+    } else
     check_status(ctx, w, nb);
   }
   HFG_HIP_CHECK(hipGetLastError());
@@ -1476,17 +1593,28 @@ static void eig_assemble_sel_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *b
   HFG_HIP_CHECK(hipGetLastError());
 }
 
-// scf::eig_gsym_sub on one device
-void eig_gsym_sub_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
-                      const int64_t *blk_idx, double *dE, double *dC) {
+// The one-call entries: scf::eig_gsym_sub on one device, whatever the context's shard.  nF matrices with the same Sinvh and
+// blocks; nev > 0: the lowest min(nev, n_b) pairs of every block.  By default nothing goes through block slots
+// (eig_blocks_multi_dev, direct); HELFEM_EIG_DIRECT=0, or more (matrix, block) pairs than one batch holds, takes the two
+// phases through ws[6] -- the checker: same E, same C, bit for bit.
+static void eig_gsym_sub_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
+                                   const int64_t *blk_idx, int nev, double *const *dEs, double *const *dCs) {
   int save_rank = ctx->shard_rank, save_n = ctx->shard_n;
   ctx->shard_rank = 0;
   ctx->shard_n = 1;
   try {
-    DevBuf<double> &buf = ctx->ws[6];
-    buf.resize(eig_block_buf_size(nblk, blk_ptr));
-    eig_blocks_dev(ctx, N, dF, dS, nblk, blk_ptr, blk_idx, buf.p);
-    eig_assemble_dev(ctx, N, nblk, blk_ptr, blk_idx, buf.p, dE, dC);
+    if (helfem::tuning_live().eig_direct && nF * nblk <= MAXB) {  // (read at every call)
+      eig_blocks_multi_dev(ctx, N, nF, dFs, dS, nblk, blk_ptr, blk_idx, nullptr, nev, dEs, dCs);
+    } else {
+      const size_t sz = eig_block_buf_size(nblk, blk_ptr);
+      DevBuf<double> &buf = ctx->ws[6];
+      buf.resize(nF * sz);
+      double *bufs[MAXB];
+      if (nF > MAXB) throw std::logic_error("eig_gsym_sub: too many matrices in one call\n");
+      for (int f = 0; f < nF; f++) bufs[f] = buf.p + f * sz;
+      eig_blocks_multi_dev(ctx, N, nF, dFs, dS, nblk, blk_ptr, blk_idx, bufs, nev);
+      for (int f = 0; f < nF; f++) eig_assemble_sel_dev(ctx, N, nblk, blk_ptr, blk_idx, bufs[f], dEs[f], dCs[f], nev);
+    }
   } catch (...) {
     ctx->shard_rank = save_rank;
     ctx->shard_n = save_n;
@@ -1496,25 +1624,16 @@ void eig_gsym_sub_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, i
   ctx->shard_n = save_n;
 }
 
+void eig_gsym_sub_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
+                      const int64_t *blk_idx, double *dE, double *dC) {
+  eig_gsym_sub_multi_dev(ctx, N, 1, &dF, dS, nblk, blk_ptr, blk_idx, 0, &dE, &dC);
+}
+
 // the lowest min(nev, n_b) eigenpairs of every block on one device: E (K = eig_sel_count values, ascending), C (N x K)
 void eig_gsym_sub_sel_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
                           const int64_t *blk_idx, int nev, double *dE, double *dC) {
   if (nev < 1) throw std::logic_error("eig_gsym_sub_sel: nev must be at least 1\n");
-  int save_rank = ctx->shard_rank, save_n = ctx->shard_n;
-  ctx->shard_rank = 0;
-  ctx->shard_n = 1;
-  try {
-    DevBuf<double> &buf = ctx->ws[6];
-    buf.resize(eig_block_buf_size(nblk, blk_ptr));
-    eig_blocks_multi_dev(ctx, N, 1, &dF, dS, nblk, blk_ptr, blk_idx, &buf.p, nev);
-    eig_assemble_sel_dev(ctx, N, nblk, blk_ptr, blk_idx, buf.p, dE, dC, nev);
-  } catch (...) {
-    ctx->shard_rank = save_rank;
-    ctx->shard_n = save_n;
-    throw;
-  }
-  ctx->shard_rank = save_rank;
-  ctx->shard_n = save_n;
+  eig_gsym_sub_multi_dev(ctx, N, 1, &dF, dS, nblk, blk_ptr, blk_idx, nev, &dE, &dC);
 }
 
 /// column supports of the symmetry blocks of a block-structured Sinvh (scf_helpers.cpp:150-157): cols[blk_ptr[ib] ...] =
@@ -1551,25 +1670,9 @@ void eig_block_supports(hfg_ctx *ctx, int N, const double *dS, int nblk, const i
 // it twice in a row with the same Sinvh and symmetry blocks)
 void eig_gsym_sub_pair_dev(hfg_ctx *ctx, int N, const double *dFa, const double *dFb, const double *dS, int nblk, const int64_t *blk_ptr,
                            const int64_t *blk_idx, double *dEa, double *dCa, double *dEb, double *dCb) {
-  int save_rank = ctx->shard_rank, save_n = ctx->shard_n;
-  ctx->shard_rank = 0;
-  ctx->shard_n = 1;
-  try {
-    const size_t sz = eig_block_buf_size(nblk, blk_ptr);
-    DevBuf<double> &buf = ctx->ws[6];
-    buf.resize(2 * sz);
-    const double *Fs[2] = {dFa, dFb};
-    double *bufs[2] = {buf.p, buf.p + sz};
-    eig_blocks_multi_dev(ctx, N, 2, Fs, dS, nblk, blk_ptr, blk_idx, bufs);
-    eig_assemble_dev(ctx, N, nblk, blk_ptr, blk_idx, bufs[0], dEa, dCa);
-    eig_assemble_dev(ctx, N, nblk, blk_ptr, blk_idx, bufs[1], dEb, dCb);
-  } catch (...) {
-    ctx->shard_rank = save_rank;
-    ctx->shard_n = save_n;
-    throw;
-  }
-  ctx->shard_rank = save_rank;
-  ctx->shard_n = save_n;
+  const double *Fs[2] = {dFa, dFb};
+  double *Es[2] = {dEa, dEb}, *Cs[2] = {dCa, dCb};
+  eig_gsym_sub_multi_dev(ctx, N, 2, Fs, dS, nblk, blk_ptr, blk_idx, 0, Es, Cs);
 }
 
 }  // namespace hfg

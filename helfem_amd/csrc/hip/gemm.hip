@@ -48,12 +48,15 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 // or 64: pure streaming of C) run at 1.2-1.6 TB/s.
 // MAP: column maps (GemmTask::amap, cmap; op(A) = A): column k of A is read at A[:, amap[k]], column j of the product is
 // stored at C[:, cmap[j]]
-template <int BM, int BN, bool ACC = false, int MF = 1, bool MAP = false>
+// RMAP: row and column maps of the stored product (GemmTask::rmap, cmap; any op(A), op(B)): element (i, j) goes to
+// C[rmap[i], cmap[j]]; the operands are read as without maps
+template <int BM, int BN, bool ACC = false, int MF = 1, bool MAP = false, bool RMAP = false>
 __device__ __forceinline__ void dgemm_tile(int id, int transA, int transB, int M, int N, int K, double alpha,
                                            const double *__restrict__ A, int lda, const double *__restrict__ B, int ldb,
                                            double beta, double *__restrict__ C, int ldc, double (*As)[16][BM + 16],
                                            double (*Bs)[16][BN + 16], int sym = 0, int kbeg = 0, int kend = -1, int over = 0,
-                                           const int *__restrict__ amap = nullptr, const int *__restrict__ cmap = nullptr) {
+                                           const int *__restrict__ amap = nullptr, const int *__restrict__ cmap = nullptr,
+                                           const int64_t *__restrict__ rmap = nullptr) {
   constexpr int BK = 16;
   constexpr int PAD = 16;
   constexpr int WM = BM / 2, WN = BN / 2;  // wave tile
@@ -343,7 +346,8 @@ __device__ __forceinline__ void dgemm_tile(int id, int transA, int transB, int M
         int gm = bm + wm + i * 16 + l15, gn = bn + wn + j * 16 + l4 + 4 * r;
         if (gm < M && gn < N) {
           size_t o;
-          if constexpr (MAP) o = (size_t)cmap[gn] * ldc + gm;
+          if constexpr (RMAP) o = (size_t)cmap[gn] * ldc + (size_t)rmap[gm];
+          else if constexpr (MAP) o = (size_t)cmap[gn] * ldc + gm;
           else o = (size_t)gn * ldc + gm;
           double v = alpha * acc(i, j, r);
           if (splitk) {
@@ -393,6 +397,21 @@ __global__ __launch_bounds__(256, 2) void k_dgemm_tasklist_map(const GemmTask *_
                                       0, -1, 0, t.amap, t.cmap);
 }
 
+// The plain task list with the product stored through the tasks' row and column maps (beta == 0, no sym): the last product
+// of the blocked eigensolve writes every eigenvector at its basis-function rows and its ranked column of the N x N matrix
+// (eig.hip), with the k order and the tiles of k_dgemm_tasklist.  Every active task has rmap and cmap set.
+template <int BM, int BN, int MF = 1>
+__global__ __launch_bounds__(256, 2) void k_dgemm_tasklist_scatter(const GemmTask *__restrict__ tasks) {
+  __shared__ __attribute__((aligned(16))) double As[2][16][BM + 16];
+  __shared__ __attribute__((aligned(16))) double Bs[2][16][BN + 16];
+  const GemmTask t = tasks[blockIdx.y];
+  if (t.M <= 0 || t.N <= 0) return;
+  const int nt = ((t.M + BM - 1) / BM) * ((t.N + BN - 1) / BN);
+  if ((int)blockIdx.x >= nt) return;
+  dgemm_tile<BM, BN, false, MF, false, true>(blockIdx.x, t.tA, t.tB, t.M, t.N, t.K, t.alpha, t.A, t.lda, t.B, t.ldb, 0.0, t.C, t.ldc,
+                                             As, Bs, 0, 0, -1, t.over, nullptr, t.cmap, t.rmap);
+}
+
 // Task lists with an explicit workgroup list (task, tile), dealt out so that each XCD takes ONE contiguous eighth of the
 // list: all tiles of a task then run on the same XCD and its A operand is fetched from HBM once instead of by all eight
 // L2s (exchange_lr.hip: the 1.9 MB element table of a task was read 8 times -- 9 of the 15 GB the product fetched).
@@ -439,6 +458,23 @@ __global__ __launch_bounds__(256, 2) void k_dgemm_tasklist_split2(const GemmTask
   const int kbeg = half ? Kh : 0, kend = half ? t.K : Kh;
   if (kbeg >= kend) return;
   dgemm_tile<BM, BN, false, 1>(tile, t.tA, t.tB, t.M, t.N, t.K, t.alpha, t.A, t.lda, t.B, t.ldb, 0.0, t.C, t.ldc, As, Bs, sym, kbeg, kend);
+}
+// the same with the halves added through the tasks' row and column maps (k_dgemm_tasklist_scatter): the mapped elements of
+// C must be zero on entry
+template <int BM, int BN>
+__global__ __launch_bounds__(256, 2) void k_dgemm_tasklist_split2_scatter(const GemmTask *__restrict__ tasks) {
+  __shared__ __attribute__((aligned(16))) double As[2][16][BM + 16];
+  __shared__ __attribute__((aligned(16))) double Bs[2][16][BN + 16];
+  const GemmTask t = tasks[blockIdx.y];
+  if (t.M <= 0 || t.N <= 0) return;
+  const int nt = ((t.M + BM - 1) / BM) * ((t.N + BN - 1) / BN);
+  const int tile = blockIdx.x >> 1, half = blockIdx.x & 1;
+  if (tile >= nt) return;
+  const int Kh = ((t.K / 2 + 15) / 16) * 16;
+  const int kbeg = half ? Kh : 0, kend = half ? t.K : Kh;
+  if (kbeg >= kend) return;
+  dgemm_tile<BM, BN, false, 1, false, true>(tile, t.tA, t.tB, t.M, t.N, t.K, t.alpha, t.A, t.lda, t.B, t.ldb, 0.0, t.C, t.ldc, As, Bs, 0,
+                                            kbeg, kend, 0, nullptr, t.cmap, t.rmap);
 }
 
 // upper triangle := transpose of the lower one for the symmetric products of a task list (sym tasks only): 64 x 64
@@ -499,11 +535,11 @@ const char *tile_name(GemmTile tile) {
 
 // the kernel of a task list: every legal combination maps to one instantiation, anything else is refused
 typedef void (*TaskKernel)(const GemmTask *);
-constexpr int ACC = 1, SPLIT2 = 2, MAP = 4;
-constexpr int variant(GemmTile tile, int flags) { return 8 * (int)tile + flags; }
+constexpr int ACC = 1, SPLIT2 = 2, MAP = 4, SCATTER = 8;
+constexpr int variant(GemmTile tile, int flags) { return 16 * (int)tile + flags; }
 TaskKernel tasklist_kernel(GemmTile tile, const GemmHow &how) {
   const bool m4 = mfma4();
-  switch (variant(tile, how.acc * ACC + how.split2 * SPLIT2 + how.map * MAP)) {
+  switch (variant(tile, how.acc * ACC + how.split2 * SPLIT2 + how.map * MAP + how.scatter * SCATTER)) {
     case variant(GemmTile::T64, 0): return m4 ? k_dgemm_tasklist<64, 64, false, 0> : k_dgemm_tasklist<64, 64>;
     case variant(GemmTile::T128, 0): return m4 ? k_dgemm_tasklist<128, 128, false, 0> : k_dgemm_tasklist<128, 128>;
     case variant(GemmTile::T128x64, 0): return k_dgemm_tasklist<128, 64>;
@@ -512,16 +548,22 @@ TaskKernel tasklist_kernel(GemmTile tile, const GemmHow &how) {
     case variant(GemmTile::T64, MAP): return m4 ? k_dgemm_tasklist_map<0> : k_dgemm_tasklist_map<1>;
     case variant(GemmTile::T128, SPLIT2): return k_dgemm_tasklist_split2<128, 128>;
     case variant(GemmTile::T128x64, SPLIT2): return k_dgemm_tasklist_split2<128, 64>;
+    case variant(GemmTile::T64, SCATTER): return m4 ? k_dgemm_tasklist_scatter<64, 64, 0> : k_dgemm_tasklist_scatter<64, 64>;
+    case variant(GemmTile::T128, SCATTER): return m4 ? k_dgemm_tasklist_scatter<128, 128, 0> : k_dgemm_tasklist_scatter<128, 128>;
+    case variant(GemmTile::T128x64, SCATTER): return k_dgemm_tasklist_scatter<128, 64>;
+    case variant(GemmTile::T128, SPLIT2 + SCATTER): return k_dgemm_tasklist_split2_scatter<128, 128>;
+    case variant(GemmTile::T128x64, SPLIT2 + SCATTER): return k_dgemm_tasklist_split2_scatter<128, 64>;
     default:
       throw std::logic_error(std::string("gemm_tasklist_dev: no kernel for tile ") + tile_name(tile) + (how.acc ? " acc" : "") +
-                             (how.split2 ? " split2" : "") + (how.map ? " map" : ""));
+                             (how.split2 ? " split2" : "") + (how.map ? " map" : "") + (how.scatter ? " scatter" : ""));
   }
 }
 }  // namespace
 
 /// Launches the task list: grid (tiles of a maxM x maxN product, tasks).  GemmHow (internal.h) says which tiles and which
 /// variant of the engine: acc -- streaming epilogue, beta != 0 in every active task; split2 -- two workgroups per tile, each
-/// half of K, beta == 0 tasks whose outputs the caller has ZEROED; map -- GemmTask::amap and cmap set in every active task
+/// half of K, beta == 0 tasks whose outputs the caller has ZEROED; map -- GemmTask::amap and cmap set in every active task;
+/// scatter -- GemmTask::rmap and cmap set in every active task, beta == 0 (with split2: the mapped elements zeroed)
 void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, GemmHow how) {
   if (ntasks <= 0 || maxM <= 0 || maxN <= 0) return;
   GemmTile tile = how.tile;

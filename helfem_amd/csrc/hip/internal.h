@@ -14,7 +14,7 @@ namespace hfg {
 enum class GemmTile { Auto, T64, T128, T128x64 };  // Auto: gemm_prefers_128() picks T64 or T128 (T64 only up to 65535 tasks)
 struct GemmHow {
   GemmTile tile = GemmTile::Auto;
-  bool acc = false, split2 = false, map = false;
+  bool acc = false, split2 = false, map = false, scatter = false;
 };
 // kernel by (tile, variant); HELFEM_MFMA=4x4x4 reaches the plain, acc and map lists and gemm_dev:
 //   {} / {T64} / {T128}           k_dgemm_tasklist<64, 64> or <128, 128>
@@ -22,6 +22,8 @@ struct GemmHow {
 //   {T64 or T128, acc}            k_dgemm_tasklist<.., true>      C = alpha A B + beta C, beta != 0 in every active task
 //   {T64, map}                    k_dgemm_tasklist_map            GemmTask::amap and cmap set in every active task
 //   {T128 or T128x64, split2}     k_dgemm_tasklist_split2<..>     beta == 0 tasks, C zeroed by the caller
+//   {T64, T128 or T128x64, scatter}  k_dgemm_tasklist_scatter<..>  GemmTask::rmap and cmap set in every active task, beta == 0
+//   {T128 or T128x64, split2, scatter}  k_dgemm_tasklist_split2_scatter<..>  likewise, the mapped elements of C zeroed by the caller
 // anything else throws std::logic_error
 void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, GemmHow how = {});  // gemm.hip
 // k_dgemm_tasklist_wl<tile>; T64, T128 or T128x64, split2 with T128x64 only
