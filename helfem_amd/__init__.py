@@ -266,6 +266,23 @@ class Context(object):
         _check(lib().hfg_profile_get(self.h, name.encode(), ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
 
+    def cuhf_update(self, S, Ca, na, Cb, nb, Fa, Fb):
+        """hfg_cuhf_update_devptr on torch tensors of this context's device (contiguous float64, column-major): the
+        constrained-UHF form of ROHF, Fa += lambda and Fb -= lambda in place.  S: overlap (N x N); Ca, Cb: orbitals whose
+        first na / nb columns formed Pa / Pb; N is taken from Fa.  na == nb or min(na, nb) == 0 changes nothing."""
+        N = int(round(Fa.numel() ** 0.5))
+        na, nb = int(na), int(nb)
+        for t, count, what in ((S, N * N, "S"), (Ca, N * na, "Ca"), (Cb, N * nb, "Cb"), (Fa, N * N, "Fa"), (Fb, N * N, "Fb")):
+            if t is None or not (t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float64" and t.numel() >= count):
+                raise ValueError("Context.cuhf_update: %s must be a contiguous float64 tensor on the device with at least %d elements"
+                                 % (what, count))
+        if N * N != Fa.numel() or Fb.numel() != Fa.numel():
+            raise ValueError("Context.cuhf_update: Fa and Fb are N x N")
+        f = lib().hfg_cuhf_update_devptr
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                      ctypes.c_void_p, ctypes.c_void_p]
+        _check(f(self.h, N, S.data_ptr(), Ca.data_ptr(), na, Cb.data_ptr(), nb, Fa.data_ptr(), Fb.data_ptr()))
+
 
 _default_ctx = None
 
@@ -1474,6 +1491,15 @@ class DeviceSCFStep(object):
     def _diis_solve(self, diis):
         diis.solve(self.F)
 
+    # the hook of run() between energy() and the DIIS update: nothing here, the CUHF constraint in DeviceROHFStep
+    _applies_cuhf = False
+
+    def _constraint_begin(self, S):
+        pass
+
+    def _constrain(self):
+        pass
+
     def run(self, S, maxit=50, convthr=1e-7, Enucr=0.0, allreduce=None, exchange_blocks=None, diis=None, callback=None,
             rohf=False, cuhf=False, readocc=None, maverage=False, dampfock=1.0):
         """SCF to convergence: the loop of main.cpp:780-995 with the reference's ADIIS + CDIIS.  S: the overlap matrix (numpy,
@@ -1483,12 +1509,16 @@ class DeviceSCFStep(object):
         exchange_blocks as in step(); every rank runs its own DeviceDIIS on identical inputs, so DIIS adds no collective.
         diis: a DeviceDIIS with its metric set (default: order 5, this step's Sinvh and symmetry blocks); callback(it, Etot,
         maxerr) after every iteration.  Returns the energies of energy() plus iterations, converged and the trace
-        [(Etot, maxerr), ...].  ROHF / CUHF, readocc, maverage and dampfock stay with the drivers: the keywords rohf, cuhf,
+        [(Etot, maxerr), ...].  Restricted open-shell runs are DeviceROHFStep's, whose hook between energy() and the DIIS
+        update applies the CUHF constraint; readocc, maverage and dampfock stay with the drivers.  The keywords rohf, cuhf,
         readocc, maverage and dampfock exist only so that a script ported from the drivers fails loudly (NotImplementedError)
-        instead of running without them; they have no other effect."""
-        _refuse_out_of_scope(type(self).__name__, rohf, cuhf, readocc, maverage, dampfock)
+        instead of running without them; they have no other effect (rohf and cuhf are accepted by DeviceROHFStep, which
+        applies the constraint with or without them)."""
+        _refuse_out_of_scope(type(self).__name__, rohf and not self._applies_cuhf, cuhf and not self._applies_cuhf, readocc, maverage,
+                             dampfock)
         if self.H0 is None:
             raise RuntimeError("run: set_matrices first")
+        self._constraint_begin(S)
         t = self.torch
         if diis is None:
             diis = DeviceDIIS(self.ctx, self.N, self._nspin())
@@ -1502,6 +1532,7 @@ class DeviceSCFStep(object):
         for it in range(1, int(maxit) + 1):
             self._fock_stage(allreduce)
             res = self.energy(Enucr)
+            self._constrain()  # (the energy is that of the unconstrained build, as in the drivers)
             maxerr = self._diis_update(diis, res["Etot"])
             dE = res["Etot"] - Eold
             Eold = res["Etot"]
@@ -1718,3 +1749,47 @@ class DeviceUSCFStep(DeviceSCFStep):
 
     def _diis_solve(self, diis):
         diis.solve(self.Fa, self.Fb)
+
+
+class DeviceROHFStep(DeviceUSCFStep):
+    """DeviceUSCFStep for a restricted open-shell iteration, the constrained-UHF form of ROHF (scf::ROHF_update,
+    scf_helpers.cpp:470-523; --restricted 1 with nela != nelb in the drivers): after the Fock build, Fa += lambda and
+    Fb -= lambda, with lambda the core-virtual coupling of (Fa - Fb) / 2 between the natural orbitals of Pa + Pb, from the
+    occupied orbitals the densities were formed from (Context.cuhf_update, hfg_cuhf_update_devptr).  The eigensolve and the
+    DIIS history see the constrained matrices; the energy is that of the unconstrained build, as in the drivers.  The
+    constraint needs the overlap matrix (run() takes it; set_overlap() before step()) and the orbitals: a density set
+    without them (set_density without Ca, Cb) is refused.  Every rank applies it to identical inputs: no collective.
+    With symmetry blocks lambda is block diagonal up to rounding when the orbitals are; the eigensolve and the blocked DIIS
+    error read the diagonal blocks only."""
+
+    _applies_cuhf = True
+
+    def __init__(self, *args, **kw):
+        super(DeviceROHFStep, self).__init__(*args, **kw)
+        self.S = None
+
+    def set_overlap(self, S):
+        """the overlap matrix (numpy, N x N) the constraint is formed with; kept on the device"""
+        S = np.asfortranarray(S, dtype=np.float64)
+        if S.shape != (self.N, self.N):
+            raise ValueError("DeviceROHFStep.set_overlap: S is N x N")
+        self.S = self.torch.from_numpy(S.ravel(order="F").copy()).to(self.dev)
+
+    def _constraint_begin(self, S):
+        if S is not None:
+            self.set_overlap(S)
+
+    def _constrain(self):
+        if self.S is None:
+            raise RuntimeError("DeviceROHFStep: set_overlap first")
+        if not self.have_C:
+            raise RuntimeError("DeviceROHFStep: the constraint needs the orbitals the densities were formed from "
+                               "(set_density with Ca and Cb, or start from the core guess)")
+        self.ctx.cuhf_update(self.S, self.Ca, self.nela, self.Cb, self.nelb, self.Fa, self.Fb)
+
+    def step(self, allreduce=None, exchange_blocks=None):
+        """one iteration of DeviceUSCFStep.step with the constraint between the Fock build and the eigensolve"""
+        self._fock_stage(allreduce)
+        self._constrain()
+        self._eig_stage(allreduce, exchange_blocks)
+        self._density_stage()

@@ -151,6 +151,15 @@ void diis_history_dev(hfg_ctx *ctx, const DiisHistory &h, int j0, int nhtot, con
 // dFa = sum_k w_k F_k[0 : NN], dFb = sum_k w_k F_k[NN : 2 NN] (nspin == 2)
 void diis_extrapolate_dev(hfg_ctx *ctx, const DiisComb &c, size_t NN, int nspin, double *dFa, double *dFb);  // diis_dev.hip
 
+// cuhf_dev.hip: the constrained-UHF form of ROHF (scf::ROHF_update) on device pointers
+constexpr int CUHF_LR_MAXCOLS = 128;  // occupied columns of both spins together that the low-rank route takes
+// Fa += lambda, Fb -= lambda from the occupied orbitals (N x nocca, N x noccb) and S: rank nocca + noccb work
+void cuhf_lowrank_dev(hfg_ctx *ctx, int N, const double *dS, const double *dCa, int nocca, const double *dCb, int noccb, double *dFa,
+                      double *dFb);  // cuhf_dev.hip
+// the dense sequence of the SCF driver from P = Pa + Pb, Sh (N x n, Sh^T Sinvh = 1) and Sinvh (N x n)
+void cuhf_dense_dev(hfg_ctx *ctx, int N, int n, const double *dP, const double *dSh, const double *dSinvh, int nocca, int noccb,
+                    double *dFa, double *dFb);  // cuhf_dev.hip
+
 // scf_device.hip
 helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::scf::Options &opt, int nel, double Enucr, int symm,
                                     const std::vector<std::vector<size_t> > &dsym, int ldft, int mdft,

@@ -34,6 +34,7 @@ enum class RsTei { host, dev };
   X(uscf_kbatch, bool, false, "HELFEM_USCF_KBATCH", true, "=1", atoi(e) == 1, "DeviceUSCFStep: K[Pa] and K[Pb] through one call of hfg_exchange_occ_batch_devptr; off: one call per spin") \
   X(diis_blocks, bool, true, "HELFEM_DIIS_BLOCKS", false, "off if 0", atoi(e) != 0, "DIIS error per symmetry block; off: the four dense N^3 products (checker)") \
   X(diis_lowrank, bool, true, "HELFEM_DIIS_LOWRANK", false, "off if 0", atoi(e) != 0, "blocked DIIS error from the occupied orbitals; off: per-block n^3 products from F and P (checker)") \
+  X(cuhf_lowrank, bool, true, "HELFEM_CUHF_LOWRANK", true, "off if 0", atoi(e) != 0, "hfg_cuhf_update_devptr: the constraint from the occupied orbitals (rank na + nb, up to 128 columns); off: the dense natural-orbital sequence always (checker)") \
   X(eig_pair, bool, true, "HELFEM_EIG_PAIR", false, "off if 0", atoi(e) != 0, "both spins' Fock matrices in one batched eigensolve; off: two calls") \
   X(eig_direct, bool, true, "HELFEM_EIG_DIRECT", true, "off if 0", atoi(e) != 0, "one-call blocked eigensolve (hfg_eig_gsym_sub_dev, _sel_dev, _pair_devptr) ranks before its last product and stores that product straight into C; off: block slots, then hfg_eig_assemble_dev (checker)") \
   X(trd_mode, TrdMode, TrdMode::persistent, "HELFEM_TRD", false, "word", !strcmp(e, "persistent") ? TrdMode::persistent : !strcmp(e, "twokernel") ? TrdMode::twokernel : !strcmp(e, "unblocked") ? TrdMode::unblocked : TrdMode::chain, "tridiagonalisation: persistent = k_trdp where the batch fits, else the chain; chain (and any unknown word) = one k_trdf launch per column always (checker); twokernel = k_trdb_gemv + k_trdb_w; unblocked = the first-generation kernels") \

@@ -415,6 +415,25 @@ int hfg_fock_finish_pol_devptr(hfg_ctx *ctx, hfg_basis *basis, const double *dFc
 int hfg_eig_gsym_sub_pair_devptr(hfg_ctx *ctx, int64_t N, const double *dFa, const double *dFb, const double *dSinvh, int nblk,
                                  const int64_t *blk_ptr, const int64_t *blk_idx, double *dEa, double *dCa, double *dEb,
                                  double *dCb);
+/* The constrained-UHF form of ROHF, scf::ROHF_update (scf_helpers.cpp:470-523), on matrices in HBM (column-major): dFa += lambda,
+ * dFb -= lambda in place, lambda the core-virtual coupling of (Fa - Fb) / 2 between the natural orbitals of Pa + Pb.  dS: the
+ * overlap (N x N); dCa (N x nocca) and dCb (N x noccb): the occupied orbitals the densities were formed from, Pa = Ca Ca^T,
+ * Pb = Cb Cb^T.  With nocca + noccb <= 128 the natural orbitals of non-zero occupation come from the eigenvectors of the
+ * (nocca + noccb)-order matrix C^T S C and lambda from rank-(nocca + noccb) products: O(N^2 (nocca + noccb)) work, Fa and Fb
+ * read twice and written once.  More columns, or HELFEM_CUHF_LOWRANK=0 (read at every call), take the dense sequence of the
+ * SCF driver: S^{-1/2} and its partner from dS, P from the orbitals, an eigensolve of order N and eight N^3 products.  Both
+ * need non-zero occupation gaps at the core / active and active / virtual boundaries.  nocca == noccb, or either zero, leaves
+ * dFa and dFb untouched and launches nothing.  Everything is queued on the context's stream behind the caller's work there and
+ * the outputs are ordered with what the caller queues next; the eigensolver's status read-back synchronises the stream once per
+ * call (the dense route, which also forms S^{-1/2}: three times), growth of the context's workspace when a larger shape arrives once more.  Fixed summation
+ * orders and no atomics: two contexts give equal bits, and on the low-rank route lambda is symmetric bit for bit.  Named
+ * *_devptr, not *_dev, like hfg_coulomb_batch_devptr: the stream ordering is tested in tests/test_gpu_cuhf_stream_order.py.
+ * hfg_rohf_update is the same update on host matrices as the reference states it, from P = Pa + Pb, Sh (N x n, the partner
+ * of Sinvh: Sh^T Sinvh = 1) and Sinvh (N x n): the dense sequence, since it has no orbitals. */
+int hfg_cuhf_update_devptr(hfg_ctx *ctx, int64_t N, const double *dS, const double *dCa, int64_t nocca, const double *dCb,
+                           int64_t noccb, double *dFa, double *dFb);
+int hfg_rohf_update(hfg_ctx *ctx, int64_t N, int64_t n, double *Fa, double *Fb, const double *P, const double *Sh,
+                    const double *Sinvh, int64_t nocca, int64_t noccb);
 /* Which entries of the compact buffer the caller reads.  blockid_dev: the device array hfg_fock_finish_dev takes as
  * dBlockId (symmetry block of every basis function), or NULL to clear.  A set-up call (it synchronises the device and
  * copies the array to the host): from it the context derives the shell pairs (x, y) in which some function of x and some

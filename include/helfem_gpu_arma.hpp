@@ -418,6 +418,20 @@ Mat form_Sinvh(const Context &ctx, const Mat &S, bool chol, const std::vector<UV
   check(hfg_form_sinvh(ctx.handle(), (int64_t)N, detail::data_of(S, 0), chol ? 1 : 0, (int)m_idx.size(), ptr.data(), idx.data(), detail::data_of(X, 0)));
   return X;
 }
+/// scf::ROHF_update (scf_helpers.cpp:470), the constrained-UHF form of ROHF: Fa += lambda, Fb -= lambda in place, from the total
+/// density P, Sh (the partner of Sinvh: Sh^T Sinvh = 1) and Sinvh (N x n).  Host matrices carry no orbitals, so this is the
+/// dense natural-orbital sequence on the device (hfg_rohf_update); a loop that keeps its matrices in HBM and knows its occupied
+/// orbitals calls hfg_cuhf_update_devptr instead, whose work is O(N^2 (nocca + noccb)).
+template <class Mat>
+void ROHF_update(const Context &ctx, Mat &Fa, Mat &Fb, const Mat &P, const Mat &Sh, const Mat &Sinvh, size_t nocca, size_t noccb) {
+  const size_t N = Fa.n_rows, n = Sinvh.n_cols;
+  detail::need_square(Fa, N, "ROHF_update");
+  detail::need_square(Fb, N, "ROHF_update");
+  detail::need_square(P, N, "ROHF_update");
+  if ((size_t)Sinvh.n_rows != N || (size_t)Sh.n_rows != N || (size_t)Sh.n_cols != n) throw std::logic_error("ROHF_update: incompatible dimensions\n");
+  check(hfg_rohf_update(ctx.handle(), (int64_t)N, (int64_t)n, detail::data_of(Fa, 0), detail::data_of(Fb, 0), detail::data_of(P, 0),
+                        detail::data_of(Sh, 0), detail::data_of(Sinvh, 0), (int64_t)nocca, (int64_t)noccb));
+}
 }  // namespace scf
 
 /// the whole calculation with every matrix resident in HBM (hfg_scf_run): what a driver calls instead of looping over

@@ -1,0 +1,31 @@
+"""Worker of tests/test_gpu_rohf_run.py: two ranks (gloo) on ONE GPU run DeviceROHFStep.run to convergence, every rank with
+its own DeviceDIIS and its own constraint, and every rank writes its energies, iteration count and trace."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main(out_prefix, names):
+    import helfem_amd as hf
+    from helfem_amd import parallel
+    import rohf_run_common as common
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank, local_rank, world = parallel.init(backend="gloo" if world > 1 else None)
+    allred = parallel.allreduce_sum_ if world > 1 else None
+    xblocks = parallel.broadcast_block_slots_ if world > 1 else None
+    out = {}
+    for name in names:
+        step, S, Enucr = common.make_step(hf, name, rank=rank, nranks=world)
+        out[name] = step.run(S, Enucr=Enucr, allreduce=allred, exchange_blocks=xblocks)
+    json.dump(out, open("%s.rank%d.json" % (out_prefix, rank), "w"))
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main(sys.argv[1], sys.argv[2].split(","))
