@@ -663,6 +663,83 @@ class AtomicTwoDBasis(TwoDBasis):
         _check(lib().hfg_rs_exchange(ctx.h, self.h, _p(P), _p(K)))
         return K
 
+    # ---- the mixed-kernel table set: alpha K[1/r12] + beta K[screened kernel] in one build ----------------
+    def mix_exchange_tables(self, alpha, beta, ctx=None):
+        """hfg_mix_exchange_tables: mix the uploaded Coulomb and range-separated tables on the device for
+        K = alpha K[1/r12] + beta K[screened].  Uploads first when nothing is uploaded.  True: the set is there (a repeated
+        call with the same values does no work); False: it would exceed the bound of the pair path, nothing was allocated
+        and K is to be built from the two table sets."""
+        if ctx is not None and self._uploaded is None:
+            self.upload(ctx=ctx)
+        ctx = ctx or self._ensure()
+        f = lib().hfg_mix_exchange_tables
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
+        rc = f(ctx.h, self.h, float(alpha), float(beta))
+        if rc == 4:
+            return False
+        _check(rc)
+        return True
+
+    def mix_exchange(self, P):
+        """alpha K[P] + beta K_screened[P] from the mixed set (hfg_mix_exchange); numpy in, numpy out"""
+        if self.ctx is None:
+            raise RuntimeError("The mixed exchange tables have not been built (mix_exchange_tables)!")
+        P = _f(P)
+        K = np.zeros_like(P, order="F")
+        f = lib().hfg_mix_exchange
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_double_p, c_double_p]
+        _check(f(self.ctx.h, self.h, _p(P), _p(K)))
+        return K
+
+    def mix_exchange_torch(self, dP, dC=None, nocc=None, out=None, ctx=None):
+        """the device-pointer entries on torch tensors in HBM (contiguous float64).  dP: nP densities of Nbf x Nbf, one after
+        the other, column-major; dC (optional): nP sets of Nbf x Nbf orbital columns, the first nocc[b] of set b being the
+        factors of P_b.  One density goes through hfg_mix_exchange_devptr / hfg_mix_exchange_occ_devptr (nocc an integer or
+        a list of one), more through hfg_mix_exchange_occ_batch_devptr.  Queued on the context's stream, honours its shard,
+        not waited for; returns `out`."""
+        import torch
+        ctx = ctx or self.ctx
+        N = self.Nbf()
+        N2 = N * N
+        if out is None:
+            out = torch.empty_like(dP)
+        for t in (dP, out) + ((dC,) if dC is not None else ()):
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() % N2 or t.numel() != dP.numel():
+                raise ValueError("mix_exchange_torch: contiguous float64 device tensors of nP * Nbf * Nbf elements")
+        nP = dP.numel() // N2
+        L = lib()
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        if dC is not None:
+            counts = np.ascontiguousarray(np.atleast_1d(nocc), dtype=np.int64)
+            if len(counts) != nP:
+                raise ValueError("mix_exchange_torch: one count of occupied orbitals per density")
+        if nP == 1 and dC is None:
+            L.hfg_mix_exchange_devptr.argtypes = [ctypes.c_void_p] * 4
+            _check(L.hfg_mix_exchange_devptr(ctx.h, self.h, ptr(dP), ptr(out)))
+        elif nP == 1:
+            L.hfg_mix_exchange_occ_devptr.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
+            _check(L.hfg_mix_exchange_occ_devptr(ctx.h, self.h, ptr(dP), ptr(dC), int(counts[0]), ptr(out)))
+        else:
+            L.hfg_mix_exchange_occ_batch_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                            c_i64_p, ctypes.c_int64, ctypes.c_void_p]
+            _check(L.hfg_mix_exchange_occ_batch_devptr(ctx.h, self.h, nP, ptr(dP), ptr(dC) if dC is not None else None,
+                                                       counts.ctypes.data_as(c_i64_p) if dC is not None else None, N, ptr(out)))
+        return out
+
+    def mixed_table(self, L, iel, kel):
+        """one block of the mixed set read back from the device, padded: p^2 x p^2, rows = primitives of element iel, columns
+        = primitives of element kel (hfg_basis_get_prim, which = 16)"""
+        f = lib().hfg_basis_get_prim
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
+                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+        r, c = ctypes.c_int64(), ctypes.c_int64()
+        ctxh = self.ctx.h if self.ctx is not None else None
+        idx = int(iel) * self._Nel + int(kel)
+        _check(f(ctxh, self.h, 16, int(L), idx, None, ctypes.byref(r), ctypes.byref(c)))
+        out = np.zeros((r.value, c.value), order="F")
+        _check(f(ctxh, self.h, 16, int(L), idx, _p(out), ctypes.byref(r), ctypes.byref(c)))
+        return out
+
 
 def exchange_batch_plan(ranks, max_members=0):
     """chunks of a batched exchange build (hfg_exchange_batch_plan, no device): (chunk_of, nchunks) for the ranks of the
@@ -1233,6 +1310,11 @@ class DeviceDIIS(object):
         return self._get(3, self.nspin * n * n).reshape(self.nspin, n, n).transpose(0, 2, 1)
 
 
+# HELFEM_EXL_MIX unset: whether a screened kernel's hybrids (1 Yukawa, 2 erfc) take the mixed-kernel table set; as measured
+# (profiles/exl_mix_time.txt) the one build's latency is 1.9 to 3.3 times shorter than that of the step objects' two builds, for both kernels
+MIX_BY_DEFAULT = {1: True, 2: True}
+
+
 def _refuse_out_of_scope(who, rohf, cuhf, readocc, maverage, dampfock):
     """what the step objects' run() leaves to the drivers (hfg_scf_run)"""
     bad = [name for name, on in (("ROHF", rohf), ("CUHF", cuhf), ("readocc", readocc is not None and int(readocc) >= 0),
@@ -1252,9 +1334,10 @@ class DeviceSCFStep(object):
     """
 
     def __init__(self, basis, x_func, c_func, ldft, mdft, nocc, symmetry=1, device=0, rank=0, nranks=1,
-                 dens_thr=1e-12, kfrac=0.0, device_tei=False, fock_shard="auto"):
+                 dens_thr=1e-12, kfrac=0.0, device_tei=False, fock_shard="auto", kshort=0.0, omega=0.0, rs_kind=None):
         self.nocc = int(nocc)
-        self._setup(basis, x_func, c_func, ldft, mdft, symmetry, device, rank, nranks, dens_thr, kfrac, device_tei, fock_shard)
+        self._setup(basis, x_func, c_func, ldft, mdft, symmetry, device, rank, nranks, dens_thr, kfrac, device_tei, fock_shard,
+                    kshort, omega, rs_kind)
         f64 = dict(dtype=self.torch.float64, device=self.dev)
         L, N = lib(), self.N
         self.Fc = self.torch.zeros(int(L.hfg_fock_compact_size(basis.h)), **f64)
@@ -1265,12 +1348,25 @@ class DeviceSCFStep(object):
         self.P = self.torch.zeros(N * N, **f64)
         nb = int(L.hfg_eig_block_buf_size(len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p)))
         self.blockbuf = self.torch.zeros(nb, **f64)
-        if self.kfrac != 0.0:
+        if self.anyK:
             self.K = self.torch.zeros(N * N, **f64)
             self.Pa = self.torch.zeros(N * N, **f64)
 
-    def _setup(self, basis, x_func, c_func, ldft, mdft, symmetry, device, rank, nranks, dens_thr, kfrac, device_tei, fock_shard):
+    def _setup(self, basis, x_func, c_func, ldft, mdft, symmetry, device, rank, nranks, dens_thr, kfrac, device_tei, fock_shard,
+               kshort=0.0, omega=0.0, rs_kind=None):
         """what the restricted and the unrestricted step share: context, shard, tables, symmetry blocks and their declaration"""
+        # range-separated hybrids: F += kfrac K[1/r12] + kshort K[screened kernel of range omega] (atomic/main.cpp:763-780)
+        self.kshort, self.omega = float(kshort), float(omega)
+        self.rs_kind = 0
+        self.mix = False  # K from one build on the mixed-kernel table set
+        self.Krs = None   # the screened matrix of the two-build route
+        if self.kshort != 0.0:
+            if not isinstance(basis, AtomicTwoDBasis):
+                raise RuntimeError("Range separated functionals are not supported.")  # diatomic/main.cpp:393
+            self.rs_kind = xc_rs_kind(x_func) if rs_kind is None else int(rs_kind)
+            if self.rs_kind not in (1, 2) or self.omega == 0.0:
+                raise ValueError("kshort != 0 needs a screened kernel (rs_kind 1 Yukawa or 2 erfc, from the exchange functional "
+                                 "when None) and its range omega != 0")
         import torch
         self.torch = torch
         self.basis = basis
@@ -1286,8 +1382,20 @@ class DeviceSCFStep(object):
         # xGMI.  The exchange build (tens of ms) and the eigensolve's blocks are always sharded.
         self.fock_shard = os.environ.get("HELFEM_FOCK_SHARD", fock_shard)  # the environment wins (tests, A/B runs)
         if device_tei:  # in-element tables (with the exchange-ordered ones when K is wanted) built on this context's device
-            basis.compute_tei(float(kfrac) != 0.0, device=True, ctx=self.ctx)
+            basis.compute_tei(float(kfrac) != 0.0 or self.kshort != 0.0, device=True, ctx=self.ctx)
+        if self.kshort != 0.0:
+            # the screened tables: on the device with device_tei, otherwise where HELFEM_RS_TEI puts the drivers' (host: threaded
+            # host code and upload)
+            switches = {r["name"]: r["value"] for r in tuning_table()}
+            on_device = bool(device_tei) or switches["HELFEM_RS_TEI"] == "dev"
+            basis._compute_rs(self.rs_kind, self.omega, on_device, self.ctx)
         basis.upload(ldft, mdft, ctx=self.ctx)
+        if self.kshort != 0.0:
+            # HELFEM_EXL_MIX: 0 the two builds (checker), positive the mixed set, negative (default) by kernel kind as measured
+            want = int(switches["HELFEM_EXL_MIX"])
+            if want > 0 or (want < 0 and MIX_BY_DEFAULT[self.rs_kind]):
+                # False: beyond the bound of the pair path, nothing allocated -- the two-build route
+                self.mix = basis.mix_exchange_tables(float(kfrac), self.kshort, ctx=self.ctx)
         L = lib()
         L.hfg_fock_compact_size.restype = ctypes.c_int64
         L.hfg_eig_block_buf_size.restype = ctypes.c_int64
@@ -1307,9 +1415,18 @@ class DeviceSCFStep(object):
         self.Sinvh = None
         # hybrid functionals: F += kfrac K[Pa] (main.cpp:820-877); K is dense, its shards (output shells j % n == rank) sum
         self.kfrac = float(kfrac)
+        self.anyK = self.kfrac != 0.0 or self.kshort != 0.0
+        # what _add_exchange and the energy multiply self.K with: with a screened term exchange() leaves the weighted sum
+        self.kscale = self.kfrac if self.kshort == 0.0 else 1.0
         self.have_C = False
         self.have_density = False  # set_density() or density() has filled the density buffers
-        if self.kfrac != 0.0:
+        if self.kshort != 0.0:
+            self.Krs = None if self.mix else torch.zeros(N * N, dtype=torch.float64, device=self.dev)
+            for name in ("hfg_rs_exchange_dev", "hfg_mix_exchange_devptr"):
+                getattr(L, name).argtypes = [ctypes.c_void_p] * 4
+            L.hfg_mix_exchange_occ_devptr.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
+            L.hfg_mix_exchange_occ_batch_devptr.argtypes = L.hfg_exchange_occ_batch_devptr.argtypes
+        if self.anyK:
             L.hfg_exchange_occ_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                ctypes.c_void_p]
             L.hfg_exchange_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -1336,11 +1453,30 @@ class DeviceSCFStep(object):
     def exchange(self):
         """K[Pa], Pa = P/2 (closed shell; basis.exchange(Pa) of main.cpp:822) into self.K"""
         self.torch.mul(self.P, 0.5, out=self.Pa)
-        if self.have_C:
-            _check(lib().hfg_exchange_occ_dev(self.ctx.h, self.basis.h, self._ptr(self.Pa), self._ptr(self.C),
-                                              ctypes.c_int64(self.nocc), self._ptr(self.K)))
-        else:
-            _check(lib().hfg_exchange_dev(self.ctx.h, self.basis.h, self._ptr(self.Pa), self._ptr(self.K)))
+        self._build_K(self.Pa, self.C, self.nocc, self.K)
+
+    def _build_K(self, P, C, nocc, K):
+        """one spin's exchange matrix into K: K[P] without a screened term (the caller weights it with kfrac); with one,
+        kfrac K[P] + kshort K_screened[P], from one build on the mixed set or (HELFEM_EXL_MIX=0, a set beyond the bound) from
+        the two table sets, added on the device"""
+        L, h, b = lib(), self.ctx.h, self.basis.h
+        if self.mix:
+            if self.have_C:
+                _check(L.hfg_mix_exchange_occ_devptr(h, b, self._ptr(P), self._ptr(C), ctypes.c_int64(nocc), self._ptr(K)))
+            else:
+                _check(L.hfg_mix_exchange_devptr(h, b, self._ptr(P), self._ptr(K)))
+            return
+        if self.kfrac != 0.0:
+            if self.have_C:
+                _check(L.hfg_exchange_occ_dev(h, b, self._ptr(P), self._ptr(C), ctypes.c_int64(nocc), self._ptr(K)))
+            else:
+                _check(L.hfg_exchange_dev(h, b, self._ptr(P), self._ptr(K)))
+        if self.kshort != 0.0:
+            _check(L.hfg_rs_exchange_dev(h, b, self._ptr(P), self._ptr(self.Krs)))
+            if self.kfrac != 0.0:
+                K.mul_(self.kfrac).add_(self.Krs, alpha=self.kshort)
+            else:
+                self.torch.mul(self.Krs, self.kshort, out=K)
 
     def fock_partial(self):
         _check(lib().hfg_fock_compact_dev(self.ctx.h, self.basis.h, self.x_func, self.c_func, self._ptr(self.P),
@@ -1386,11 +1522,11 @@ class DeviceSCFStep(object):
             allreduce(self.Fc)
             allreduce(self.scal)
         self.fock_finish()
-        if self.kfrac != 0.0:
+        if self.anyK:
             self.exchange()
             if allreduce is not None:
                 allreduce(self.K)
-            self.F.add_(self.K, alpha=self.kfrac)  # K of a block-diagonal density is block diagonal: no mask needed
+            self.F.add_(self.K, alpha=self.kscale)  # K of a block-diagonal density is block diagonal: no mask needed
         self._eig_stage(allreduce, exchange_blocks)
         self.density()
         self.have_C = True  # self.C now holds the orbitals self.P was formed from
@@ -1418,14 +1554,14 @@ class DeviceSCFStep(object):
         else:
             self._whole_shard(self.fock_partial)
         self.fock_finish()
-        if self.kfrac != 0.0:
+        if self.anyK:
             self.exchange()
             if allreduce is not None:
                 allreduce(self.K)
             self._add_exchange()
 
     def _add_exchange(self):
-        self.F.add_(self.K, alpha=self.kfrac)
+        self.F.add_(self.K, alpha=self.kscale)
 
     def _eig_stage(self, allreduce, exchange_blocks):
         """the eigensolve half of step(): one call on one rank without collectives, else eig_partial, collective, eig_finish"""
@@ -1446,11 +1582,11 @@ class DeviceSCFStep(object):
         return self.J
 
     def _energy_terms(self):
-        """device scalars [E1, 2 Ecoul, Exx / kfrac]"""
+        """device scalars [E1, 2 Ecoul, Exx / _exx_factor()]"""
         t = self.torch
         J = self._coulomb_energy_matrix(self.P)
         terms = [t.dot(self.P, self.H0), t.dot(self.P, J)]
-        terms.append(t.dot(self.Pa, self.K) if self.kfrac != 0.0 else t.zeros((), dtype=t.float64, device=self.dev))
+        terms.append(t.dot(self.Pa, self.K) if self.anyK else t.zeros((), dtype=t.float64, device=self.dev))
         return terms
 
     def energy(self, Enucr=0.0):
@@ -1464,7 +1600,7 @@ class DeviceSCFStep(object):
         return r
 
     def _exx_factor(self):
-        return self.kfrac  # Exx = tr(Pa kfrac K[Pa]), Pa = P / 2, both spins
+        return self.kscale  # Exx = tr(Pa kfrac K[Pa]), Pa = P / 2, both spins (a screened term: K holds the weighted sum)
 
     def _nspin(self):
         return 1
@@ -1564,11 +1700,12 @@ class DeviceUSCFStep(DeviceSCFStep):
     """
 
     def __init__(self, basis, x_func, c_func, ldft, mdft, nocc, symmetry=1, device=0, rank=0, nranks=1,
-                 dens_thr=1e-12, kfrac=0.0, device_tei=False, fock_shard="auto"):
+                 dens_thr=1e-12, kfrac=0.0, device_tei=False, fock_shard="auto", kshort=0.0, omega=0.0, rs_kind=None):
         self.nela, self.nelb = int(nocc[0]), int(nocc[1])
         if self.nela < 1 or self.nelb < 0:
             raise ValueError("DeviceUSCFStep: nocc = (nela >= 1, nelb >= 0)")
-        self._setup(basis, x_func, c_func, ldft, mdft, symmetry, device, rank, nranks, dens_thr, kfrac, device_tei, fock_shard)
+        self._setup(basis, x_func, c_func, ldft, mdft, symmetry, device, rank, nranks, dens_thr, kfrac, device_tei, fock_shard,
+                    kshort, omega, rs_kind)
         t, N, L = self.torch, self.N, lib()
         f64 = dict(dtype=t.float64, device=self.dev)
         self.nc = int(L.hfg_fock_compact_size(basis.h))
@@ -1581,7 +1718,7 @@ class DeviceUSCFStep(DeviceSCFStep):
             nb = int(L.hfg_eig_block_buf_size(len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p)))
             self.blockbuf_a, self.blockbuf_b = t.zeros(nb, **f64), t.zeros(nb, **f64)
         self.kbatch = False
-        if self.kfrac != 0.0:  # one buffer, so that one all-reduce serves both spins
+        if self.anyK:  # one buffer, so that one all-reduce serves both spins
             self.K = t.zeros(2 * N * N, **f64)
             self.Ka, self.Kb = self.K[:N * N], self.K[N * N:]
             # HELFEM_USCF_KBATCH=1 (off by default): both spins through one batched exchange build, from staging buffers
@@ -1590,6 +1727,8 @@ class DeviceUSCFStep(DeviceSCFStep):
             if self.kbatch:
                 self.Pab, self.Cab = t.zeros(2 * N * N, **f64), t.zeros(2 * N * N, **f64)
                 self._nocc = np.array([self.nela, self.nelb], dtype=np.int64)
+                if self.Krs is not None:  # the two-build route: both spins' screened matrices side by side
+                    self.Krs = t.zeros(2 * N * N, **f64)
 
     def _spins(self):
         return ((self.Pa, self.Fa, self.Ea, self.Ca, self.nela), (self.Pb, self.Fb, self.Eb, self.Cb, self.nelb))
@@ -1611,24 +1750,35 @@ class DeviceUSCFStep(DeviceSCFStep):
         """K[Pa] and K[Pb] (basis.exchange of main.cpp:822-829) into self.Ka, self.Kb"""
         if self.kbatch:
             N2 = self.N * self.N
+            L, h, b = lib(), self.ctx.h, self.basis.h
             self.Pab[:N2].copy_(self.Pa)
             self.Pab[N2:].copy_(self.Pb)
             if self.have_C:
                 self.Cab[:N2].copy_(self.Ca)
                 self.Cab[N2:].copy_(self.Cb)
-                _check(lib().hfg_exchange_occ_batch_devptr(self.ctx.h, self.basis.h, 2, self._ptr(self.Pab), self._ptr(self.Cab),
+            if self.mix:  # both spins' weighted sums from the mixed set
+                _check(L.hfg_mix_exchange_occ_batch_devptr(h, b, 2, self._ptr(self.Pab), self._ptr(self.Cab) if self.have_C else None,
+                                                           self._nocc.ctypes.data_as(c_i64_p) if self.have_C else None, self.N,
+                                                           self._ptr(self.K)))
+                return
+            if self.kfrac != 0.0:
+                if self.have_C:
+                    _check(L.hfg_exchange_occ_batch_devptr(h, b, 2, self._ptr(self.Pab), self._ptr(self.Cab),
                                                            self._nocc.ctypes.data_as(c_i64_p), self.N, self._ptr(self.K)))
-            else:
-                _check(lib().hfg_exchange_batch_devptr(self.ctx.h, self.basis.h, 2, self._ptr(self.Pab), self._ptr(self.K)))
+                else:
+                    _check(L.hfg_exchange_batch_devptr(h, b, 2, self._ptr(self.Pab), self._ptr(self.K)))
+            if self.kshort != 0.0:  # the two-build route
+                _check(L.hfg_rs_exchange_batch_devptr(h, b, 2, self._ptr(self.Pab), self._ptr(self.Krs)))
+                if self.kfrac != 0.0:
+                    self.K.mul_(self.kfrac).add_(self.Krs, alpha=self.kshort)
+                else:
+                    self.torch.mul(self.Krs, self.kshort, out=self.K)
             return
         for (P, _, _, C, nocc), K in zip(self._spins(), (self.Ka, self.Kb)):
             if nocc == 0:
                 K.zero_()
-            elif self.have_C:
-                _check(lib().hfg_exchange_occ_dev(self.ctx.h, self.basis.h, self._ptr(P), self._ptr(C), ctypes.c_int64(nocc),
-                                                  self._ptr(K)))
             else:
-                _check(lib().hfg_exchange_dev(self.ctx.h, self.basis.h, self._ptr(P), self._ptr(K)))
+                self._build_K(P, C, nocc, K)
 
     def fock_partial(self):
         _check(lib().hfg_fock_compact_pol_devptr(self.ctx.h, self.basis.h, self.x_func, self.c_func, self._ptr(self.Pa),
@@ -1679,12 +1829,11 @@ class DeviceUSCFStep(DeviceSCFStep):
             allreduce(self.Fc)
             allreduce(self.scal)
         self.fock_finish()
-        if self.kfrac != 0.0:
+        if self.anyK:
             self.exchange()
             if allreduce is not None:
                 allreduce(self.K)
-            self.Fa.add_(self.Ka, alpha=self.kfrac)
-            self.Fb.add_(self.Kb, alpha=self.kfrac)
+            self._add_exchange()
         if self.nranks == 1:
             self.eig_pair()
         else:
@@ -1700,8 +1849,8 @@ class DeviceUSCFStep(DeviceSCFStep):
 
     # ---- the pieces of DeviceSCFStep.run that differ for two spins -----------------------------------------------------
     def _add_exchange(self):
-        self.Fa.add_(self.Ka, alpha=self.kfrac)
-        self.Fb.add_(self.Kb, alpha=self.kfrac)
+        self.Fa.add_(self.Ka, alpha=self.kscale)
+        self.Fb.add_(self.Kb, alpha=self.kscale)
 
     def _eig_stage(self, allreduce, exchange_blocks):
         if self.nranks == 1:
@@ -1722,12 +1871,12 @@ class DeviceUSCFStep(DeviceSCFStep):
         t.add(self.Pa, self.Pb, out=self.Pt)
         J = self._coulomb_energy_matrix(self.Pt)
         terms = [t.dot(self.Pt, self.H0), t.dot(self.Pt, J)]
-        terms.append(t.dot(self.Pa, self.Ka) + t.dot(self.Pb, self.Kb) if self.kfrac != 0.0
+        terms.append(t.dot(self.Pa, self.Ka) + t.dot(self.Pb, self.Kb) if self.anyK
                      else t.zeros((), dtype=t.float64, device=self.dev))
         return terms
 
     def _exx_factor(self):
-        return 0.5 * self.kfrac  # Exx = 1/2 (tr Pa kfrac K[Pa] + tr Pb kfrac K[Pb])
+        return 0.5 * self.kscale  # Exx = 1/2 (tr Pa kfrac K[Pa] + tr Pb kfrac K[Pb]); a screened term: the weighted sums
 
     def _nspin(self):
         return 2

@@ -20,7 +20,7 @@ OBJDIR = os.path.join(ROOT, "helfem_amd", "build")
 
 HOST_SRCS = ["host/fem.cpp", "host/special.cpp", "host/atomic_basis.cpp", "host/diatomic_basis.cpp", "host/scf.cpp", "host/diis.cpp", "host/checkpoint.cpp", "host/dftfuncs.cpp", "host/tuning.cpp"]
 HIP_SRCS = ["hip/tables.cpp", "hip/capi.cpp", "hip/fock.hip", "hip/exchange.hip", "hip/exchange_lr.hip", "hip/gemm.hip", "hip/eig.hip", "hip/dc.hip", "hip/stsel.hip", "hip/trd.hip", "hip/trdp.hip",
-            "hip/misc.hip", "hip/scf_gpu.cpp", "hip/scf_device.hip", "hip/diis_dev.hip", "hip/cuhf_dev.hip", "hip/tei_dev.hip", "hip/rs_tei_dev.hip"]
+            "hip/misc.hip", "hip/scf_gpu.cpp", "hip/scf_device.hip", "hip/diis_dev.hip", "hip/cuhf_dev.hip", "hip/tei_dev.hip", "hip/rs_tei_dev.hip", "hip/exchange_mix.hip"]
 
 
 # Kernel arguments preloaded into SGPRs at wave launch (gfx940+): every launch of the eigensolver's dependent chains
@@ -108,8 +108,9 @@ def build_adapter_test(verbose=True):
     """tests/cpp/adapter_test, eigsel_adapter_test and coulomb_batch_adapter_test: call the hot path through
     include/helfem_gpu_arma.hpp (built next to the library; the GPU box runs them from tests/test_gpu_adapter.py,
     tests/test_gpu_eigsel_adapter.py and tests/test_gpu_coulomb_batch.py); rohf_adapter_check: scf::ROHF_update
-    (tests/test_rohf_cpu.py compile-only, tests/test_gpu_rohf_run.py on the device)"""
-    for name in ("adapter_test", "eigsel_adapter_test", "coulomb_batch_adapter_test", "rohf_adapter_check"):
+    (tests/test_rohf_cpu.py compile-only, tests/test_gpu_rohf_run.py on the device); mix_exchange_adapter_check:
+    atomic::TwoDBasis::mix_exchange (tests/test_exchange_mix_cpu.py compile-only, tests/test_gpu_exchange_mix.py on the device)"""
+    for name in ("adapter_test", "eigsel_adapter_test", "coulomb_batch_adapter_test", "rohf_adapter_check", "mix_exchange_adapter_check"):
         _build_adapter_program(name, verbose)
 
 

@@ -288,6 +288,7 @@ int hfg_angular_basis(int lmax, int mmax, int *lval, int *mval, int *nang) {
 int hfg_basis_destroy(hfg_basis *b) {
   HFG_TRY
   if (!b) return 0;
+  delete b->dev_mix;
   delete b->dev;
   delete b->dev_rs;
   delete b;
@@ -350,6 +351,7 @@ int hfg_compute_rs_tei(hfg_basis *b, int rs_kind, double omega) {
   else if (rs_kind == 2) b->ab.compute_erfc(omega);
   else throw std::logic_error("unknown range-separation kernel (1 = Yukawa, 2 = erfc)\n");
   b->rs_on_device = false;
+  drop_mix_tables(b);  // mixed from the tables this call has replaced
   HFG_CATCH
 }
 
@@ -406,6 +408,20 @@ int hfg_basis_get_prim(hfg_ctx *ctx, const hfg_basis *b, int which, int ilm, int
     // atomic basis: which 0 = prim_tei[L] (TwoDBasis.cpp:666-739), 8 = disjoint_L, 10 = disjoint_m1L; ilm = L
     const helfem::atomic::TwoDBasis &B = b->ab;
     const size_t E = B.Nel(), NL = (size_t)B.N_L();
+    if (which == 16) {
+      // one block of the mixed-kernel set (hfg_mix_exchange_tables), element pair iel = e * Nel + f, read back from the device
+      // in its PADDED p^2 x p^2 form (rows: primitives of e, columns: primitives of f; hip/tables.h), so that the padding shows
+      if (!ctx) throw std::logic_error("hfg_basis_get_prim: the tables live on the device, a context is needed\n");
+      const hfg_dev_tables *t = exchange_tables(const_cast<hfg_basis *>(b), ExTables::mix);
+      if (ilm < 0 || ilm >= t->Ntab || iel < 0 || iel >= t->E * t->E) throw std::logic_error("hfg_basis_get_prim: index out of range\n");
+      const size_t blk = (size_t)t->p * t->p * t->p * t->p;
+      *rows = *cols = (int64_t)t->p * t->p;
+      if (!out) return 0;
+      HFG_HIP_CHECK(hipSetDevice(ctx->device));
+      HFG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      HFG_HIP_CHECK(hipMemcpy(out, t->tei.p + ((size_t)ilm * t->E * t->E + iel) * blk, sizeof(double) * blk, hipMemcpyDeviceToHost));
+      return 0;
+    }
     if (which != 4 && !(which >= 12 && which <= 15) && ((which != 0 && which != 8 && which != 10) || ilm < 0 || (size_t)ilm >= NL || iel < 0 || (size_t)iel >= E))
       throw std::logic_error("hfg_basis_get_prim: index out of range\n");
     if (which >= 12 && which <= 15 && b->rs_on_device) {
@@ -731,11 +747,48 @@ int hfg_exchange_dev(hfg_ctx *ctx, hfg_basis *b, const double *dP, double *dK) {
 int hfg_exchange_occ_dev(hfg_ctx *ctx, hfg_basis *b, const double *dP, const double *dC, int64_t nocc, double *dK) {
   HFG_TRY
   if (nocc < 1 || !dC) throw std::logic_error("hfg_exchange_occ_dev: occupied orbitals missing\n");
-  exchange_dev(ctx, b, dP, dK, false, dC, (int)nocc);
+  exchange_dev(ctx, b, dP, dK, ExTables::coulomb, dC, (int)nocc);
   HFG_CATCH
 }
 int hfg_rs_exchange_dev(hfg_ctx *ctx, hfg_basis *b, const double *dP, double *dK) {
-  HFG_TRY exchange_dev(ctx, b, dP, dK, true);
+  HFG_TRY exchange_dev(ctx, b, dP, dK, ExTables::screened);
+  HFG_CATCH
+}
+// alpha K[1/r12] + beta K[screened kernel] of the range-separated hybrids from the mixed-kernel table set (hip/exchange_mix.hip)
+int hfg_mix_exchange_tables(hfg_ctx *ctx, hfg_basis *b, double alpha, double beta) {
+  HFG_TRY return mix_exchange_tables_dev(ctx, b, alpha, beta);
+  HFG_CATCH
+}
+static void mix_args(const char *who, hfg_ctx *ctx, hfg_basis *b, const void *in, const void *out) {
+  if (!ctx || !b) throw std::logic_error(std::string(who) + ": null context or basis\n");
+  if (b->kind == 0) throw std::logic_error("Range separated functionals are not supported.\n");
+  if (!in || !out) throw std::logic_error(std::string(who) + ": null matrix pointer\n");
+}
+int hfg_mix_exchange_devptr(hfg_ctx *ctx, hfg_basis *b, const double *dP, double *dK) {
+  HFG_TRY
+  mix_args("hfg_mix_exchange_devptr", ctx, b, dP, dK);
+  exchange_dev(ctx, b, dP, dK, ExTables::mix);
+  HFG_CATCH
+}
+int hfg_mix_exchange_occ_devptr(hfg_ctx *ctx, hfg_basis *b, const double *dP, const double *dC, int64_t nocc, double *dK) {
+  HFG_TRY
+  mix_args("hfg_mix_exchange_occ_devptr", ctx, b, dP, dK);
+  if (nocc < 1 || !dC) throw std::logic_error("hfg_mix_exchange_occ_devptr: occupied orbitals missing\n");
+  exchange_dev(ctx, b, dP, dK, ExTables::mix, dC, (int)nocc);
+  HFG_CATCH
+}
+int hfg_mix_exchange_occ_batch_devptr(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *dP, const double *dC, const int64_t *nocc,
+                                      int64_t ldc_cols, double *dK) {
+  HFG_TRY
+  if (!coulomb_batch_args("hfg_mix_exchange_occ_batch_devptr", ctx, b, nP, dP, dK)) return 0;
+  if (b->kind == 0) throw std::logic_error("Range separated functionals are not supported.\n");
+  if (dC || nocc) {  // both or neither: without them every density is factorised
+    if (!dC || !nocc) throw std::logic_error("hfg_mix_exchange_occ_batch_devptr: null pointer to the occupied orbitals or their counts\n");
+    for (int64_t i = 0; i < nP; i++)
+      if (nocc[i] < 0 || nocc[i] > ldc_cols)
+        throw std::logic_error("hfg_mix_exchange_occ_batch_devptr: a count of occupied orbitals outside 0 ... ldc_cols\n");
+  }
+  exchange_batch_dev(ctx, b, nP, dP, dK, ExTables::mix, dC, nocc, ldc_cols);
   HFG_CATCH
 }
 // the batched exchange entries: the refusals of the batched Coulomb entries
@@ -746,7 +799,7 @@ int hfg_exchange_batch_devptr(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const doub
 }
 int hfg_rs_exchange_batch_devptr(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *dP, double *dK) {
   HFG_TRY
-  if (coulomb_batch_args("hfg_rs_exchange_batch_devptr", ctx, b, nP, dP, dK)) exchange_batch_dev(ctx, b, nP, dP, dK, true);
+  if (coulomb_batch_args("hfg_rs_exchange_batch_devptr", ctx, b, nP, dP, dK)) exchange_batch_dev(ctx, b, nP, dP, dK, ExTables::screened);
   HFG_CATCH
 }
 int hfg_exchange_occ_batch_devptr(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *dP, const double *dC, const int64_t *nocc,
@@ -757,7 +810,7 @@ int hfg_exchange_occ_batch_devptr(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const 
   for (int64_t i = 0; i < nP; i++)
     if (nocc[i] < 0 || nocc[i] > ldc_cols)
       throw std::logic_error("hfg_exchange_occ_batch_devptr: a count of occupied orbitals outside 0 ... ldc_cols\n");
-  exchange_batch_dev(ctx, b, nP, dP, dK, false, dC, nocc, ldc_cols);
+  exchange_batch_dev(ctx, b, nP, dP, dK, ExTables::coulomb, dC, nocc, ldc_cols);
   HFG_CATCH
 }
 int hfg_exchange_batch_plan(int64_t nP, const int *ranks, int max_members, int *chunk_of, int *nchunks) {
@@ -926,28 +979,41 @@ int hfg_rs_exchange(hfg_ctx *ctx, hfg_basis *b, const double *P, double *K) {
   size_t N = b->Nbf();
   Stage st(ctx);
   double *dP = st.up(P, N * N), *dK = st.alloc(N * N);
-  exchange_dev(ctx, b, dP, dK, true);
+  exchange_dev(ctx, b, dP, dK, ExTables::screened);
   st.down(K, dK, N * N);
   st.sync();
   HFG_CATCH
 }
-static int exchange_batch_host(const char *who, hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *P, double *K, bool rs) {
+int hfg_mix_exchange(hfg_ctx *ctx, hfg_basis *b, const double *P, double *K) {
+  HFG_TRY
+  mix_args("hfg_mix_exchange", ctx, b, P, K);
+  exchange_tables(b, ExTables::mix);  // (refuses before anything is staged)
+  FullShard full(ctx);
+  size_t N = b->Nbf();
+  Stage st(ctx);
+  double *dP = st.up(P, N * N), *dK = st.alloc(N * N);
+  exchange_dev(ctx, b, dP, dK, ExTables::mix);
+  st.down(K, dK, N * N);
+  st.sync();
+  HFG_CATCH
+}
+static int exchange_batch_host(const char *who, hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *P, double *K, ExTables which) {
   HFG_TRY
   if (!coulomb_batch_args(who, ctx, b, nP, P, K)) return 0;
   FullShard full(ctx);
   size_t n = b->Nbf() * b->Nbf() * (size_t)nP;
   Stage st(ctx);
   double *dP = st.up(P, n), *dK = st.alloc(n);
-  exchange_batch_dev(ctx, b, nP, dP, dK, rs);
+  exchange_batch_dev(ctx, b, nP, dP, dK, which);
   st.down(K, dK, n);
   st.sync();
   HFG_CATCH
 }
 int hfg_exchange_batch(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *P, double *K) {
-  return exchange_batch_host("hfg_exchange_batch", ctx, b, nP, P, K, false);
+  return exchange_batch_host("hfg_exchange_batch", ctx, b, nP, P, K, ExTables::coulomb);
 }
 int hfg_rs_exchange_batch(hfg_ctx *ctx, hfg_basis *b, int64_t nP, const double *P, double *K) {
-  return exchange_batch_host("hfg_rs_exchange_batch", ctx, b, nP, P, K, true);
+  return exchange_batch_host("hfg_rs_exchange_batch", ctx, b, nP, P, K, ExTables::screened);
 }
 int hfg_model_potential(hfg_ctx *ctx, hfg_basis *b, const hfg_model_pot *p1, const hfg_model_pot *p2, double *H) {
   HFG_TRY

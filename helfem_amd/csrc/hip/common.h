@@ -131,6 +131,11 @@ struct hfg_basis {
   helfem::atomic::TwoDBasis ab;
   hfg_dev_tables *dev = nullptr;
   hfg_dev_tables *dev_rs = nullptr;  // range-separated exchange kernel (atomic), see tables.h
+  // alpha K[1/r12] + beta K[screened kernel] from ONE table set in the pair layout of the erfc set (hip/exchange_mix.hip);
+  // built from dev and dev_rs by hfg_mix_exchange_tables for the values below, dropped whenever either of them changes
+  hfg_dev_tables *dev_mix = nullptr;
+  double mix_alpha = 0.0, mix_beta = 0.0, mix_omega = 0.0;
+  int mix_kind = 0;
   int dev_device = -1;
   // primitive in-element integral tables built on the device (hip/tei_dev.hip) instead of host Mats
   hfg::DevBuf<double> dev_tei;

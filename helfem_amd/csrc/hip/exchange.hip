@@ -260,14 +260,25 @@ static ExAux &exaux_for(hfg_ctx *ctx, hfg_dev_tables *t) {
   return t->work.get<ExAux>(WS_EX, [&](ExAux &a) { exaux_setup(ctx, t, &a); });
 }
 
-// rs: the range-separated kernel of TwoDBasis::rs_exchange (src/atomic/TwoDBasis.cpp:1142) through basis->dev_rs
-void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, bool rs, const double *Lknown, int rknown) {
-  hfg_dev_tables *t = rs ? basis->dev_rs : basis->dev;
+hfg_dev_tables *exchange_tables(hfg_basis *basis, ExTables which) {
+  if (which == ExTables::mix) {
+    if (!basis->dev_mix || !basis->dev_mix->have_tei)
+      throw std::logic_error("The mixed exchange tables have not been built (hfg_mix_exchange_tables after hfg_basis_upload)!\n");
+    return basis->dev_mix;
+  }
+  hfg_dev_tables *t = which == ExTables::screened ? basis->dev_rs : basis->dev;
   if (!t || !t->have_tei) throw std::logic_error("Primitive teis have not been computed!\n");
+  return t;
+}
+
+// which: ExTables::screened is the range-separated kernel of TwoDBasis::rs_exchange (src/atomic/TwoDBasis.cpp:1142) through
+// basis->dev_rs, ExTables::mix the drivers' alpha K + beta K_screened through basis->dev_mix
+void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, ExTables which, const double *Lknown, int rknown) {
+  hfg_dev_tables *t = exchange_tables(basis, which);
   if (basis->dev_device != ctx->device) throw std::logic_error("basis tables live on a different device\n");
   // the screened builds of the range-separated hybrids are timed under names of their own, so that a profile shows which kernel
   // a functional ran and what the second build of an iteration costs
-  ProfScope ps(ctx, !rs ? "exchange" : (t->rs_kind == 1 ? "exchange_yukawa" : "exchange_erfc"));
+  ProfScope ps(ctx, which == ExTables::coulomb ? "exchange" : which == ExTables::mix ? "exchange_mix" : (t->rs_kind == 1 ? "exchange_yukawa" : "exchange_erfc"));
   // fast path for the low-rank densities of SCF runs (exchange_lr.hip); HELFEM_EXCHANGE=general forces the
   // general kernels below, which take any symmetric P
   if (!helfem::tuning_live().exchange_general && exchange_lowrank_dev(ctx, t, dP, dK, Lknown, rknown)) return;  // (read at every call)

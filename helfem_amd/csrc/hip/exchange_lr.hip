@@ -1118,7 +1118,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   if (N > 1024 * EXL_QMAX) return false;
   // erfc kernel (pair_tei): no factorisation over elements; the element-pair products below need an exchange-ordered
   // copy of the pair tables
-  if (t->pair_tei && (double)ntt * Ntab * E * E * p * p * p * p * sizeof(double) > 32e9) return false;
+  if (t->pair_tei && (double)ntt * Ntab * E * E * p * p * p * p * sizeof(double) > EXL_PAIR_MAX_BYTES) return false;
   if (t->pair_tei && !tuning().exl_pair) return false;
   ExLRAux &a = exlr_for(ctx, t);
   for (const ExLRAux::MRun &run : a.runs)
@@ -1730,11 +1730,10 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
 
 /// nP densities (N x N each, one after the other) -> nP exchange matrices.  dC (or null): nP sets of occupied columns,
 /// N x ldc each, the first nocc[b] of set b being the factors of P_b (hfg_exchange_occ_dev); nocc is a host array.
-void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK, bool rs, const double *dC,
+void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK, ExTables which, const double *dC,
                         const int64_t *nocc, int64_t ldc) {
   if (nP <= 0) return;
-  hfg_dev_tables *t = rs ? basis->dev_rs : basis->dev;
-  if (!t || !t->have_tei) throw std::logic_error("Primitive teis have not been computed!\n");
+  hfg_dev_tables *t = exchange_tables(basis, which);
   if (basis->dev_device != ctx->device) throw std::logic_error("basis tables live on a different device\n");
   const int N = t->N;
   const size_t N2 = (size_t)N * N;
@@ -1742,7 +1741,7 @@ void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double
   auto known = [&](int64_t b) { return hint && nocc[b] >= 0 && nocc[b] <= EXL_RMAX; };
   auto single = [&](int64_t b) {
     if (known(b) && nocc[b] == 0) HFG_HIP_CHECK(hipMemsetAsync(dK + b * N2, 0, sizeof(double) * N2, ctx->stream));
-    else exchange_dev(ctx, basis, dP + b * N2, dK + b * N2, rs, known(b) ? dC + (size_t)b * N * ldc : nullptr, known(b) ? (int)nocc[b] : 0);
+    else exchange_dev(ctx, basis, dP + b * N2, dK + b * N2, which, known(b) ? dC + (size_t)b * N * ldc : nullptr, known(b) ? (int)nocc[b] : 0);
   };
   ProfScope ps(ctx, "exchange_batch");
   bool batched = nP > 1 && !helfem::tuning_live().exchange_general;

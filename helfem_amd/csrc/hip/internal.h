@@ -65,14 +65,23 @@ void fock_finish_pol_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dFc, cons
                          double *dFa, double *dFb);  // fock.hip
 
 // exchange.hip, exchange_lr.hip
-void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, bool rs = false, const double *Lknown = nullptr,
-                  int rknown = 0);  // exchange.hip
+// the table set an exchange build reads: basis->dev (1/r12), basis->dev_rs (the screened kernel of hfg_rs_exchange) or
+// basis->dev_mix (alpha 1/r12 + beta screened, exchange_mix.hip)
+enum class ExTables { coulomb, screened, mix };
+hfg_dev_tables *exchange_tables(hfg_basis *basis, ExTables which);  // exchange.hip; throws when the set is not there
+void exchange_dev(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK, ExTables which = ExTables::coulomb,
+                  const double *Lknown = nullptr, int rknown = 0);  // exchange.hip
 bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, double *dK, const double *Lknown,
                           int rknown);  // exchange_lr.hip
 // nP densities in one pass over the exchange-ordered tables per chunk (hfg_exchange_batch_devptr); dC / nocc (host array) / ldc:
 // nP sets of occupied columns as exchange_dev's Lknown, or null
-void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK, bool rs = false,
+void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK, ExTables which = ExTables::coulomb,
                         const double *dC = nullptr, const int64_t *nocc = nullptr, int64_t ldc = 0);  // exchange_lr.hip
+
+// exchange_mix.hip
+constexpr double EXL_PAIR_MAX_BYTES = 32e9;  // largest pair table the low-rank path takes (exchange_lowrank_dev) and the mixed set builds
+// fills basis->dev_mix for (alpha, beta) from dev and dev_rs; 0: built or already there, 4: beyond EXL_PAIR_MAX_BYTES (nothing allocated)
+int mix_exchange_tables_dev(hfg_ctx *ctx, hfg_basis *basis, double alpha, double beta);  // exchange_mix.hip
 
 // tei_dev.hip
 void compute_tei_dev(hfg_ctx *ctx, hfg_basis *basis);  // tei_dev.hip

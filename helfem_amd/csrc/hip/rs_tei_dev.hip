@@ -362,6 +362,7 @@ void compute_rs_tei_dev(hfg_ctx *ctx, hfg_basis *basis, int rs_kind, double omeg
   HFG_HIP_CHECK(hipSetDevice(ctx->device));
   helfem::atomic::TwoDBasis &b = basis->ab;
   basis->rs_on_device = false;
+  drop_mix_tables(basis);  // mixed from the tables this call replaces
   if (rs_kind == 1) yukawa_dev(ctx, basis, omega);
   else erfc_dev(ctx, basis, omega);
   b.rs_kind = rs_kind;

@@ -689,12 +689,12 @@ helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::s
       // factors instead of recovering them from Ps
       auto buildK = [&](const double *Ps, const double *Cs, int nocc, double *K) {  // K = kfrac K[1/r12] + kshort K[screened kernel]
         if (opt.kfrac != 0.0) {
-          exchange_dev(ctx, hb, Ps, K, false, Cs, nocc);
+          exchange_dev(ctx, hb, Ps, K, ExTables::coulomb, Cs, nocc);
           d.axpby(0.0, K, opt.kfrac, K, NN);
         } else
           HFG_HIP_CHECK(hipMemsetAsync(K, 0, sizeof(double) * NN, s));
         if (opt.omega != 0.0) {
-          exchange_dev(ctx, hb, Ps, Krs.p, true, Cs, nocc);
+          exchange_dev(ctx, hb, Ps, Krs.p, ExTables::screened, Cs, nocc);
           d.axpby(opt.kshort, Krs.p, 1.0, K, NN);
         }
       };

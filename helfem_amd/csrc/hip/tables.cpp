@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <functional>
+#include <memory>
 #include <set>
 
 namespace hfg {
@@ -168,7 +169,7 @@ BasisView view_of(const hfg_basis *basis, bool rs = false) {
 }
 }  // namespace
 
-static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_dev_tables *t, int ldft, int mdft);
+static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_dev_tables *t, int ldft, int mdft, bool tei_later = false);
 
 static void upload_tables(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft) {
   if (!basis->have_tei()) throw std::logic_error("Primitive teis have not been computed!\n");
@@ -192,19 +193,37 @@ static void upload_rs_tables(hfg_ctx *ctx, hfg_basis *basis) {
   fill_tables(ctx, basis, b, t, 0, 0);
 }
 
+void drop_mix_tables(hfg_basis *basis) {
+  delete basis->dev_mix;
+  basis->dev_mix = nullptr;
+}
+
+hfg_dev_tables *new_mix_tables(hfg_ctx *ctx, hfg_basis *basis) {
+  BasisView b = view_of(basis);  // the Coulomb couplings and LM_fac
+  b.pair_tei = 1;
+  b.ndt = 0;
+  HFG_HIP_CHECK(hipSetDevice(ctx->device));
+  std::unique_ptr<hfg_dev_tables> t(new hfg_dev_tables());
+  fill_tables(ctx, basis, b, t.get(), 0, 0, true);
+  return t.release();
+}
+
 void upload_basis_tables(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft, bool with_rs) {
+  drop_mix_tables(basis);
   upload_tables(ctx, basis, ldft, mdft);
   delete basis->dev_rs;
   basis->dev_rs = nullptr;
   if (with_rs) upload_rs_tables(ctx, basis);
 }
 
-static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_dev_tables *t, int ldft, int mdft) {
+// tei_later: the primitive integrals are allocated and left to the caller (new_mix_tables)
+static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_dev_tables *t, int ldft, int mdft, bool tei_later) {
   hipStream_t s = ctx->stream;
   // tables already in this layout on the device: the Coulomb set of tei_dev.hip, the range-separated set of rs_tei_dev.hip
   const bool use_dev_tei = b.rs_kind ? basis->rs_on_device : basis->tei_on_device;
   const hfg::DevBuf<double> &dev_tei = b.rs_kind ? basis->dev_rs_tei : basis->dev_tei;
   t->rs_kind = b.rs_kind;
+  t->rs_omega = b.rs_kind ? basis->ab.rs_lambda : 0.0;
   t->pair_tei = b.pair_tei;
 
   const int A = t->A = b.A;
@@ -352,14 +371,14 @@ static void fill_tables(hfg_ctx *ctx, hfg_basis *basis, const BasisView &b, hfg_
     const size_t blk = pp * pp;
     const int nper = b.pair_tei ? E * E : E;  // blocks per (type, slot)
     t->tei.resize((size_t)b.ntt * Ntab * nper * blk);
-    if (use_dev_tei) {
+    if (use_dev_tei && !tei_later) {
       if (dev_tei.n < (size_t)b.ntt * Ntab * nper * blk) throw std::logic_error("device tei buffer has the wrong size");
       HFG_HIP_CHECK(hipMemcpyAsync(t->tei.p, dev_tei.p, sizeof(double) * (size_t)b.ntt * Ntab * nper * blk,
                                    hipMemcpyDeviceToDevice, s));
       HFG_HIP_CHECK(hipStreamSynchronize(s));
     }
     std::vector<double> stage(blk);
-    if (!use_dev_tei)
+    if (!use_dev_tei && !tei_later)
     for (int tt = 0; tt < b.ntt; tt++)
       for (int tab = 0; tab < Ntab; tab++)
         for (int eb = 0; eb < nper; eb++) {

@@ -39,6 +39,7 @@ struct hfg_dev_tables {
   // tei[tab][e][f][c][r] holds one p^2 x p^2 block per ELEMENT PAIR (rows: primitives of e, columns: primitives of f),
   // LMfac = 4 pi mu/(2L+1).
   int rs_kind = 0;
+  double rs_omega = 0.0;  // lambda or mu the screened slots were uploaded for (0: the Coulomb kernel)
   int pair_tei = 0;
 
   hfg::DevBuf<int> shell_l, shell_m, shell_off, shell_skip;
@@ -76,8 +77,13 @@ struct hfg_dev_tables {
 };
 
 namespace hfg {
-/// build (or rebuild) basis->dev on the context's device and drop basis->dev_rs; with_rs: rebuild dev_rs too, from the
-/// range-separated tables of compute_yukawa / compute_erfc / compute_rs_tei_dev.  The old table sets take their
-/// workspaces with them.
+/// build (or rebuild) basis->dev on the context's device and drop basis->dev_rs and basis->dev_mix; with_rs: rebuild dev_rs
+/// too, from the range-separated tables of compute_yukawa / compute_erfc / compute_rs_tei_dev.  The old table sets take
+/// their workspaces with them.
 void upload_basis_tables(hfg_ctx *ctx, hfg_basis *basis, int ldft, int mdft, bool with_rs);
+/// the mixed-kernel set (hfg_basis::dev_mix): the shells and couplings of basis->dev with LM_fac = 4 pi/(2L+1), pair_tei = 1,
+/// no disjoint tables and an UNFILLED tei[tab][e][f][c][r] that hip/exchange_mix.hip writes; the caller owns the result
+hfg_dev_tables *new_mix_tables(hfg_ctx *ctx, hfg_basis *basis);
+/// delete basis->dev_mix with its workspaces (wherever dev or dev_rs is rebuilt or dropped)
+void drop_mix_tables(hfg_basis *basis);
 }  // namespace hfg

@@ -26,6 +26,7 @@ enum class RsTei { host, dev };
   X(exl_groups, int, 4, "HELFEM_EXL_GROUPS", false, "int", std::max(1, std::min(EXL_GMAX, atoi(e))), "groups of 64 factors tried before the general kernels take over, clamped to 1 ... 16") \
   X(exl_hint, bool, true, "HELFEM_EXL_HINT", false, "off if 0", atoi(e) != 0, "the SCF loop's occupied orbitals taken as the factors of P; off: always factorise and verify P (checker)") \
   X(exl_pair, bool, true, "HELFEM_EXL_PAIR", false, "off if 0", atoi(e) != 0, "low-rank fast path for the pair (erfc) tables; off: general kernels") \
+  X(exl_mix, int, -1, "HELFEM_EXL_MIX", true, "int", atoi(e), "range-separated hybrids in the step objects: 0 = K from two builds, hfg_exchange_occ_dev and hfg_rs_exchange_dev, added on the device (checker); other non-negative = one build on the mixed-kernel table set (hfg_mix_exchange_tables); negative: by kernel kind as measured, the mixed set for both Yukawa and erfc") \
   X(fock_overlap, bool, true, "HELFEM_FOCK_OVERLAP", false, "off if 0", atoi(e) != 0, "Coulomb kernels on the side stream beside the XC kernels; off: one after the other on the main stream") \
   X(fock_skip, bool, true, "HELFEM_FOCK_SKIP", true, "off if 0", atoi(e) != 0, "Fock build skips shell pairs whose density block is zero and, after hfg_ctx_set_fock_blocks, pairs the caller does not read; off: every pair is computed (checker)") \
   X(xc_lds_limit, size_t, 150 * 1024, "HELFEM_XC_LDS_LIMIT", false, "int", (size_t)atol(e), "bytes of LDS the angular XC kernels plan with; smaller forces the chunked kernels (tests)") \

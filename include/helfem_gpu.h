@@ -376,6 +376,25 @@ int hfg_exchange_batch_devptr(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const 
 int hfg_rs_exchange_batch_devptr(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK);
 int hfg_exchange_occ_batch_devptr(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, const double *dC,
                                   const int64_t *nocc, int64_t ldc_cols, double *dK);
+/* The exact exchange of the range-separated hybrids, alpha K[1/r12] + beta K[screened kernel] (hfg_xc_exact_exchange), from
+ * ONE build on a mixed-kernel table set (DESIGN 3.3a "Mixed-kernel set"; atomic handles only, a diatomic one gets "Range
+ * separated functionals are not supported.").  hfg_mix_exchange_tables mixes the uploaded tables on the device, once: it
+ * needs hfg_basis_upload with exchange tables and, for beta != 0, an uploaded range-separated set of either kind (status 1
+ * with a text that names what is missing).  A second call with the same (alpha, beta) on unchanged tables does nothing;
+ * hfg_basis_upload, hfg_compute_rs_tei and hfg_compute_rs_tei_dev drop the set, after which the exchange entries below fail
+ * until it is rebuilt.  Status 4: the set would exceed the 32e9 bytes of the pair path, nothing was allocated and the caller
+ * builds K from the two table sets.  The exchange entries are hfg_exchange_dev, hfg_exchange_occ_dev and
+ * hfg_exchange_occ_batch_devptr (dC and nocc may both be NULL there) on that set: asynchronous on the context's stream,
+ * honouring its shard, K_b of the batch bitwise that of the single entry.  Not named *_dev, like hfg_coulomb_batch_devptr;
+ * their stream ordering is tested in tests/test_gpu_exchange_mix.py.  hfg_mix_exchange takes host pointers.
+ * hfg_basis_get_prim with which = 16 reads one block of the set back: ilm = L, iel = e * Nel + f, the padded p^2 x p^2
+ * block (rows: primitives of e, columns: primitives of f). */
+int hfg_mix_exchange_tables(hfg_ctx *ctx, hfg_basis *basis, double alpha, double beta);
+int hfg_mix_exchange(hfg_ctx *ctx, hfg_basis *basis, const double *P, double *K);
+int hfg_mix_exchange_devptr(hfg_ctx *ctx, hfg_basis *basis, const double *dP, double *dK);
+int hfg_mix_exchange_occ_devptr(hfg_ctx *ctx, hfg_basis *basis, const double *dP, const double *dC, int64_t nocc, double *dK);
+int hfg_mix_exchange_occ_batch_devptr(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, const double *dC,
+                                      const int64_t *nocc, int64_t ldc_cols, double *dK);
 /* The chunks of a batched exchange build, no device needed: ranks[b] factors of density b (0: the zero matrix, no chunk,
  * chunk_of[b] = -1; negative or above 64: routed alone), chunk_of[b] the chunk of density b, *nchunks their number.  Chunks
  * are runs of consecutive densities whose ranks sum to 64 at most, of max_members densities at most (0: the value of
@@ -594,7 +613,8 @@ int hfg_chk_read_diatomic_basis(hfg_chk *chk, int lpad, hfg_basis **basis);
 /* When enabled, every kernel family is bracketed by hipEvents on the context's stream; the
  * accumulated device time (ms) and launch count per family can be read back after a synchronize.
  * names: "coulomb", "coulomb_batch" (the batched build; "coulomb_batch_tei": its pass over the tables), "xc", "exchange" (the full-range build; "exchange_yukawa" / "exchange_erfc": the screened build of
- * hfg_rs_exchange and of the range-separated hybrids), "eig_reduce", "eig_tridiag", "eig_tridiag_solve",
+ * hfg_rs_exchange and of the range-separated hybrids; "exchange_mix": the build on the mixed-kernel set, "exchange_mix_tables":
+ * its mixing, once), "eig_reduce", "eig_tridiag", "eig_tridiag_solve",
  * "eig_backtransform", "gemm", "density", "scatter". */
 int hfg_profile_enable(hfg_ctx *ctx, int on);
 int hfg_profile_reset(hfg_ctx *ctx);

@@ -281,6 +281,22 @@ class TwoDBasis : public BasisBase<Mat> {
   Mat rs_exchange(const Mat &P) const { return this->two_body(hfg_rs_exchange, P, "rs_exchange"); }
   /// hfg_rs_exchange_batch: out[b] is bitwise rs_exchange(P[b])
   std::vector<Mat> rs_exchange(const std::vector<Mat> &P) const { return this->two_body_batch(hfg_rs_exchange_batch, P, "rs_exchange"); }
+  /// alpha exchange(P) + beta rs_exchange(P) as the drivers add them for a range-separated hybrid (src/atomic/main.cpp:763-780),
+  /// from ONE build on the mixed-kernel table set (hfg_mix_exchange_tables: mixed on the device at the first call with these
+  /// weights).  A set beyond the bound of the pair path (status 4) is not built: the sum of the two builds is returned.
+  Mat mix_exchange(const Mat &P, double alpha, double beta) const {
+    detail::need_square(P, this->N_, "mix_exchange");
+    if (!this->uploaded_) this->upload(this->lang_, this->mang_);
+    const int rc = hfg_mix_exchange_tables(this->context(), this->b_, alpha, beta);
+    if (rc == 4) {
+      Mat K = this->exchange(P);
+      const Mat Krs = rs_exchange(P);
+      for (size_t i = 0; i < this->N_ * this->N_; i++) detail::data_of(K, 0)[i] = alpha * detail::data_of(K, 0)[i] + beta * detail::data_of(Krs, 0)[i];
+      return K;
+    }
+    check(rc);
+    return this->two_body(hfg_mix_exchange, P, "mix_exchange");
+  }
 };
 }  // namespace atomic
 
