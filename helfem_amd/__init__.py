@@ -243,6 +243,28 @@ class Context(object):
         """declare the device matrix at this address constant (None withdraws): see hfg_ctx_fix_sinvh"""
         _check(lib().hfg_ctx_fix_sinvh(self.h, ctypes.c_void_p(device_ptr or 0)))
 
+    FOCK_BAND_STATES = ("none", "declared", "refused")
+
+    def declare_fock_band(self, basis, H0_ptr=None, blockid_ptr=None):
+        """declare, beside fix_sinvh, that every Fock matrix of the blocked eigensolves is local in the radial element index
+        (F = H0 + J + XC; hfg_ctx_declare_fock_band).  H0_ptr / blockid_ptr: device addresses of H0 (N x N) and of the
+        per-function block ids; an H0 with a non-zero entry outside the pattern refuses the declaration.  Returns
+        fock_band_state()."""
+        f = lib().hfg_ctx_declare_fock_band
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int_p]
+        st = ctypes.c_int()
+        _check(f(self.h, basis.h, ctypes.c_void_p(H0_ptr or 0), ctypes.c_void_p(blockid_ptr or 0), ctypes.byref(st)))
+        return self.FOCK_BAND_STATES[st.value]
+
+    def fock_band_state(self):
+        """"none", "declared" or "refused" (H0 had an entry outside the pattern): what the last declare_fock_band left;
+        fix_sinvh resets it to "none" """
+        f = lib().hfg_ctx_fock_band_state
+        f.argtypes = [ctypes.c_void_p, c_int_p]
+        st = ctypes.c_int()
+        _check(f(self.h, ctypes.byref(st)))
+        return self.FOCK_BAND_STATES[st.value]
+
     def profile(self, on=True):
         _check(lib().hfg_profile_enable(self.h, 1 if on else 0))
 
@@ -749,6 +771,25 @@ def exchange_batch_plan(ranks, max_members=0):
     n = ctypes.c_int(0)
     _check(lib().hfg_exchange_batch_plan(len(r), r.ctypes.data_as(c_int_p), int(max_members), out.ctypes.data_as(c_int_p), ctypes.byref(n)))
     return out.tolist(), n.value
+
+
+def eig_band_plan(node, pm, E):
+    """plan of the banded F X of one symmetry block (hfg_eig_band_plan, no device): node[i] = radial node of position i of
+    the block's index list, pm = nodes per element - 1, E elements.  Returns (perm, steps, banded): the positions
+    radial-major (the row order of F in the product), for every 64-row tile in that order the starts of its k steps (16
+    columns each, in the caller's column order), and whether the block takes the row tasks (False: every tile has all steps)."""
+    nd = np.ascontiguousarray(node, dtype=np.int32)
+    n = len(nd)
+    nt = (n + 63) // 64
+    cap = nt * ((n + 15) // 16)
+    perm = np.zeros(n, dtype=np.int64)
+    toff, ks = np.zeros(nt + 1, dtype=np.int32), np.zeros(max(cap, 1), dtype=np.int32)
+    banded = ctypes.c_int(0)
+    f = lib().hfg_eig_band_plan
+    f.argtypes = [ctypes.c_int64, c_int_p, ctypes.c_int, ctypes.c_int, c_i64_p, c_int_p, c_int_p, ctypes.c_int64, c_int_p]
+    _check(f(n, nd.ctypes.data_as(c_int_p), int(pm), int(E), perm.ctypes.data_as(c_i64_p), toff.ctypes.data_as(c_int_p),
+             ks.ctypes.data_as(c_int_p), cap, ctypes.byref(banded)))
+    return perm, [ks[toff[t]:toff[t + 1]].copy() for t in range(nt)], bool(banded.value)
 
 
 class DFTGrid(object):
@@ -1440,6 +1481,11 @@ class DeviceSCFStep(object):
         self.ctx.fix_sinvh(None)
         self.Sinvh = t.from_numpy(np.asfortranarray(Sinvh).ravel(order="F").copy()).to(self.dev)
         self.ctx.fix_sinvh(self.Sinvh.data_ptr())  # constant until the next set_matrices
+        # F = H0 + J + XC is local in the radial element index: the eigensolve skips the structural zeros of F in F X.  Not with
+        # exact or screened exchange in F, not under the CUHF constraint; an H0 with an entry outside the pattern refuses it
+        # (ctx.fock_band_state() tells)
+        if not self.anyK and not self._applies_cuhf:
+            self.ctx.declare_fock_band(self.basis, self.H0.data_ptr(), self.blockid.data_ptr())
 
     def set_density(self, P, C=None):
         """total density P = 2 C_occ C_occ^T; C (N x >= nocc, optional): the orbitals it was formed from, which the exact

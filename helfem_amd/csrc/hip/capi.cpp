@@ -5,6 +5,7 @@
 #include "../host/diis.h"
 #include "../host/dftfuncs.h"
 #include "../host/exchange_batch_plan.h"
+#include "../host/eig_band_plan.h"
 #include "../host/fock_need.h"
 #include <cstring>
 #include <memory>
@@ -198,6 +199,53 @@ int hfg_ctx_synchronize(hfg_ctx *c) {
 int hfg_ctx_fix_sinvh(hfg_ctx *c, const double *dSinvh) {
   HFG_TRY
   c->fix_sinvh(dSinvh);
+  HFG_CATCH
+}
+
+int hfg_ctx_declare_band(hfg_ctx *c, int64_t N, const int *node, int pm, int E, const double *dH0, const int *dBlockId, int *state) {
+  HFG_TRY
+  if (!c) throw std::logic_error("hfg_ctx_declare_band: null context\n");
+  const int st = eig_declare_band(c, (int)N, node, pm, E, dH0, dBlockId);
+  if (state) *state = st;
+  HFG_CATCH
+}
+
+int hfg_ctx_declare_fock_band(hfg_ctx *c, hfg_basis *b, const double *dH0, const int *dBlockId, int *state) {
+  HFG_TRY
+  if (!c || !b) throw std::logic_error("hfg_ctx_declare_fock_band: null context or basis\n");
+  const hfg_dev_tables *t = b->dev;
+  if (!t) throw std::logic_error("hfg_ctx_declare_fock_band: the basis tables are not uploaded\n");
+  // the pure basis of fock_finish_dev: shell-major, the first radial function of a shell left out where the tables say so
+  std::vector<int> node;
+  node.reserve(t->N);
+  for (int s = 0; s < t->A; s++)
+    for (int n = (t->h_shell_skip[s] ? 1 : 0); n < t->R; n++) node.push_back(n);
+  if ((int)node.size() != t->N) throw std::logic_error("hfg_ctx_declare_fock_band: basis tables and basis size disagree\n");
+  const int st = eig_declare_band(c, t->N, node.data(), t->p - 1, t->E, dH0, dBlockId);
+  if (state) *state = st;
+  HFG_CATCH
+}
+
+int hfg_ctx_fock_band_state(hfg_ctx *c, int *state) {
+  HFG_TRY
+  if (!c || !state) throw std::logic_error("hfg_ctx_fock_band_state: null pointer\n");
+  *state = c->band_state;
+  HFG_CATCH
+}
+
+int hfg_eig_band_plan(int64_t n, const int *node, int pm, int E, int64_t *perm, int *toff, int *kstart, int64_t cap, int *banded) {
+  HFG_TRY
+  if (n < 1 || pm < 1 || E < 1) throw std::logic_error("hfg_eig_band_plan: empty block or basis\n");
+  if (!node || !perm || !toff || !kstart) throw std::logic_error("hfg_eig_band_plan: null pointer\n");
+  for (int64_t i = 0; i < n; i++)
+    if (node[i] < 0 || node[i] > pm * E) throw std::logic_error("hfg_eig_band_plan: radial node outside the elements\n");
+  helfem::eig_band_order(n, node, perm);
+  std::vector<int> ks, to;
+  const bool b = helfem::eig_band_plan(n, node, perm, pm, E, ks, to);
+  if ((int64_t)ks.size() > cap) throw std::logic_error("hfg_eig_band_plan: output capacity too small\n");
+  std::copy(to.begin(), to.end(), toff);
+  std::copy(ks.begin(), ks.end(), kstart);
+  if (banded) *banded = b ? 1 : 0;
   HFG_CATCH
 }
 

@@ -102,7 +102,16 @@ struct hfg_ctx {
   void fix_sinvh(const double *p) {
     fixed_sinvh = p;
     fixed_gen++;
+    band_node.clear();  // the declared pattern goes with the matrix it was declared beside
+    band_state = 0;
   }
+  // hfg_ctx_declare_fock_band: the caller's promise that every Fock matrix of the blocked eigensolves under the current
+  // hfg_ctx_fix_sinvh is local in the radial element index (F = H0 + J + XC): band_node[i] is the radial node of basis
+  // function i, band_pm = p - 1 nodes per element, band_E elements.  Dropped by the next hfg_ctx_fix_sinvh.
+  // band_state: 0 no declaration, 1 declared, 2 refused (the H0 handed in has a non-zero entry outside the pattern).
+  std::vector<int> band_node;
+  int band_pm = 0, band_E = 0;
+  int band_state = 0;
   // hfg_ctx_set_fock_blocks: the shell pairs need[x*A+y] and m-group pairs gneed[ga*G+gb] of the compact Fock matrix that
   // the caller reads, for the table set they were derived from (null: none set, everything is built)
   hfg::DevBuf<int> fock_need, fock_gneed;
@@ -178,8 +187,13 @@ struct GemmTask {
   // row map (k_dgemm_tasklist_scatter, GemmHow::scatter, only; beta == 0): element (i, j) of the product is stored at
   // C[rmap[i], cmap[j]].  The last product of the blocked eigensolve (eig.hip) writes into the N x N eigenvector matrix through them.
   const int64_t *rmap = nullptr;
+  // k-step list (k_dgemm_tasklist_klist, GemmHow::klist, only; with rmap and cmap): the k loop takes the nk steps of 16 columns
+  // that start at kstart[0] < kstart[1] < ... (multiples of 4, at least 16 apart, below K); all other columns of A are zero
+  const int *kstart = nullptr;
+  int nk = 0;
+  int kpad = 0;  // (fills the struct)
 };
-static_assert(sizeof(GemmTask) == 104, "GemmTask is compared bytewise: keep it free of padding");
+static_assert(sizeof(GemmTask) == 120, "GemmTask is compared bytewise: keep it free of padding");
 
 struct ProfScope {
   hfg_ctx *c;

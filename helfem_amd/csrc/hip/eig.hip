@@ -18,6 +18,7 @@
 #include "internal.h"
 #include "wave.h"
 #include "../host/eigsel_count.h"
+#include "../host/eig_band_plan.h"
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -61,6 +62,15 @@ __global__ void k_gather_f(const double *__restrict__ F, int N, const int64_t *_
   int j = blockIdx.y;
   if (i >= n) return;
   Fb[(size_t)j * n + i] = F[(size_t)rows[j] * N + rows[i]];
+}
+
+// F(irows, jrows): the rows of the block in another order than its columns (the banded F X: rows radial-major)
+__global__ void k_gather_f2(const double *__restrict__ F, int N, const int64_t *__restrict__ irows, const int64_t *__restrict__ jrows,
+                            int n, double *__restrict__ Fb) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int j = blockIdx.y;
+  if (i >= n) return;
+  Fb[(size_t)j * n + i] = F[(size_t)jrows[j] * N + irows[i]];
 }
 
 // column support of Sinvh on the block rows (scf_helpers.cpp:150-157): flag[c] = any(Sinvh(rows,c) != 0)
@@ -671,6 +681,18 @@ struct EigWork : Workspace {
   // are valid (so only under hfg_ctx_fix_sinvh); xc_have[ib]: block ib has been gathered.  Cleared with the lists.
   DevBuf<double> Xc;
   std::vector<char> xc_have;
+  // the declared radial-element pattern of F (hfg_ctx_declare_fock_band) as applied to the lists above (eig_band_plan.h),
+  // derived with them.  band_rows: the caller's index list with every block ordered radial-major (empty: no declaration in
+  // force) -- the ROWS of the gathered F under the pattern; its columns, X and everything downstream keep the caller's order.
+  // band_pos[blk_ptr[ib] + i]: position in block ib of its radial-major row i (where row i of F X is stored).  band_ks: the k
+  // steps of all row tiles, tile t of block ib at band_ks[band_koff[band_toff[ib] + t] ...).
+  std::vector<int64_t> band_rows, band_pos;
+  std::vector<int> band_ks, band_koff, band_toff;
+  bool band_any = false;  // some block takes the row tasks
+  DevBuf<long long> band_rows_dev, band_pos_dev;
+  DevBuf<int> band_ks_dev, band_iota_dev;
+  DevBuf<GemmTask> fxtasks;
+  std::vector<GemmTask> h_fxtasks;
   // one-call entries: the divide-and-conquer status word is copied home behind that stage and waited for through the event,
   // so that the host returns while the last product is still running
   int *h_status = nullptr;
@@ -1285,13 +1307,55 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
     if (blk_ptr[ib + 1] == blk_ptr[ib]) throw std::logic_error("eig_gsym_sub: empty symmetry block\n");
   // column support of every block (scf_helpers.cpp:150-157).  It depends on Sinvh and the blocks only: when the caller
   // has declared Sinvh fixed (hfg_ctx_fix_sinvh) the lists of the previous call are still on the device
+  // the declared pattern of F: valid beside the declared Sinvh only, ignored under HELFEM_EIG_BAND=0 (read at every call)
+  const bool want_band = ctx->fixed_sinvh && ctx->fixed_sinvh == dS && ctx->band_state == 1 && ctx->band_node.size() == (size_t)N &&
+                         helfem::tuning_live().eig_band;
   const bool cached = ctx->fixed_sinvh && ctx->fixed_sinvh == dS && w.sup_S == dS && w.sup_gen == ctx->fixed_gen &&
-                      w.sup_N == N &&
+                      w.sup_N == N && want_band == !w.band_rows.empty() &&
                       w.sup_ptr.size() == (size_t)nblk + 1 && std::equal(w.sup_ptr.begin(), w.sup_ptr.end(), blk_ptr) &&
                       w.sup_idx.size() == (size_t)N && std::equal(w.sup_idx.begin(), w.sup_idx.end(), blk_idx);
   if (!cached) {
     w.sup_S = nullptr;
     w.xc_have.clear();  // the gathered X blocks belong to the lists that go
+    HFG_HIP_CHECK(hipStreamSynchronize(s));  // the band lists may still be the source of an earlier copy
+    w.band_rows.clear();
+    w.band_pos.clear();
+    w.band_ks.clear();
+    w.band_koff.assign(1, 0);
+    w.band_toff.assign(1, 0);
+    w.band_any = false;
+    if (want_band) {
+      w.band_rows.resize(N);
+      w.band_pos.resize(N);
+      std::vector<int> nd, ks, toff;
+      int64_t nbig = 0;
+      for (int ib = 0; ib < nblk; ib++) {
+        const int64_t o = blk_ptr[ib], n = blk_ptr[ib + 1] - o;
+        nbig = std::max(nbig, n);
+        nd.resize(n);
+        for (int64_t i = 0; i < n; i++) {
+          if (blk_idx[o + i] < 0 || blk_idx[o + i] >= N) throw std::logic_error("eig_gsym_sub: block index out of range\n");
+          nd[i] = ctx->band_node[blk_idx[o + i]];
+        }
+        helfem::eig_band_order(n, nd.data(), w.band_pos.data() + o);
+        for (int64_t i = 0; i < n; i++) w.band_rows[o + i] = blk_idx[o + w.band_pos[o + i]];
+        if (helfem::eig_band_plan(n, nd.data(), w.band_pos.data() + o, ctx->band_pm, ctx->band_E, ks, toff)) w.band_any = true;
+        for (size_t t = 0; t + 1 < toff.size(); t++) w.band_koff.push_back((int)w.band_ks.size() + toff[t + 1]);
+        w.band_ks.insert(w.band_ks.end(), ks.begin(), ks.end());
+        w.band_toff.push_back((int)w.band_koff.size() - 1);
+      }
+      std::vector<int> iota(nbig);
+      for (int64_t i = 0; i < nbig; i++) iota[i] = (int)i;
+      w.band_rows_dev.resize(N);
+      w.band_pos_dev.resize(N);
+      w.band_ks_dev.resize(w.band_ks.size() + 1);
+      w.band_iota_dev.resize(nbig);
+      HFG_HIP_CHECK(hipMemcpyAsync(w.band_rows_dev.p, w.band_rows.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
+      HFG_HIP_CHECK(hipMemcpyAsync(w.band_pos_dev.p, w.band_pos.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
+      HFG_HIP_CHECK(hipMemcpyAsync(w.band_ks_dev.p, w.band_ks.data(), sizeof(int) * w.band_ks.size(), hipMemcpyHostToDevice, s));
+      HFG_HIP_CHECK(hipMemcpyAsync(w.band_iota_dev.p, iota.data(), sizeof(int) * nbig, hipMemcpyHostToDevice, s));
+      HFG_HIP_CHECK(hipStreamSynchronize(s));  // iota lives on this stack frame
+    }
     HFG_HIP_CHECK(hipMemcpyAsync(drows, blk_idx, sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
     DevBuf<int> &flag = w.ibuf2;
     flag.resize((size_t)N * nblk + 8);
@@ -1422,19 +1486,33 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
       gt[3 * nb + k] = g;
     }
     upload_cached(w.gtasks, w.h_gtasks, gt, s);
-    {
-      ProfScope ps(ctx, "eig_reduce");
+    // F X under the declared pattern: one task per 64 rows of F in radial-major ROW order (the gather below), its k loop
+    // over the tile's step list alone, the rows stored at their places in the caller's order (rmap).  Columns of F, X and T
+    // are in the caller's order, so T is bit for bit the dense product.  Once one block of the batch takes row tasks every
+    // block does (a dense one with all steps), and the grid stays that of a 64-row product.  Longest lists first: the launch
+    // hands out the tasks in order, the short ones fill the tail.
+    std::vector<GemmTask> fx;
+    if (w.band_any && !w.band_rows.empty()) {
       for (int k = 0; k < nb; k++) {
         const int ib = mine[c0 + k] % nblk;
-        const double *dF = dFs[mine[c0 + k] / nblk];
-        int n = ns[k];
-        if (keep_x && w.xc_have[ib])
-          hipLaunchKernelGGL(k_gather_f, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, N, drows + blk_ptr[ib], n, Fb.p + (size_t)k * nmax * nmax);
-        else
-          hipLaunchKernelGGL(k_gather_block, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, dS, N, drows + blk_ptr[ib],
-                             dcols + blk_ptr[ib], n, Fb.p + (size_t)k * nmax * nmax, const_cast<double *>(Xptr[k]));
-        if (keep_x) w.xc_have[ib] = 1;
+        const int n = ns[k], nt = w.band_toff[ib + 1] - w.band_toff[ib];
+        for (int t = 0; t < nt; t++) {
+          const int i0 = t * helfem::EIG_BAND_TILE, q = w.band_toff[ib] + t;
+          GemmTask g = gt[k];
+          g.A = gt[k].A + i0;
+          g.M = std::min(helfem::EIG_BAND_TILE, n - i0);
+          g.rmap = (const int64_t *)w.band_pos_dev.p + blk_ptr[ib] + i0;
+          g.cmap = w.band_iota_dev.p;
+          g.kstart = w.band_ks_dev.p + w.band_koff[q];
+          g.nk = w.band_koff[q + 1] - w.band_koff[q];
+          fx.push_back(g);
+        }
       }
+      std::stable_sort(fx.begin(), fx.end(), [](const GemmTask &a, const GemmTask &b) { return a.nk > b.nk; });
+      upload_cached(w.fxtasks, w.h_fxtasks, fx, s);
+    }
+    {
+      ProfScope ps(ctx, "eig_reduce");
       // two workgroups per tile (split K) when the batch's tiles would not fill the chip evenly: more than half, fewer
       // than all of the 2 x CU slots; HELFEM_GEMM_SPLITK = 0 / 1 forces it off / on
       const int force_split = tuning().gemm_splitk;
@@ -1443,6 +1521,24 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
         const long t1 = (ns[k] + 127) / 128;
         full_tiles += t1 * t1;
         low_tiles += t1 * (t1 + 1) / 2;
+      }
+      // the row tasks of the banded F X are 64 x 64 work with the 16x16x4 instruction: forced large tiles, split K or
+      // HELFEM_MFMA keep the dense tasks
+      const bool band_fx = !fx.empty() && force_split < 0 && !gemm_prefers_128(ctx, full_tiles) && !tuning().mfma_4x4x4;
+      for (int k = 0; k < nb; k++) {
+        const int ib = mine[c0 + k] % nblk;
+        const double *dF = dFs[mine[c0 + k] / nblk];
+        int n = ns[k];
+        double *Fk = Fb.p + (size_t)k * nmax * nmax;
+        if (!(keep_x && w.xc_have[ib]))
+          hipLaunchKernelGGL(k_gather_block, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, dS, N, drows + blk_ptr[ib],
+                             dcols + blk_ptr[ib], n, Fk, const_cast<double *>(Xptr[k]));
+        else if (!band_fx)
+          hipLaunchKernelGGL(k_gather_f, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, N, drows + blk_ptr[ib], n, Fk);
+        if (band_fx)  // the rows of F radial-major, its columns in the caller's order
+          hipLaunchKernelGGL(k_gather_f2, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, N, (const int64_t *)w.band_rows_dev.p + blk_ptr[ib],
+                             drows + blk_ptr[ib], n, Fk);
+        if (keep_x) w.xc_have[ib] = 1;
       }
       const int slots = 2 * eig_num_cus(ctx);
       const bool split_full = force_split >= 0 ? force_split != 0 : (full_tiles < slots && nm >= 256);
@@ -1462,7 +1558,13 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
       w.full_how = full;
       if (full.split2)
         for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(T1.p + (size_t)k * nmax * nmax, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
-      gemm_tasklist_dev(ctx, w.gtasks.p, nb, nm, nm, full);
+      if (band_fx) {
+        GemmHow how;
+        how.tile = GemmTile::T64;
+        how.scatter = how.klist = true;
+        gemm_tasklist_dev(ctx, w.fxtasks.p, (int)fx.size(), helfem::EIG_BAND_TILE, nm, how);
+      } else
+        gemm_tasklist_dev(ctx, w.gtasks.p, nb, nm, nm, full);
       if (low.split2)
         for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(w.A[k].p, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
       gemm_tasklist_dev(ctx, w.gtasks.p + nb, nb, nm, nm, low);
@@ -1664,6 +1766,52 @@ void eig_block_supports(hfg_ctx *ctx, int N, const double *dS, int nblk, const i
     if (cnt != (int)(blk_ptr[ib + 1] - blk_ptr[ib]))
       throw std::logic_error("eig_gsym_sub: Sinvh is not block structured (columns with support != block size)\n");
   }
+}
+
+// flag = 1 when H (N x N) has a non-zero entry, inside a symmetry block (blockid null: anywhere), whose two radial
+// functions share no element
+__global__ void k_band_outside(const double *__restrict__ H, int N, const int *__restrict__ node, const int *__restrict__ blockid,
+                               int pm, int E, int *__restrict__ flag) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
+  int bad = 0;
+  if (row < N && (!blockid || blockid[row] == blockid[col]) && !helfem::eig_band_share(node[row], node[col], pm, E))
+    bad = H[(size_t)col * N + row] != 0.0;  // (a NaN counts)
+  bad = __syncthreads_or(bad);
+  if (bad && threadIdx.x == 0) atomicOr(flag, 1);
+}
+
+/// hfg_ctx_declare_fock_band: node (N values, host) = radial node of every basis function, pm = p - 1, E elements; dH0
+/// (device, N x N, may be null) is checked against the pattern inside the blocks of dBlockId (device, N ids, may be null)
+/// by one reduction.  Returns the context's band_state: 1 declared, 2 refused.  Needs hfg_ctx_fix_sinvh first.
+int eig_declare_band(hfg_ctx *ctx, int N, const int *node, int pm, int E, const double *dH0, const int *dBlockId) {
+  if (!ctx->fixed_sinvh) throw std::logic_error("hfg_ctx_declare_fock_band: no Sinvh is declared fixed (hfg_ctx_fix_sinvh)\n");
+  if (N < 1 || pm < 1 || E < 1 || !node) throw std::logic_error("hfg_ctx_declare_fock_band: invalid pattern\n");
+  for (int i = 0; i < N; i++)
+    if (node[i] < 0 || node[i] > pm * E) throw std::logic_error("hfg_ctx_declare_fock_band: radial node outside the elements\n");
+  ctx->band_node.clear();
+  ctx->band_state = 0;
+  EigWork &w = work_for(ctx);
+  w.sup_S = nullptr;  // lists and plans derived under an earlier declaration go
+  if (dH0) {
+    hipStream_t s = ctx->stream;
+    DevBuf<int> &buf = w.ibuf2;
+    buf.resize((size_t)N + 8);
+    int flag = 0;
+    HFG_HIP_CHECK(hipMemcpyAsync(buf.p + 1, node, sizeof(int) * N, hipMemcpyHostToDevice, s));
+    HFG_HIP_CHECK(hipMemsetAsync(buf.p, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_band_outside, dim3((N + 255) / 256, N), dim3(256), 0, s, dH0, N, buf.p + 1, dBlockId, pm, E, buf.p);
+    HFG_HIP_CHECK(hipMemcpyAsync(&flag, buf.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HFG_HIP_CHECK(hipStreamSynchronize(s));
+    if (flag) {
+      ctx->band_state = 2;
+      return 2;
+    }
+  }
+  ctx->band_node.assign(node, node + N);
+  ctx->band_pm = pm;
+  ctx->band_E = E;
+  ctx->band_state = 1;
+  return 1;
 }
 
 // scf::eig_gsym_sub for the two spin matrices of an unrestricted iteration in one batch (diatomic/main.cpp:936-958 calls

@@ -50,13 +50,18 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 // stored at C[:, cmap[j]]
 // RMAP: row and column maps of the stored product (GemmTask::rmap, cmap; any op(A), op(B)): element (i, j) goes to
 // C[rmap[i], cmap[j]]; the operands are read as without maps
-template <int BM, int BN, bool ACC = false, int MF = 1, bool MAP = false, bool RMAP = false>
+// KLIST: the k loop runs over the nk steps of 16 columns that start at kstart[0] < kstart[1] < ... (GemmTask::kstart; multiples
+// of 4, at least 16 apart) instead of over all of K: every other column of op(A) is known to be zero.  A start that is a
+// multiple of 4 keeps every column in the group of four that one MFMA takes in the full loop, and a skipped group would
+// add exact zeros there, so the product is bit for bit that of the full loop (finite operands).
+template <int BM, int BN, bool ACC = false, int MF = 1, bool MAP = false, bool RMAP = false, bool KLIST = false>
 __device__ __forceinline__ void dgemm_tile(int id, int transA, int transB, int M, int N, int K, double alpha,
                                            const double *__restrict__ A, int lda, const double *__restrict__ B, int ldb,
                                            double beta, double *__restrict__ C, int ldc, double (*As)[16][BM + 16],
                                            double (*Bs)[16][BN + 16], int sym = 0, int kbeg = 0, int kend = -1, int over = 0,
                                            const int *__restrict__ amap = nullptr, const int *__restrict__ cmap = nullptr,
-                                           const int64_t *__restrict__ rmap = nullptr) {
+                                           const int64_t *__restrict__ rmap = nullptr, const int *__restrict__ kstart = nullptr,
+                                           int nk = 0) {
   constexpr int BK = 16;
   constexpr int PAD = 16;
   constexpr int WM = BM / 2, WN = BN / 2;  // wave tile
@@ -259,6 +264,34 @@ __device__ __forceinline__ void dgemm_tile(int id, int transA, int transB, int M
   // caller) with FP64 atomics; with two halves per tile the sum has two addends, so its value does not depend on their order
   const bool splitk = kend >= 0;
   const int kstop = splitk ? min(kend, K) : K;
+  if constexpr (KLIST) {
+    static_assert(MF == 1 && !ACC && !MAP, "the k-step list goes with the plain 16x16x4 tile");
+    if (nk > 0) {
+      load_tiles(kstart[0]);
+      store_tiles(0);
+    }
+    __syncthreads();
+    int kbuf = 0;
+    for (int st = 0; st < nk; st++) {
+      const bool more = (st + 1 < nk);
+      if (more) load_tiles(kstart[st + 1]);
+#pragma unroll
+      for (int kk = 0; kk < BK; kk += 4) {
+        double fa[TM], fb[TN];
+#pragma unroll
+        for (int i = 0; i < TM; i++) fa[i] = As[kbuf][kk + l4][wm + i * 16 + l15];
+#pragma unroll
+        for (int j = 0; j < TN; j++) fb[j] = Bs[kbuf][kk + l4][wn + j * 16 + l15];
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+          for (int j = 0; j < TN; j++) accv[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[i], accv[i][j], 0, 0, 0);
+      }
+      if (more) store_tiles(kbuf ^ 1);
+      __syncthreads();
+      kbuf ^= 1;
+    }
+  } else {
   load_tiles(kbeg);
   store_tiles(0);
   __syncthreads();
@@ -298,6 +331,7 @@ __device__ __forceinline__ void dgemm_tile(int id, int transA, int transB, int M
     if (more) store_tiles(buf ^ 1);
     __syncthreads();  // one barrier per step: buffer buf has been read by every wave, buffer buf ^ 1 is complete
     buf ^= 1;
+  }
   }
   // acc[i][j][r] = C[bm+wm+16i+l15][bn+wn+16j+l4+4r]
   if constexpr (PRE) {
@@ -410,6 +444,19 @@ __global__ __launch_bounds__(256, 2) void k_dgemm_tasklist_scatter(const GemmTas
   if ((int)blockIdx.x >= nt) return;
   dgemm_tile<BM, BN, false, MF, false, true>(blockIdx.x, t.tA, t.tB, t.M, t.N, t.K, t.alpha, t.A, t.lda, t.B, t.ldb, 0.0, t.C, t.ldc,
                                              As, Bs, 0, 0, -1, t.over, nullptr, t.cmap, t.rmap);
+}
+
+// k_dgemm_tasklist_scatter<64, 64> with the k loop over the tasks' step lists (GemmTask::kstart, nk): the row tasks of the
+// banded F X (eig.hip).  No transposes, beta == 0; every active task has rmap, cmap and kstart set.
+__global__ __launch_bounds__(256, 2) void k_dgemm_tasklist_klist(const GemmTask *__restrict__ tasks) {
+  __shared__ __attribute__((aligned(16))) double As[2][16][64 + 16];
+  __shared__ __attribute__((aligned(16))) double Bs[2][16][64 + 16];
+  const GemmTask t = tasks[blockIdx.y];
+  if (t.M <= 0 || t.N <= 0) return;
+  const int nt = ((t.M + 63) / 64) * ((t.N + 63) / 64);
+  if ((int)blockIdx.x >= nt) return;
+  dgemm_tile<64, 64, false, 1, false, true, true>(blockIdx.x, 0, 0, t.M, t.N, t.K, t.alpha, t.A, t.lda, t.B, t.ldb, 0.0, t.C, t.ldc, As, Bs,
+                                                  0, 0, -1, t.over, nullptr, t.cmap, t.rmap, t.kstart, t.nk);
 }
 
 // Task lists with an explicit workgroup list (task, tile), dealt out so that each XCD takes ONE contiguous eighth of the
@@ -535,11 +582,11 @@ const char *tile_name(GemmTile tile) {
 
 // the kernel of a task list: every legal combination maps to one instantiation, anything else is refused
 typedef void (*TaskKernel)(const GemmTask *);
-constexpr int ACC = 1, SPLIT2 = 2, MAP = 4, SCATTER = 8;
-constexpr int variant(GemmTile tile, int flags) { return 16 * (int)tile + flags; }
+constexpr int ACC = 1, SPLIT2 = 2, MAP = 4, SCATTER = 8, KLIST = 16;
+constexpr int variant(GemmTile tile, int flags) { return 32 * (int)tile + flags; }
 TaskKernel tasklist_kernel(GemmTile tile, const GemmHow &how) {
   const bool m4 = mfma4();
-  switch (variant(tile, how.acc * ACC + how.split2 * SPLIT2 + how.map * MAP + how.scatter * SCATTER)) {
+  switch (variant(tile, how.acc * ACC + how.split2 * SPLIT2 + how.map * MAP + how.scatter * SCATTER + how.klist * KLIST)) {
     case variant(GemmTile::T64, 0): return m4 ? k_dgemm_tasklist<64, 64, false, 0> : k_dgemm_tasklist<64, 64>;
     case variant(GemmTile::T128, 0): return m4 ? k_dgemm_tasklist<128, 128, false, 0> : k_dgemm_tasklist<128, 128>;
     case variant(GemmTile::T128x64, 0): return k_dgemm_tasklist<128, 64>;
@@ -551,11 +598,12 @@ TaskKernel tasklist_kernel(GemmTile tile, const GemmHow &how) {
     case variant(GemmTile::T64, SCATTER): return m4 ? k_dgemm_tasklist_scatter<64, 64, 0> : k_dgemm_tasklist_scatter<64, 64>;
     case variant(GemmTile::T128, SCATTER): return m4 ? k_dgemm_tasklist_scatter<128, 128, 0> : k_dgemm_tasklist_scatter<128, 128>;
     case variant(GemmTile::T128x64, SCATTER): return k_dgemm_tasklist_scatter<128, 64>;
+    case variant(GemmTile::T64, SCATTER + KLIST): return k_dgemm_tasklist_klist;
     case variant(GemmTile::T128, SPLIT2 + SCATTER): return k_dgemm_tasklist_split2_scatter<128, 128>;
     case variant(GemmTile::T128x64, SPLIT2 + SCATTER): return k_dgemm_tasklist_split2_scatter<128, 64>;
     default:
       throw std::logic_error(std::string("gemm_tasklist_dev: no kernel for tile ") + tile_name(tile) + (how.acc ? " acc" : "") +
-                             (how.split2 ? " split2" : "") + (how.map ? " map" : "") + (how.scatter ? " scatter" : ""));
+                             (how.split2 ? " split2" : "") + (how.map ? " map" : "") + (how.scatter ? " scatter" : "") + (how.klist ? " klist" : ""));
   }
 }
 }  // namespace

@@ -14,7 +14,7 @@ namespace hfg {
 enum class GemmTile { Auto, T64, T128, T128x64 };  // Auto: gemm_prefers_128() picks T64 or T128 (T64 only up to 65535 tasks)
 struct GemmHow {
   GemmTile tile = GemmTile::Auto;
-  bool acc = false, split2 = false, map = false, scatter = false;
+  bool acc = false, split2 = false, map = false, scatter = false, klist = false;
 };
 // kernel by (tile, variant); HELFEM_MFMA=4x4x4 reaches the plain, acc and map lists and gemm_dev:
 //   {} / {T64} / {T128}           k_dgemm_tasklist<64, 64> or <128, 128>
@@ -24,6 +24,7 @@ struct GemmHow {
 //   {T128 or T128x64, split2}     k_dgemm_tasklist_split2<..>     beta == 0 tasks, C zeroed by the caller
 //   {T64, T128 or T128x64, scatter}  k_dgemm_tasklist_scatter<..>  GemmTask::rmap and cmap set in every active task, beta == 0
 //   {T128 or T128x64, split2, scatter}  k_dgemm_tasklist_split2_scatter<..>  likewise, the mapped elements of C zeroed by the caller
+//   {T64, scatter, klist}         k_dgemm_tasklist_klist        the scatter list with the k loop over GemmTask::kstart, nk (no transposes)
 // anything else throws std::logic_error
 void gemm_tasklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxM, int maxN, GemmHow how = {});  // gemm.hip
 // k_dgemm_tasklist_wl<tile>; T64, T128 or T128x64, split2 with T128x64 only
@@ -110,6 +111,10 @@ int64_t eig_sel_count(int nblk, const int64_t *blk_ptr, int64_t nev);  // eig.hi
 void eig_sym_sel_dev(hfg_ctx *ctx, int n, const double *dA, int nev, double *dE, double *dC);  // eig.hip
 void eig_gsym_sub_sel_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
                           const int64_t *blk_idx, int nev, double *dE, double *dC);  // eig.hip
+
+// hfg_ctx_declare_fock_band: the radial-element pattern of F for the blocked eigensolves under the current hfg_ctx_fix_sinvh;
+// returns hfg_ctx::band_state (1 declared, 2 refused: dH0 has a non-zero entry outside the pattern)
+int eig_declare_band(hfg_ctx *ctx, int N, const int *node, int pm, int E, const double *dH0, const int *dBlockId);  // eig.hip
 
 // dc.hip, stsel.hip, trd.hip, trdp.hip: the stages of the eigensolver
 void tridiag_dc_batch(hfg_ctx *ctx, int nblk, const int *ns, double *const *d, double *const *e, double *const *Z);  // dc.hip

@@ -38,6 +38,7 @@ enum class RsTei { host, dev };
   X(cuhf_lowrank, bool, true, "HELFEM_CUHF_LOWRANK", true, "off if 0", atoi(e) != 0, "hfg_cuhf_update_devptr: the constraint from the occupied orbitals (rank na + nb, up to 128 columns); off: the dense natural-orbital sequence always (checker)") \
   X(eig_pair, bool, true, "HELFEM_EIG_PAIR", false, "off if 0", atoi(e) != 0, "both spins' Fock matrices in one batched eigensolve; off: two calls") \
   X(eig_direct, bool, true, "HELFEM_EIG_DIRECT", true, "off if 0", atoi(e) != 0, "one-call blocked eigensolve (hfg_eig_gsym_sub_dev, _sel_dev, _pair_devptr) ranks before its last product and stores that product straight into C; off: block slots, then hfg_eig_assemble_dev (checker)") \
+  X(eig_band, bool, true, "HELFEM_EIG_BAND", true, "off if 0", atoi(e) != 0, "blocked eigensolve under a declared radial-element pattern of F (hfg_ctx_declare_fock_band): rows of F radial-major, F X as row-tile tasks over the k steps that meet their non-zero columns, bit for bit the dense product; off: the declaration is ignored (checker)") \
   X(trd_mode, TrdMode, TrdMode::persistent, "HELFEM_TRD", false, "word", !strcmp(e, "persistent") ? TrdMode::persistent : !strcmp(e, "twokernel") ? TrdMode::twokernel : !strcmp(e, "unblocked") ? TrdMode::unblocked : TrdMode::chain, "tridiagonalisation: persistent = k_trdp where the batch fits, else the chain; chain (and any unknown word) = one k_trdf launch per column always (checker); twokernel = k_trdb_gemv + k_trdb_w; unblocked = the first-generation kernels") \
   X(trdp_min, int, 256, "HELFEM_TRDP_MIN", false, "int", atoi(e), "smallest order the persistent kernel takes") \
   X(trdp_r, int, 0, "HELFEM_TRDP_R", false, "int", atoi(e), "rows per thread of the persistent kernel forced (0: the first that fits)") \

@@ -60,6 +60,27 @@ int hfg_ctx_set_shard(hfg_ctx *ctx, int rank, int nranks);
  * (scf_helpers.cpp:150-157) from it once instead of in every iteration.  Without it every call re-derives them. */
 int hfg_ctx_fix_sinvh(hfg_ctx *ctx, const double *dSinvh);
 
+/* The caller's promise, beside hfg_ctx_fix_sinvh and until its next call, that every Fock matrix handed to the blocked
+ * eigensolves with that Sinvh is local in the radial finite-element index: F(i, j) != 0 only where the radial functions of
+ * i and j lie in a common element.  That holds for F = H0 + J + XC of every LDA / GGA / meta-GGA (and for DIIS
+ * combinations of such matrices), not with exact or range-separated exchange and not under the CUHF constraint.  node[i]
+ * (host, N values, 0 ... pm * E): radial node of basis function i; pm = nodes per element - 1; E elements.  The eigensolve
+ * then takes the rows of every block of F radial-major and forms F X over the k steps that meet the non-zero columns of each
+ * 64-row tile, columns and summation order as in the dense product: E and C are bit for bit those without the declaration
+ * (HELFEM_EIG_BAND=0 ignores it).  dH0 (device, N x N, or
+ * NULL): checked by one reduction, inside the blocks of dBlockId (device, N block ids, or NULL: everywhere); a non-zero
+ * entry outside the pattern refuses the declaration without an error.  *state (may be NULL), and hfg_ctx_fock_band_state:
+ * 0 no declaration, 1 declared, 2 refused.  hfg_ctx_declare_fock_band takes the pattern from the uploaded tables of basis. */
+int hfg_ctx_declare_band(hfg_ctx *ctx, int64_t N, const int *node, int pm, int E, const double *dH0, const int *dBlockId, int *state);
+int hfg_ctx_declare_fock_band(hfg_ctx *ctx, hfg_basis *basis, const double *dH0, const int *dBlockId, int *state);
+int hfg_ctx_fock_band_state(hfg_ctx *ctx, int *state);
+/* The plan behind it, no device needed: node[i] = radial node of position i of one block's index list (n values).  perm (n):
+ * the positions radial-major, the ROW order of F in the product; tile t = rows perm[64 t ...] takes the k steps
+ * kstart[toff[t] ... toff[t + 1]) (toff: (n + 63) / 64 + 1 values; kstart: cap values at most, ((n + 63) / 64) * ((n + 15) / 16)
+ * always suffice): 16 columns each, in the caller's column order, ascending multiples of 4.  *banded: 0 when the block
+ * keeps the dense product (every tile gets all steps). */
+int hfg_eig_band_plan(int64_t n, const int *node, int pm, int E, int64_t *perm, int *toff, int *kstart, int64_t cap, int *banded);
+
 /* ---- basis (host-side setup; no GPU needed) ------------------------------------------------
  * Constructor arguments of diatomic::basis::TwoDBasis (src/diatomic/basis.cpp:307):
  * Z1,Z2,Rhalf, primitive basis (only primbas 4 = LIP on Gauss-Lobatto nodes), n_quad, element
