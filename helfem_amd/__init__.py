@@ -176,6 +176,16 @@ def lib():
         L.hfg_diis_size.argtypes = [ctypes.c_void_p]
         L.hfg_diis_get.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_int64]
         L.hfg_coulomb_dev.argtypes = [ctypes.c_void_p] * 4
+        # the step objects' entries (DeviceSCFStep and its subclasses)
+        L.hfg_fock_compact_size.restype = ctypes.c_int64
+        L.hfg_eig_block_buf_size.restype = ctypes.c_int64
+        L.hfg_fock_compact_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]
+        for name in ("hfg_exchange_dev", "hfg_rs_exchange_dev", "hfg_mix_exchange_devptr"):
+            getattr(L, name).argtypes = [ctypes.c_void_p] * 4
+        for name in ("hfg_exchange_occ_dev", "hfg_mix_exchange_occ_devptr"):
+            getattr(L, name).argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
+        L.hfg_mix_exchange_occ_batch_devptr.argtypes = L.hfg_exchange_occ_batch_devptr.argtypes
         _lib = L
     return _lib
 
@@ -736,14 +746,10 @@ class AtomicTwoDBasis(TwoDBasis):
             if len(counts) != nP:
                 raise ValueError("mix_exchange_torch: one count of occupied orbitals per density")
         if nP == 1 and dC is None:
-            L.hfg_mix_exchange_devptr.argtypes = [ctypes.c_void_p] * 4
             _check(L.hfg_mix_exchange_devptr(ctx.h, self.h, ptr(dP), ptr(out)))
         elif nP == 1:
-            L.hfg_mix_exchange_occ_devptr.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
             _check(L.hfg_mix_exchange_occ_devptr(ctx.h, self.h, ptr(dP), ptr(dC), int(counts[0]), ptr(out)))
         else:
-            L.hfg_mix_exchange_occ_batch_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                            c_i64_p, ctypes.c_int64, ctypes.c_void_p]
             _check(L.hfg_mix_exchange_occ_batch_devptr(ctx.h, self.h, nP, ptr(dP), ptr(dC) if dC is not None else None,
                                                        counts.ctypes.data_as(c_i64_p) if dC is not None else None, N, ptr(out)))
         return out
@@ -1365,6 +1371,25 @@ def _refuse_out_of_scope(who, rohf, cuhf, readocc, maverage, dampfock):
                                   "scf_run_atomic)" % (who, ", ".join(bad)))
 
 
+def _exchange_route(mix, kfrac, kshort, have_C, batch):
+    """the library entries of one exchange build, in call order, as (entry, destination): "K" the matrix handed on, "Krs" the
+    screened matrix of the two-build route, which the caller then adds (K = kfrac K + kshort Krs).  mix: the mixed-kernel
+    table set is there and one build returns the weighted sum; have_C: the occupied orbitals the density was formed from
+    are at hand (the screened build never takes them); batch: several densities in one pass (HELFEM_USCF_KBATCH)"""
+    if mix:
+        if batch:  # the one batched entry takes null orbitals and counts without have_C
+            return [("hfg_mix_exchange_occ_batch_devptr", "K")]
+        return [("hfg_mix_exchange_occ_devptr" if have_C else "hfg_mix_exchange_devptr", "K")]
+    plain, occ, screened = (("hfg_exchange_batch_devptr", "hfg_exchange_occ_batch_devptr", "hfg_rs_exchange_batch_devptr") if batch
+                            else ("hfg_exchange_dev", "hfg_exchange_occ_dev", "hfg_rs_exchange_dev"))
+    route = []
+    if kfrac != 0.0:
+        route.append((occ if have_C else plain, "K"))
+    if kshort != 0.0:
+        route.append((screened, "Krs"))
+    return route
+
+
 class DeviceSCFStep(object):
     """One SCF iteration's hot path, device resident (torch tensors are only used as HBM buffers):
 
@@ -1372,6 +1397,11 @@ class DeviceSCFStep(object):
         all-reduce --> (E, C) --> P' = C_occ C_occ^T
 
     i.e. main.cpp:784-788, 808-900 and 934-971 of the reference's diatomic driver without DIIS.
+
+    step() and run() are written once, here, as compositions of stages, and the stages that act spin by spin (eigensolve,
+    density, core guess, adding K) loop over _spins(), of which this class has one.  A subclass supplies its buffers and
+    what differs for them: the Fock build's entries, the exchange densities, the energy terms, the DIIS hand-over, the
+    one-call eigensolve and when it is taken (_eig_in_one_call), and the hook between Fock build and eigensolve (_constrain).
     """
 
     def __init__(self, basis, x_func, c_func, ldft, mdft, nocc, symmetry=1, device=0, rank=0, nranks=1,
@@ -1437,11 +1467,6 @@ class DeviceSCFStep(object):
             if want > 0 or (want < 0 and MIX_BY_DEFAULT[self.rs_kind]):
                 # False: beyond the bound of the pair path, nothing allocated -- the two-build route
                 self.mix = basis.mix_exchange_tables(float(kfrac), self.kshort, ctx=self.ctx)
-        L = lib()
-        L.hfg_fock_compact_size.restype = ctypes.c_int64
-        L.hfg_eig_block_buf_size.restype = ctypes.c_int64
-        L.hfg_fock_compact_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]
         N = basis.Nbf()
         self.N = N
         self.blocks = basis.get_sym_idx(symmetry)
@@ -1461,16 +1486,8 @@ class DeviceSCFStep(object):
         self.kscale = self.kfrac if self.kshort == 0.0 else 1.0
         self.have_C = False
         self.have_density = False  # set_density() or density() has filled the density buffers
-        if self.kshort != 0.0:
-            self.Krs = None if self.mix else torch.zeros(N * N, dtype=torch.float64, device=self.dev)
-            for name in ("hfg_rs_exchange_dev", "hfg_mix_exchange_devptr"):
-                getattr(L, name).argtypes = [ctypes.c_void_p] * 4
-            L.hfg_mix_exchange_occ_devptr.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
-            L.hfg_mix_exchange_occ_batch_devptr.argtypes = L.hfg_exchange_occ_batch_devptr.argtypes
-        if self.anyK:
-            L.hfg_exchange_occ_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                               ctypes.c_void_p]
-            L.hfg_exchange_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        if self.kshort != 0.0 and not self.mix:
+            self.Krs = torch.zeros(N * N, dtype=torch.float64, device=self.dev)
 
     def _ptr(self, t):
         return ctypes.c_void_p(t.data_ptr())
@@ -1499,26 +1516,23 @@ class DeviceSCFStep(object):
     def exchange(self):
         """K[Pa], Pa = P/2 (closed shell; basis.exchange(Pa) of main.cpp:822) into self.K"""
         self.torch.mul(self.P, 0.5, out=self.Pa)
-        self._build_K(self.Pa, self.C, self.nocc, self.K)
+        self._build_K(self.Pa, self.C, ctypes.c_int64(self.nocc), self.K)
 
-    def _build_K(self, P, C, nocc, K):
-        """one spin's exchange matrix into K: K[P] without a screened term (the caller weights it with kfrac); with one,
-        kfrac K[P] + kshort K_screened[P], from one build on the mixed set or (HELFEM_EXL_MIX=0, a set beyond the bound) from
-        the two table sets, added on the device"""
-        L, h, b = lib(), self.ctx.h, self.basis.h
-        if self.mix:
-            if self.have_C:
-                _check(L.hfg_mix_exchange_occ_devptr(h, b, self._ptr(P), self._ptr(C), ctypes.c_int64(nocc), self._ptr(K)))
-            else:
-                _check(L.hfg_mix_exchange_devptr(h, b, self._ptr(P), self._ptr(K)))
-            return
-        if self.kfrac != 0.0:
-            if self.have_C:
-                _check(L.hfg_exchange_occ_dev(h, b, self._ptr(P), self._ptr(C), ctypes.c_int64(nocc), self._ptr(K)))
-            else:
-                _check(L.hfg_exchange_dev(h, b, self._ptr(P), self._ptr(K)))
-        if self.kshort != 0.0:
-            _check(L.hfg_rs_exchange_dev(h, b, self._ptr(P), self._ptr(self.Krs)))
+    def _build_K(self, P, C, nocc, K, batch=0):
+        """the exchange matrix of one density into K, or (batch = their number) of several, stored one after the other in P,
+        C and K with nocc a pointer to their counts: K[P] without a screened term (the caller weights it with kfrac); with
+        one, kfrac K[P] + kshort K_screened[P], from one build on the mixed set or (HELFEM_EXL_MIX=0, a set beyond the bound)
+        from the two table sets, added on the device.  Which entries: _exchange_route"""
+        L = lib()
+        head = (self.ctx.h, self.basis.h, batch) if batch else (self.ctx.h, self.basis.h)
+        for name, dest in _exchange_route(self.mix, self.kfrac, self.kshort, self.have_C, bool(batch)):
+            args = [self._ptr(P)]
+            if "_occ_" in name:
+                args += [self._ptr(C), nocc] if self.have_C else [None, None]
+                if batch:
+                    args.append(self.N)  # columns per set of orbitals
+            _check(getattr(L, name)(*head, *args, self._ptr(K if dest == "K" else self.Krs)))
+        if self.kshort != 0.0 and not self.mix:
             if self.kfrac != 0.0:
                 K.mul_(self.kfrac).add_(self.Krs, alpha=self.kshort)
             else:
@@ -1532,15 +1546,29 @@ class DeviceSCFStep(object):
         _check(lib().hfg_fock_finish_dev(self.ctx.h, self.basis.h, self._ptr(self.Fc), self._ptr(self.H0),
                                          self._ptr(self.blockid), self._ptr(self.F)))
 
+    def _spins(self):
+        """(P, F, E, C, nocc) per spin: what the stages below loop over"""
+        return ((self.P, self.F, self.E, self.C, self.nocc),)
+
+    def _blockbufs(self):
+        """the eigensolve's block slots, one buffer per spin"""
+        return (self.blockbuf,)
+
+    def _spin_K(self):
+        """the exchange matrix of each spin, as exchange() leaves them"""
+        return (self.K,)
+
     def eig_partial(self):
-        _check(lib().hfg_eig_blocks_dev(self.ctx.h, ctypes.c_int64(self.N), self._ptr(self.F), self._ptr(self.Sinvh),
-                                        len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p),
-                                        self.blk_idx.ctypes.data_as(c_i64_p), self._ptr(self.blockbuf)))
+        for (_, F, _, _, _), buf in zip(self._spins(), self._blockbufs()):
+            _check(lib().hfg_eig_blocks_dev(self.ctx.h, ctypes.c_int64(self.N), self._ptr(F), self._ptr(self.Sinvh),
+                                            len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p),
+                                            self.blk_idx.ctypes.data_as(c_i64_p), self._ptr(buf)))
 
     def eig_finish(self):
-        _check(lib().hfg_eig_assemble_dev(self.ctx.h, ctypes.c_int64(self.N), len(self.blocks),
-                                          self.blk_ptr.ctypes.data_as(c_i64_p), self.blk_idx.ctypes.data_as(c_i64_p),
-                                          self._ptr(self.blockbuf), self._ptr(self.E), self._ptr(self.C)))
+        for (_, _, E, C, _), buf in zip(self._spins(), self._blockbufs()):
+            _check(lib().hfg_eig_assemble_dev(self.ctx.h, ctypes.c_int64(self.N), len(self.blocks),
+                                              self.blk_ptr.ctypes.data_as(c_i64_p), self.blk_idx.ctypes.data_as(c_i64_p),
+                                              self._ptr(buf), self._ptr(E), self._ptr(C)))
 
     def eig_whole(self):
         """the eigensolve of one rank in one call (hfg_eig_gsym_sub_dev): no block slots between two phases"""
@@ -1549,35 +1577,29 @@ class DeviceSCFStep(object):
                                           self.blk_idx.ctypes.data_as(c_i64_p), self._ptr(self.E), self._ptr(self.C)))
 
     def density(self):
-        _check(lib().hfg_form_density_dev(self.ctx.h, ctypes.c_int64(self.N), ctypes.c_int64(self.N), self._ptr(self.C),
-                                          ctypes.c_int64(self.nocc), self._ptr(self.P)))
+        """P_s = C_s,occ C_s,occ^T of every spin; a spin without electrons gets a zero density"""
+        for P, _, _, C, nocc in self._spins():
+            if nocc == 0:
+                P.zero_()
+                continue
+            _check(lib().hfg_form_density_dev(self.ctx.h, ctypes.c_int64(self.N), ctypes.c_int64(self.N), self._ptr(C),
+                                              ctypes.c_int64(nocc), self._ptr(P)))
         self.have_density = True
 
     def step(self, allreduce=None, exchange_blocks=None):
-        """one iteration; allreduce(tensor) sums a tensor over ranks in place (None: single GPU);
-        exchange_blocks(buffer, nblk) completes the per-block eigenvector slots on every rank (parallel.
-        broadcast_block_slots_: one broadcast per block from its owner; None: the sum all-reduce, which the zero
-        padding of the slots owned elsewhere also makes correct)"""
-        shard_fock = self.nranks > 1 and self.fock_shard == "always"
-        if self.nranks > 1 and not shard_fock:
-            self.ctx.set_shard(0, 1)  # every rank builds the whole J + XC: no collective
-        self.fock_partial()
-        if self.nranks > 1 and not shard_fock:
-            self.ctx.set_shard(self.rank, self.nranks)
-        if allreduce is not None and (shard_fock or self.nranks == 1):
-            allreduce(self.Fc)
-            allreduce(self.scal)
-        self.fock_finish()
-        if self.anyK:
-            self.exchange()
-            if allreduce is not None:
-                allreduce(self.K)
-            self.F.add_(self.K, alpha=self.kscale)  # K of a block-diagonal density is block diagonal: no mask needed
+        """one iteration: Fock build, the subclass's constraint (DeviceROHFStep), eigensolve, density.  allreduce(tensor)
+        sums a tensor over ranks in place (None: single GPU); exchange_blocks(buffer, nblk) completes the per-block
+        eigenvector slots on every rank (parallel.broadcast_block_slots_: one broadcast per block from its owner; None: the
+        sum all-reduce, which the zero padding of the slots owned elsewhere also makes correct).  Every rank issues the same
+        collectives in the same order: Fc, scal, K, then the block buffer of each spin.
+        The restricted step leaves P = C_occ C_occ^T, half the total density that set_density() and the Fock build take:
+        the caller doubles it before the next step() (run() does, through _density_stage)."""
+        self._fock_stage(allreduce)
+        self._constrain()
         self._eig_stage(allreduce, exchange_blocks)
         self.density()
-        self.have_C = True  # self.C now holds the orbitals self.P was formed from
+        self.have_C = True  # C now holds the orbitals P was formed from
 
-    # ---- the converging loop: main.cpp:780-995 composed from the stages above, DIIS by a DeviceDIIS --------------------
     def _whole_shard(self, fn):
         """fn() with the context unsharded: what every rank computes whole (J + XC under fock_shard != "always", the J of
         the Coulomb energy)"""
@@ -1590,7 +1612,8 @@ class DeviceSCFStep(object):
                 self.ctx.set_shard(self.rank, self.nranks)
 
     def _fock_stage(self, allreduce):
-        """fock_partial, collectives, fock_finish, exchange: the Fock-build half of step(), same policy"""
+        """the Fock-build half of step(): fock_partial, collectives, fock_finish, exchange.  J + XC is built whole on every
+        rank, without a collective, unless fock_shard is "always"; K is always sharded"""
         shard_fock = self.nranks > 1 and self.fock_shard == "always"
         if shard_fock or self.nranks == 1:
             self.fock_partial()
@@ -1607,25 +1630,41 @@ class DeviceSCFStep(object):
             self._add_exchange()
 
     def _add_exchange(self):
-        self.F.add_(self.K, alpha=self.kscale)
+        """F_s += kscale K_s.  K of a block-diagonal density is block diagonal: no mask needed"""
+        for (_, F, _, _, _), K in zip(self._spins(), self._spin_K()):
+            F.add_(K, alpha=self.kscale)
+
+    def _eig_in_one_call(self, allreduce, exchange_blocks):
+        return self.nranks == 1 and allreduce is None and exchange_blocks is None
 
     def _eig_stage(self, allreduce, exchange_blocks):
-        """the eigensolve half of step(): one call on one rank without collectives, else eig_partial, collective, eig_finish"""
-        if self.nranks == 1 and allreduce is None and exchange_blocks is None:
+        """the eigensolve half of step(): one call (eig_whole) where _eig_in_one_call allows, else eig_partial, the block
+        buffers' collective spin by spin (exchange_blocks wins over allreduce), eig_finish"""
+        if self._eig_in_one_call(allreduce, exchange_blocks):
             self.eig_whole()
             return
         self.eig_partial()
-        if exchange_blocks is not None:
-            exchange_blocks(self.blockbuf, len(self.blocks))
-        elif allreduce is not None:
-            allreduce(self.blockbuf)
+        for buf in self._blockbufs():
+            if exchange_blocks is not None:
+                exchange_blocks(buf, len(self.blocks))
+            elif allreduce is not None:
+                allreduce(buf)
         self.eig_finish()
 
+    # ---- the converging loop: main.cpp:780-995 composed from the stages above, DIIS by a DeviceDIIS --------------------
+    def _nn_buffer(self, name):
+        """the N x N device buffer self.<name>, created when first asked for: step() alone needs none of them (J is 298 MB
+        at Nbf = 6102)"""
+        buf = getattr(self, name, None)
+        if buf is None:
+            buf = self.torch.zeros(self.N * self.N, dtype=self.torch.float64, device=self.dev)
+            setattr(self, name, buf)
+        return buf
+
     def _coulomb_energy_matrix(self, P):
-        if getattr(self, "J", None) is None:
-            self.J = self.torch.zeros(self.N * self.N, dtype=self.torch.float64, device=self.dev)
-        self._whole_shard(lambda: _check(lib().hfg_coulomb_dev(self.ctx.h, self.basis.h, self._ptr(P), self._ptr(self.J))))
-        return self.J
+        J = self._nn_buffer("J")
+        self._whole_shard(lambda: _check(lib().hfg_coulomb_dev(self.ctx.h, self.basis.h, self._ptr(P), self._ptr(J))))
+        return J
 
     def _energy_terms(self):
         """device scalars [E1, 2 Ecoul, Exx / _exx_factor()]"""
@@ -1658,17 +1697,16 @@ class DeviceSCFStep(object):
         self.have_C = True
 
     def _core_guess(self, allreduce, exchange_blocks):
-        self.F.copy_(self.H0)
+        for _, F, _, _, _ in self._spins():
+            F.copy_(self.H0)
         self._eig_stage(allreduce, exchange_blocks)
         self._density_stage()
 
     def _diis_update(self, diis, E):
-        if getattr(self, "Pa", None) is None:
-            self.Pa = self.torch.zeros(self.N * self.N, dtype=self.torch.float64, device=self.dev)
-        self.torch.mul(self.P, 0.5, out=self.Pa)
+        Pa = self.torch.mul(self.P, 0.5, out=self._nn_buffer("Pa"))  # (a hybrid's constructor has made Pa already)
         if self.have_C:
-            return diis.update(E, self.F, self.Pa, self.C, self.nocc)
-        return diis.update(E, self.F, self.Pa)
+            return diis.update(E, self.F, Pa, self.C, self.nocc)
+        return diis.update(E, self.F, Pa)
 
     def _diis_solve(self, diis):
         diis.solve(self.F)
@@ -1741,8 +1779,11 @@ class DeviceUSCFStep(DeviceSCFStep):
         (Pa, Pb) --(J[Pa + Pb] + XC_a | XC_b, compact, sharded)--> all-reduce --> Fa, Fb --(eig blocks of both spins)-->
         (Ea, Ca), (Eb, Cb) --> Pa' = Ca_occ Ca_occ^T, Pb' likewise
 
-    nocc = (nela, nelb) orbitals per spin; nelb = 0 (one-electron systems) leaves Pb and K[Pb] zero.  Context, shard policy,
-    symmetry blocks and their declaration (set_fock_blocks) are the restricted step's.
+    nocc = (nela, nelb) orbitals per spin; nelb = 0 (one-electron systems) leaves Pb and K[Pb] zero.  Set-up (_setup), step(),
+    run() and the stages over _spins() are the restricted step's.  What this class overrides: its buffers and the two-entry
+    _spins(), set_density, the Fock build's _pol entries, the exchange of two densities, the one-call eigensolve (eig_pair,
+    taken on one rank whatever the collectives: the block buffers exist only with several ranks), the energy terms, and
+    the DIIS hand-over.
     """
 
     def __init__(self, basis, x_func, c_func, ldft, mdft, nocc, symmetry=1, device=0, rank=0, nranks=1,
@@ -1779,6 +1820,12 @@ class DeviceUSCFStep(DeviceSCFStep):
     def _spins(self):
         return ((self.Pa, self.Fa, self.Ea, self.Ca, self.nela), (self.Pb, self.Fb, self.Eb, self.Cb, self.nelb))
 
+    def _blockbufs(self):
+        return (self.blockbuf_a, self.blockbuf_b)
+
+    def _spin_K(self):
+        return (self.Ka, self.Kb)
+
     def set_density(self, Pa, Pb, Ca=None, Cb=None):
         """spin densities P_s = C_s,occ C_s,occ^T; Ca, Cb (optional, both or neither): the orbitals they were formed from,
         handed to the exact exchange as their factors"""
@@ -1796,35 +1843,18 @@ class DeviceUSCFStep(DeviceSCFStep):
         """K[Pa] and K[Pb] (basis.exchange of main.cpp:822-829) into self.Ka, self.Kb"""
         if self.kbatch:
             N2 = self.N * self.N
-            L, h, b = lib(), self.ctx.h, self.basis.h
             self.Pab[:N2].copy_(self.Pa)
             self.Pab[N2:].copy_(self.Pb)
             if self.have_C:
                 self.Cab[:N2].copy_(self.Ca)
                 self.Cab[N2:].copy_(self.Cb)
-            if self.mix:  # both spins' weighted sums from the mixed set
-                _check(L.hfg_mix_exchange_occ_batch_devptr(h, b, 2, self._ptr(self.Pab), self._ptr(self.Cab) if self.have_C else None,
-                                                           self._nocc.ctypes.data_as(c_i64_p) if self.have_C else None, self.N,
-                                                           self._ptr(self.K)))
-                return
-            if self.kfrac != 0.0:
-                if self.have_C:
-                    _check(L.hfg_exchange_occ_batch_devptr(h, b, 2, self._ptr(self.Pab), self._ptr(self.Cab),
-                                                           self._nocc.ctypes.data_as(c_i64_p), self.N, self._ptr(self.K)))
-                else:
-                    _check(L.hfg_exchange_batch_devptr(h, b, 2, self._ptr(self.Pab), self._ptr(self.K)))
-            if self.kshort != 0.0:  # the two-build route
-                _check(L.hfg_rs_exchange_batch_devptr(h, b, 2, self._ptr(self.Pab), self._ptr(self.Krs)))
-                if self.kfrac != 0.0:
-                    self.K.mul_(self.kfrac).add_(self.Krs, alpha=self.kshort)
-                else:
-                    self.torch.mul(self.Krs, self.kshort, out=self.K)
+            self._build_K(self.Pab, self.Cab, self._nocc.ctypes.data_as(c_i64_p), self.K, batch=2)
             return
-        for (P, _, _, C, nocc), K in zip(self._spins(), (self.Ka, self.Kb)):
+        for (P, _, _, C, nocc), K in zip(self._spins(), self._spin_K()):
             if nocc == 0:
                 K.zero_()
             else:
-                self._build_K(P, C, nocc, K)
+                self._build_K(P, C, ctypes.c_int64(nocc), K)
 
     def fock_partial(self):
         _check(lib().hfg_fock_compact_pol_devptr(self.ctx.h, self.basis.h, self.x_func, self.c_func, self._ptr(self.Pa),
@@ -1841,82 +1871,16 @@ class DeviceUSCFStep(DeviceSCFStep):
                                                   self.blk_idx.ctypes.data_as(c_i64_p), self._ptr(self.Ea), self._ptr(self.Ca),
                                                   self._ptr(self.Eb), self._ptr(self.Cb)))
 
-    def eig_partial(self):
-        for (_, F, _, _, _), buf in zip(self._spins(), (self.blockbuf_a, self.blockbuf_b)):
-            _check(lib().hfg_eig_blocks_dev(self.ctx.h, ctypes.c_int64(self.N), self._ptr(F), self._ptr(self.Sinvh),
-                                            len(self.blocks), self.blk_ptr.ctypes.data_as(c_i64_p),
-                                            self.blk_idx.ctypes.data_as(c_i64_p), self._ptr(buf)))
+    eig_whole = eig_pair  # the eigensolve of one rank in one call, for two spins
 
-    def eig_finish(self):
-        for (_, _, E, C, _), buf in zip(self._spins(), (self.blockbuf_a, self.blockbuf_b)):
-            _check(lib().hfg_eig_assemble_dev(self.ctx.h, ctypes.c_int64(self.N), len(self.blocks),
-                                              self.blk_ptr.ctypes.data_as(c_i64_p), self.blk_idx.ctypes.data_as(c_i64_p),
-                                              self._ptr(buf), self._ptr(E), self._ptr(C)))
-
-    def density(self):
-        for P, _, _, C, nocc in self._spins():
-            if nocc == 0:
-                P.zero_()
-                continue
-            _check(lib().hfg_form_density_dev(self.ctx.h, ctypes.c_int64(self.N), ctypes.c_int64(self.N), self._ptr(C),
-                                              ctypes.c_int64(nocc), self._ptr(P)))
-        self.have_density = True
-
-    def step(self, allreduce=None, exchange_blocks=None):
-        """one iteration, with the restricted step's policy for allreduce and exchange_blocks; one rank solves the blocks of
-        both spins in one batch"""
-        shard_fock = self.nranks > 1 and self.fock_shard == "always"
-        if self.nranks > 1 and not shard_fock:
-            self.ctx.set_shard(0, 1)  # every rank builds the whole J + XC: no collective
-        self.fock_partial()
-        if self.nranks > 1 and not shard_fock:
-            self.ctx.set_shard(self.rank, self.nranks)
-        if allreduce is not None and (shard_fock or self.nranks == 1):
-            allreduce(self.Fc)
-            allreduce(self.scal)
-        self.fock_finish()
-        if self.anyK:
-            self.exchange()
-            if allreduce is not None:
-                allreduce(self.K)
-            self._add_exchange()
-        if self.nranks == 1:
-            self.eig_pair()
-        else:
-            self.eig_partial()
-            for buf in (self.blockbuf_a, self.blockbuf_b):
-                if exchange_blocks is not None:
-                    exchange_blocks(buf, len(self.blocks))
-                elif allreduce is not None:
-                    allreduce(buf)
-            self.eig_finish()
-        self.density()
-        self.have_C = True  # Ca, Cb now hold the orbitals the densities were formed from
-
-    # ---- the pieces of DeviceSCFStep.run that differ for two spins -----------------------------------------------------
-    def _add_exchange(self):
-        self.Fa.add_(self.Ka, alpha=self.kscale)
-        self.Fb.add_(self.Kb, alpha=self.kscale)
-
-    def _eig_stage(self, allreduce, exchange_blocks):
-        if self.nranks == 1:
-            self.eig_pair()
-            return
-        self.eig_partial()
-        for buf in (self.blockbuf_a, self.blockbuf_b):
-            if exchange_blocks is not None:
-                exchange_blocks(buf, len(self.blocks))
-            elif allreduce is not None:
-                allreduce(buf)
-        self.eig_finish()
+    def _eig_in_one_call(self, allreduce, exchange_blocks):
+        return self.nranks == 1  # with or without collectives: one rank has no block buffers
 
     def _energy_terms(self):
         t = self.torch
-        if getattr(self, "Pt", None) is None:
-            self.Pt = t.zeros(self.N * self.N, dtype=t.float64, device=self.dev)
-        t.add(self.Pa, self.Pb, out=self.Pt)
-        J = self._coulomb_energy_matrix(self.Pt)
-        terms = [t.dot(self.Pt, self.H0), t.dot(self.Pt, J)]
+        Pt = t.add(self.Pa, self.Pb, out=self._nn_buffer("Pt"))
+        J = self._coulomb_energy_matrix(Pt)
+        terms = [t.dot(Pt, self.H0), t.dot(Pt, J)]
         terms.append(t.dot(self.Pa, self.Ka) + t.dot(self.Pb, self.Kb) if self.anyK
                      else t.zeros((), dtype=t.float64, device=self.dev))
         return terms
@@ -1930,12 +1894,6 @@ class DeviceUSCFStep(DeviceSCFStep):
     def _density_stage(self):
         self.density()
         self.have_C = True
-
-    def _core_guess(self, allreduce, exchange_blocks):
-        self.Fa.copy_(self.H0)
-        self.Fb.copy_(self.H0)
-        self._eig_stage(allreduce, exchange_blocks)
-        self._density_stage()
 
     def _diis_update(self, diis, E):
         if self.have_C:
@@ -1955,7 +1913,8 @@ class DeviceROHFStep(DeviceUSCFStep):
     constraint needs the overlap matrix (run() takes it; set_overlap() before step()) and the orbitals: a density set
     without them (set_density without Ca, Cb) is refused.  Every rank applies it to identical inputs: no collective.
     With symmetry blocks lambda is block diagonal up to rounding when the orbitals are; the eigensolve and the blocked DIIS
-    error read the diagonal blocks only."""
+    error read the diagonal blocks only.  The class overrides only the hooks of step() and run(): _constrain, between the
+    Fock build and the eigensolve, and _constraint_begin, which takes run()'s overlap matrix."""
 
     _applies_cuhf = True
 
@@ -1981,10 +1940,3 @@ class DeviceROHFStep(DeviceUSCFStep):
             raise RuntimeError("DeviceROHFStep: the constraint needs the orbitals the densities were formed from "
                                "(set_density with Ca and Cb, or start from the core guess)")
         self.ctx.cuhf_update(self.S, self.Ca, self.nela, self.Cb, self.nelb, self.Fa, self.Fb)
-
-    def step(self, allreduce=None, exchange_blocks=None):
-        """one iteration of DeviceUSCFStep.step with the constraint between the Fock build and the eigensolve"""
-        self._fock_stage(allreduce)
-        self._constrain()
-        self._eig_stage(allreduce, exchange_blocks)
-        self._density_stage()

@@ -54,7 +54,30 @@ def test_symbols_and_argtypes(hf):
     for cls in (hf.TwoDBasis, hf.AtomicTwoDBasis):
         assert callable(cls.exchange_batch) and callable(cls.exchange_batch_torch)
     assert callable(hf.AtomicTwoDBasis.rs_exchange_batch)
-    assert "hfg_exchange_occ_batch_devptr" in hf.DeviceUSCFStep.exchange.__code__.co_names
+
+
+@pytest.mark.parametrize("batch", [False, True])
+@pytest.mark.parametrize("have_C", [False, True])
+@pytest.mark.parametrize("kfrac,kshort", [(0.25, 0.0), (0.19, 0.46), (0.0, 1.0)], ids=["coulomb", "both", "screened"])
+@pytest.mark.parametrize("mix", [False, True])
+def test_exchange_route(hf, mix, kfrac, kshort, have_C, batch):
+    """the step objects' exchange router over its whole contract: which entries one exchange build calls, in which order and
+    into which matrix, for the mixed table set or not, each case of the two weights, with and without the occupied orbitals,
+    for one density and for the batch of HELFEM_USCF_KBATCH.  The table is written out here, not derived."""
+    if mix:  # one build returns the weighted sum, whatever the weights; the batched entry also serves without orbitals
+        want = [({(False, False): "hfg_mix_exchange_devptr", (True, False): "hfg_mix_exchange_occ_devptr",
+                  (False, True): "hfg_mix_exchange_occ_batch_devptr", (True, True): "hfg_mix_exchange_occ_batch_devptr"}[have_C, batch], "K")]
+    else:
+        coulomb = {(False, False): "hfg_exchange_dev", (True, False): "hfg_exchange_occ_dev",
+                   (False, True): "hfg_exchange_batch_devptr", (True, True): "hfg_exchange_occ_batch_devptr"}[have_C, batch]
+        screened = "hfg_rs_exchange_batch_devptr" if batch else "hfg_rs_exchange_dev"  # never takes the orbitals
+        want = {"coulomb": [(coulomb, "K")], "both": [(coulomb, "K"), (screened, "Krs")], "screened": [(screened, "Krs")]}[
+            "coulomb" if kshort == 0.0 else "both" if kfrac != 0.0 else "screened"]
+    got = hf._exchange_route(mix, kfrac, kshort, have_C, batch)
+    assert [tuple(r) for r in got] == want
+    L = hf.lib()
+    for name, _ in got:  # every entry is exported and declared once, by lib()
+        assert getattr(L, name).argtypes is not None, name
 
 
 def test_refusals_without_a_device(hf):

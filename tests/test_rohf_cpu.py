@@ -55,7 +55,19 @@ def test_python_interface_exists(hf):
     assert inspect.isclass(hf.DeviceROHFStep) and issubclass(hf.DeviceROHFStep, hf.DeviceUSCFStep)
     for name in ("run", "step", "set_overlap", "energy"):
         assert callable(getattr(hf.DeviceROHFStep, name)), name
-    assert hf.DeviceROHFStep.step is not hf.DeviceUSCFStep.step and hf.DeviceROHFStep.run is hf.DeviceSCFStep.run
+    assert hf.DeviceROHFStep.run is hf.DeviceSCFStep.run
+    # step() is the base class's composition; what makes it ROHF is the hook between the Fock build and the eigensolve
+    assert hf.DeviceROHFStep._constrain is not hf.DeviceSCFStep._constrain and hf.DeviceROHFStep._applies_cuhf
+
+
+def test_step_applies_the_constraint_after_the_fock_stage(hf):
+    step = object.__new__(hf.DeviceROHFStep)
+    step.S, calls = None, []
+    step._fock_stage = lambda allreduce: calls.append("fock")
+    step._eig_stage = lambda allreduce, exchange_blocks: calls.append("eig")
+    with pytest.raises(RuntimeError, match="set_overlap first"):
+        step.step()
+    assert calls == ["fock"]
 
 
 @pytest.mark.parametrize("opt", [dict(readocc=0), dict(maverage=True), dict(dampfock=0.7)])
