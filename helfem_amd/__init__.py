@@ -154,6 +154,7 @@ def lib():
         L.hfg_exchange_occ_batch_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                                     c_i64_p, ctypes.c_int64, ctypes.c_void_p]
         L.hfg_exchange_batch_plan.argtypes = [ctypes.c_int64, c_int_p, ctypes.c_int, c_int_p, c_int_p]
+        L.hfg_exl_last_plan.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
         L.hfg_fock_compact_pol_size.restype = ctypes.c_int64
         L.hfg_fock_compact_pol_size.argtypes = [ctypes.c_void_p]
         L.hfg_fock_compact_pol_devptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -487,6 +488,15 @@ class TwoDBasis(object):
         K = np.zeros_like(P, order="F")
         _check(lib().hfg_exchange(ctx.h, self.h, _p(P), _p(K)))
         return K
+
+    def exchange_last_plan(self, which="coulomb"):
+        """what the last low-rank exchange builds on a table set took (hfg_exl_last_plan; which: "coulomb", "screened" or
+        "mix"): {"single": record or None, "batch": record or None}, the kernels, tiles and launchers chosen, see
+        include/helfem_gpu.h"""
+        import json
+        buf = ctypes.create_string_buffer(1 << 14)
+        _check(lib().hfg_exl_last_plan(self.h, which.encode(), buf, ctypes.c_size_t(len(buf))))
+        return json.loads(buf.value.decode())
 
     def _batch(self, Ps, ctx):
         """the context of a batched call (uploading to it when the tables are nowhere yet) and the densities in the layout

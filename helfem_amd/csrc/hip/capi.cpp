@@ -1382,6 +1382,17 @@ int hfg_tuning_table(char *buf, size_t cap) {
   HFG_CATCH
 }
 
+int hfg_exl_last_plan(hfg_basis *basis, const char *which, char *buf, size_t cap) {
+  HFG_TRY
+  if (!basis || !which || !buf) throw std::logic_error("hfg_exl_last_plan: null basis, name or buffer\n");
+  const std::string w(which);
+  if (w != "coulomb" && w != "screened" && w != "mix") throw std::logic_error("hfg_exl_last_plan: the table set is coulomb, screened or mix\n");
+  const std::string all = exl_last_plan_json(basis, w == "coulomb" ? ExTables::coulomb : w == "screened" ? ExTables::screened : ExTables::mix);
+  if (cap == 0 || all.size() + 1 > cap) throw std::logic_error("hfg_exl_last_plan: buffer too small\n");
+  memcpy(buf, all.c_str(), all.size() + 1);
+  HFG_CATCH
+}
+
 int hfg_measure_kernel(hfg_ctx *ctx, const char *name, double *ms, int64_t *launches) {
   HFG_TRY
   if (std::string(name) == "k_trdb_gemv" || std::string(name) == "k_trdf") trd_measure_gemv(ctx, ms, launches);

@@ -20,13 +20,15 @@
 // back to the general kernels of exchange.hip.  Same sums as the reference, different association order.
 #include "internal.h"
 #include "../host/exchange_batch_plan.h"
+#include "../host/exl_plan.h"
 #include <algorithm>
 #include <cstdlib>
 
 namespace hfg {
 
-constexpr int EXL_RMAX = 64;
-constexpr int EXL_QMAX = 16;  // rows per thread in the factorisation kernel: N <= 1024 * EXL_QMAX
+// the sizes the kernels below are written for and every choice of kernel, tile and launcher: host/exl_plan.h
+using helfem::EXL_RMAX, helfem::EXL_QMAX, helfem::EXL_AG, helfem::EXL_AP;
+using helfem::ExlSwitches, helfem::ExlTile, helfem::ExlRB, helfem::ExlCross, helfem::ExlElem, helfem::ExlPlanRecord;
 
 // -------------------------------------------------------------------------------------------------
 // pivoted LDL^T, one workgroup
@@ -302,8 +304,7 @@ __global__ void k_exl_alpha_gen(const double *__restrict__ V0, const double *__r
 // its element in registers and walks over the shells j = g, g + EXL_AG, ...; the column of V is staged in LDS (the p
 // values a thread needs per shell are the same for the p lanes of an (e, j): broadcast reads).  (One workgroup per (column, shell) with the tables read
 // from L2 per output took 1.5 ms at Nbf = 4230: 268 000 workgroups of 75 active threads.)
-constexpr int EXL_AG = 4;
-constexpr int EXL_AP = 16;  // p at most
+// (EXL_AG groups of shells, p <= EXL_AP: host/exl_plan.h)
 // BATCH (exchange_batch_dev): r columns are the concatenated factors of several densities, column o belongs to density
 // bcol[o], whose columns are boff[b] .. boff[b + 1]; the output columns are density-major, NLM boff[b] + (channel, factor of
 // b): every density's block of aP / aQw has the layout of its single build, so the products never pair two densities
@@ -967,7 +968,26 @@ struct ExLRAux : Workspace {
   std::vector<MRun> runs;
   std::vector<int> chM0;
   int max_nch = 0;
+  ExlPlanRecord plan;  // what the last single build on this table set took (hfg_exl_last_plan)
 };
+
+static ExlSwitches exl_switches() {
+  ExlSwitches sw;
+  sw.rb = tuning().exl_rb;
+  sw.mgroups = tuning().exl_mgroups;
+  sw.rect = tuning().exl_rect;
+  sw.wl = tuning().exl_wl;
+  sw.splitk = tuning().exl_splitk;
+  sw.crect = tuning().exl_crect;
+  return sw;
+}
+static GemmTile exl_gemm_tile(ExlTile t) {
+  return t == ExlTile::T64 ? GemmTile::T64 : t == ExlTile::T128 ? GemmTile::T128 : t == ExlTile::T128x64 ? GemmTile::T128x64 : GemmTile::Auto;
+}
+static void exl_plan_start(ExlPlanRecord &rec, bool batch, const hfg_dev_tables *t, const ExLRAux &a) {
+  rec.start(batch, t->NLM, t->A, t->Ntab, t->E, t->p);
+  for (const ExLRAux::MRun &run : a.runs) rec.run_shells.push_back(run.nj);
+}
 
 static void exlr_setup(hfg_ctx *ctx, const hfg_dev_tables *t, ExLRAux *a) {
   hipStream_t s = ctx->stream;
@@ -1115,14 +1135,17 @@ static ExLRAux &exlr_for(hfg_ctx *ctx, hfg_dev_tables *t) {
 /// same columns one line earlier): the factorisation, its verification and their host synchronisation are skipped.
 bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, double *dK, const double *Lknown, int rknown) {
   const int A = t->A, R = t->R, E = t->E, p = t->p, Nd = t->Nd, N = t->N, NLM = t->NLM, Ntab = t->Ntab, ntt = t->ntt;
-  if (N > 1024 * EXL_QMAX) return false;
+  if (!helfem::exl_order_fits(N)) return false;
   // erfc kernel (pair_tei): no factorisation over elements; the element-pair products below need an exchange-ordered
   // copy of the pair tables
-  if (t->pair_tei && (double)ntt * Ntab * E * E * p * p * p * p * sizeof(double) > EXL_PAIR_MAX_BYTES) return false;
+  if (t->pair_tei && !helfem::exl_pair_tables_fit(ntt, Ntab, E, p, EXL_PAIR_MAX_BYTES)) return false;
   if (t->pair_tei && !tuning().exl_pair) return false;
   ExLRAux &a = exlr_for(ctx, t);
+  const ExlSwitches sw = exl_switches();
+  exl_plan_start(a.plan, false, t, a);
+  a.plan.declined = true;  // until the factors are there (the declines above come before the table set has its workspace: no record)
   for (const ExLRAux::MRun &run : a.runs)
-    if (run.nj > 256) return false;  // k_exl_V lists at most 256 coupled shells
+    if (!helfem::exl_run_fits(run.nj)) return false;  // k_exl_V lists at most 256 coupled shells
   hipStream_t s = ctx->stream;
   const int two = (ntt == 4) ? 1 : 0;
   const int pp = p * p;
@@ -1171,14 +1194,16 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
     gemm_dev(ctx, false, true, N, N, r, -1.0, Lg, N, a.LS.p, N, 1.0, a.Pwork.p, N);
     Pcur = a.Pwork.p;
   }
+  a.plan.ranks = rg;
   if (!reproduced) return false;
   int rmax_g = 0;
   for (int r : rg) rmax_g = std::max(rmax_g, r);
-  {
-    // the one-pair kernels (erfc pair tables, p > 16, HELFEM_EXL_RB=1) stage all (channel, factor) columns at once
-    const bool one_pair = t->pair_tei || p > 16 || tuning().exl_rb == 1;
-    if (one_pair && (size_t)(4 * a.max_nch * rmax_g * p + a.max_nch * rmax_g) * sizeof(double) > 150 * 1024) return false;
-  }
+  const ExlRB rb_kernel = helfem::exl_rb_kernel(t->pair_tei != 0, p, sw);
+  a.plan.rb = rb_kernel;
+  // the one-pair kernels (erfc pair tables, p > 16, HELFEM_EXL_RB=1) stage all (channel, factor) columns at once
+  if (!helfem::exl_rb_fits(rb_kernel, a.max_nch, rmax_g, p)) return false;
+  a.plan.declined = false;
+  a.plan.cross_split.assign(rg.size(), 0);
   if (rmax_g == 0) {  // P == 0
     HFG_HIP_CHECK(hipMemsetAsync(dK, 0, sizeof(double) * (size_t)N * N, s));
     return true;
@@ -1207,9 +1232,11 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   hipLaunchKernelGGL(k_exl_V, dim3(NLM, A), dim3(256), 0, s, a.Ld.p, Nd, R, A, r, a.LM_L.p, a.LM_M.p, t->shell_m.p,
                      a.c0tab.p, a.c2tab.p, t->Lp1, two, a.V0.p, a.V2.p);
   // cross products by blocks of equal m (below) need the M-major column order, which only the fast alpha kernel writes
-  const size_t alds = (size_t)(two ? 2 : 1) * Nd * sizeof(double);
-  const bool alpha_fast = !(p > EXL_AP || E * p > 512 || alds > 150 * 1024);
-  const bool grouped = !pair && a.cross_ok && alpha_fast && tuning().exl_mgroups;
+  const size_t alds = helfem::exl_alpha_lds(ntt, Nd);
+  const bool alpha_fast = helfem::exl_alpha_fast(p, E, alds);
+  const bool grouped = helfem::exl_grouped(pair, (int)a.runs.size(), alpha_fast, sw);
+  a.plan.alpha_fast = alpha_fast;
+  a.plan.grouped = grouped;
   if (!pair) {
   if (!alpha_fast)
     hipLaunchKernelGGL(k_exl_alpha_gen, dim3((unsigned)ncol, A), dim3(128), 0, s, a.V0.p, a.V2.p, t->disj.p, t->LM_tab.p,
@@ -1229,7 +1256,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   // ---- cross-element part: G_ef = aQw_e aP_f^T for e > f (the other half of K is its transpose) ----
   if (!pair) {
     std::vector<GemmTask> ct;
-    int maxMN = 0;
+    int maxMN = 0, maxM = 0, maxNc = 0;  // (maxM, maxNc: for the record)
     long tiles = 0;
     for (int e = 1; e < E; e++)
       for (int f = 0; f < e; f++) {
@@ -1245,8 +1272,8 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
           g.M = g.N = (int)Ap;
           g.K = (int)ncol;
           ct.push_back(g);
-          maxMN = (int)Ap;
-          tiles += (long)((Ap + 127) / 128) * ((Ap + 127) / 128);
+          maxMN = maxM = maxNc = (int)Ap;
+          tiles += helfem::exl_tiles128((long)Ap, (long)Ap);
           continue;
         }
         // V^t_j vanishes unless some shell i has m_i = m_j - M: a block (run of m_j, run of m_k) of G only sums over the
@@ -1264,20 +1291,35 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
             g.K = (k1 - k0) * r;
             ct.push_back(g);
             maxMN = std::max(maxMN, std::max(g.M, g.N));
-            tiles += (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
+            maxM = std::max(maxM, g.M);
+            maxNc = std::max(maxNc, g.N);
+            tiles += helfem::exl_tiles128(g.M, g.N);
           }
       }
+    const ExlCross cross = helfem::exl_cross((long)ncol, tiles, grouped, sw);
+    a.plan.cross_split[g] = (!ct.empty() && cross.split) ? 1 : 0;
+    a.plan.n_cross_split = cross.split ? (int)ct.size() : 0;
+    a.plan.n_cross_plain = cross.split ? 0 : (int)ct.size();
+    a.plan.cross_maxM = maxM;
+    a.plan.cross_maxN = maxNc;
+    a.plan.cross_minK = a.plan.cross_maxK = a.plan.cross_skipped = 0;  // (of this group)
+    for (const GemmTask &q : ct) a.plan.cross_task(q.K);
+    if (grouped && E > 1) a.plan.cross_skipped = (int)(a.runs.size() * a.runs.size()) - (int)(ct.size() / ((size_t)E * (E - 1) / 2));
+    if (!ct.empty()) {
+      (cross.split ? a.plan.cross_split_tile : a.plan.cross_plain_tile) = cross.tile;
+      if (cross.split) a.plan.cross_worklist = cross.worklist;
+    }
     if (grouped) HFG_HIP_CHECK(hipMemsetAsync(a.G.p, 0, sizeof(double) * (size_t)E * (E - 1) / 2 * Ap * Ap, s));
     if (!ct.empty()) {
       a.ctasks.upload(ct, s);
       HFG_HIP_CHECK(hipStreamSynchronize(s));  // ct lives on this stack frame
       // few large tiles (ten products of 8 x 8 tiles at Nbf = 4230: 640 tiles on 512 slots run as two rounds): two
       // half-K workgroups per tile into a zeroed G fill the slots evenly (two addends per element: deterministic)
-      if (tuning().exl_splitk && tiles < 2048 && ncol >= 512) {
+      if (cross.split) {
         if (!grouped) HFG_HIP_CHECK(hipMemsetAsync(a.G.p, 0, sizeof(double) * ct.size() * Ap * Ap, s));
         // 128 x 64 tiles: the blocks of ~300 columns pad to 320 instead of 384 (11.6 -> 11.5 ms per build; HELFEM_EXL_CRECT=0: square)
-        const GemmTile tile = (tuning().exl_crect && grouped) ? GemmTile::T128x64 : GemmTile::T128;
-        if (tile == GemmTile::T128x64 && tuning().exl_wl) {
+        const GemmTile tile = exl_gemm_tile(cross.tile);
+        if (cross.worklist) {
           // all tiles of a product on one XCD: its operand blocks are fetched once (2.4 GB were fetched for 0.3 GB of aP, aQw)
           gemm_worklist(ct, tile, true, a.h_cwl);
           a.cwl.upload(a.h_cwl, s);
@@ -1295,8 +1337,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
   const int Kt = ntt * pp;
   // the matrix-core RB kernel writes columns of a.kK >= Kt rows (zero padded like the element tables): every k step of
   // the GEMM is then a full one; the vector kernels (checkers, p > 16) and the pair tables keep the unpadded columns
-  const bool rb_one = tuning().exl_rb == 1, rb_four = tuning().exl_rb == 4;  // the one-pair and the 4 x 4 vector kernel (checkers)
-  const bool rb_mfma = !pair && p <= 16 && !rb_one && !rb_four;
+  const bool rb_mfma = rb_kernel == ExlRB::mfma;
   const int Kld = rb_mfma ? a.kK : Kt;
   size_t rb_tot = 0, c_tot = 0;
   int maxN = 0;
@@ -1373,7 +1414,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
                            p, r, ntt, a.RB.p);
       else {
         const size_t shb4 = (size_t)(4 * EXL_SB * EXL_CK * p + EXL_CK) * sizeof(double);
-        if (!rb_one && !rb_four && p <= 16) {
+        if (rb_mfma) {
           // the list of workgroups depends on the tables and on the shard only
           if (a.rbm_shard != ctx->shard_rank * 65536 + ctx->shard_n) {
             std::vector<int4> wl;
@@ -1400,7 +1441,7 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
                                  t->LM_fac.p, sgrp, a.S_off.p, a.S_list.p, a.rb_off.p, a.rbm_list.p, a.rbm_n, Nd, R, E, p, r, Kld,
                                  a.RB.p, nullptr, 1);
           }
-        } else if (rb_one || p > 16)
+        } else if (rb_kernel == ExlRB::one_pair)
           hipLaunchKernelGGL(k_exl_RB, dim3(max_ns * (max_ns + 1) / 2, E, nz), dim3(256), shb, s, a.V0.p, a.V2.p, a.tab_ch_off.p,
                              a.tab_ch.p, t->LM_fac.p, sgrp, a.S_off.p, a.S_list.p, a.rb_off.p, tau0, Nd, R, E, p, r, ntt,
                              a.RB.p);
@@ -1418,10 +1459,14 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
     // ... for the shorter pair lists; with the longer lists of larger angular bases the padding is small either way and
     // the square tiles' lower LDS traffic per flop wins (measured: Nbf = 4230, 1000 pairs per task on average, 11.6 against
     // 12.0 ms per build; Nbf = 6102, 28.6 against 29.4 the other way round)
-    const int rect_env = tuning().exl_rect;
     double ncols_tot = 0.0;
     for (const GemmTask &q : tasks) ncols_tot += (double)q.N;
-    const bool rect_tiles = rect_env >= 0 ? rect_env != 0 : (ncols_tot < 1500.0 * (double)tasks.size());
+    const ExlElem elem = helfem::exl_elem(ncols_tot, tasks.size(), sw);
+    a.plan.elem_tile = elem.tile;
+    a.plan.elem_worklist = elem.worklist;
+    a.plan.n_elem = (int)tasks.size();
+    a.plan.max_pairs = maxN;
+    a.plan.elem_over = tasks[0].over != 0;
     // bench.py: HIP events around this launch alone ("exl_element_gemm") and its USEFUL work in GFLOP, 2 p^2 pairs (ntt p^2)
     // per task without any padding, accumulated in the `ms` field of "exl_element_gemm_gflop"
     ProfScope pgemm(ctx, "exl_element_gemm");
@@ -1431,17 +1476,16 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
       ctx->prof["exl_element_gemm_gflop"].ms += gf;
       ctx->prof["exl_element_gemm_gflop"].launches += 1;
     }
-    if (tuning().exl_wl) {  // (off, the checker: plain task-list grid)
+    if (elem.worklist) {  // (off, the checker: plain task-list grid)
       // all tiles of a task on one XCD (its element table is then fetched from HBM once, not by all eight L2s)
       // short pair lists: 64 x 64 tiles (three workgroups per CU; 5.71 against 6.08 ms with 128 x 64 at Nbf = 4230); long lists:
       // 128 x 128 (15.5 against 15.8 ms with 64 x 64 at Nbf = 6102).  HELFEM_EXL_RECT = 0 / 1 / 2 forces 128 x 128 / 128 x 64 / 64 x 64
-      const int tile_mode = rect_env >= 0 ? rect_env : (rect_tiles ? 2 : 0);
-      const GemmTile tile = tile_mode == 2 ? GemmTile::T64 : tile_mode == 1 ? GemmTile::T128x64 : GemmTile::T128;
+      const GemmTile tile = exl_gemm_tile(elem.tile);
       gemm_worklist(tasks, tile, false, a.h_gwl);
       a.gwl.upload(a.h_gwl, s);  // (h_gwl lives in the aux until the synchronisation at the end of the build)
       gemm_worklist_dev(ctx, a.tasks.p, a.gwl.p, (int)a.h_gwl.size(), tile);
     } else
-      gemm_tasklist_dev(ctx, a.tasks.p, (int)tasks.size(), pp, maxN, {rect_tiles ? GemmTile::T128x64 : GemmTile::Auto});
+      gemm_tasklist_dev(ctx, a.tasks.p, (int)tasks.size(), pp, maxN, {exl_gemm_tile(elem.tile)});
   }
   if (pair)
     hipLaunchKernelGGL(k_exl_reduce_pair, dim3(A * A, E * (E + 1) / 2), dim3(256), 0, s, a.C.p, a.c_off.p, a.S_off.p, a.pos.p,
@@ -1479,18 +1523,16 @@ struct ExLBatchAux : Workspace {
   std::vector<long long> h_rb_off, h_c_off;
   std::vector<GemmTask> h_tasks, h_csplit, h_cplain, h_ctasks;
   long rbm_key = -1;  // (shard, densities) the list of k_exl_RBm's workgroups was made for
+  ExlPlanRecord plan;  // what the last chunk on this table set took (hfg_exl_last_plan)
 };
 
 /// the table sets whose batches run the batched stages: those whose single build takes the matrix-core RB kernel and the
 /// fast alpha kernel.  The others (erfc pair tables, more than 16 nodes per element, the checkers of HELFEM_EXL_RB) loop
 /// over the single build inside the batched entry.
 static bool exl_batch_takes(const hfg_dev_tables *t, const ExLRAux &a) {
-  if (t->N > 1024 * EXL_QMAX || t->pair_tei || t->p > EXL_AP || t->E * t->p > 512) return false;
-  if (tuning().exl_rb == 1 || tuning().exl_rb == 4) return false;
-  if ((size_t)(t->ntt == 4 ? 2 : 1) * t->Nd * sizeof(double) > 150 * 1024) return false;
-  for (const ExLRAux::MRun &run : a.runs)
-    if (run.nj > 256) return false;
-  return true;
+  std::vector<int> nj;
+  for (const ExLRAux::MRun &run : a.runs) nj.push_back(run.nj);
+  return helfem::exl_batch_takes(t->N, t->pair_tei != 0, t->p, t->E, t->ntt, t->Nd, nj.data(), (int)nj.size(), exl_switches());
 }
 
 /// one chunk: nB >= 2 densities of ranks rk[b] >= 1 (64 in all at most) with factors Lp[b] (N x rk[b]) and signs sp[b]
@@ -1502,6 +1544,13 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
   const int two = (ntt == 4) ? 1 : 0;
   const int pp = p * p;
   if (E > 65535 || nB > 32767) throw std::logic_error("exchange_batch_chunk: element or density index beyond the work list's fields\n");
+  const ExlSwitches sw = exl_switches();
+  exl_plan_start(w.plan, true, t, a);
+  w.plan.chunks++;
+  w.plan.ranks.assign(rk, rk + nB);
+  w.plan.cross_split.assign(nB, 0);
+  w.plan.alpha_fast = true;  // (exl_batch_takes)
+  w.plan.rb = ExlRB::mfma;
 
   // ---- the chunk's factor columns, one density after the other ----
   w.h_boff.assign(nB + 1, 0);
@@ -1537,9 +1586,10 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
                      a.Ld.p);
   hipLaunchKernelGGL(k_exl_V, dim3(NLM, A), dim3(256), 0, s, a.Ld.p, Nd, R, A, rT, a.LM_L.p, a.LM_M.p, t->shell_m.p, a.c0tab.p,
                      a.c2tab.p, t->Lp1, two, a.V0.p, a.V2.p);
-  const bool grouped = a.cross_ok && tuning().exl_mgroups;
+  const bool grouped = helfem::exl_grouped(false, (int)a.runs.size(), true, sw);
+  w.plan.grouped = grouped;
   {
-    const size_t alds = (size_t)(two ? 2 : 1) * Nd * sizeof(double);
+    const size_t alds = helfem::exl_alpha_lds(ntt, Nd);
     const int per = E * p, ng = std::max(1, std::min(EXL_AG, 512 / per));
     if (alds > 64 * 1024)
       HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_exl_alpha<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)alds));
@@ -1554,6 +1604,7 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
     w.h_csplit.clear();
     w.h_cplain.clear();
     int maxMN = 0, n1 = 0;  // largest side and number of the tasks of ONE density
+    ExlCross split_how;
     for (int b = 0; b < nB; b++) {
       const int r = rk[b];
       const size_t base = (size_t)NLM * w.h_boff[b] * Na;  // this density's block of aP / aQw: the layout of its single build
@@ -1575,7 +1626,8 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
             g.K = NLM * r;
             ct.push_back(g);
             maxMN = (int)Ap;
-            tiles += (long)((Ap + 127) / 128) * ((Ap + 127) / 128);
+            w.plan.cross_maxM = w.plan.cross_maxN = (int)Ap;
+            tiles += helfem::exl_tiles128((long)Ap, (long)Ap);
             continue;
           }
           for (const ExLRAux::MRun &rj : a.runs)
@@ -1591,13 +1643,19 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
               g.K = (k1 - k0) * r;
               ct.push_back(g);
               maxMN = std::max(maxMN, std::max(g.M, g.N));
-              tiles += (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
+              w.plan.cross_maxM = std::max(w.plan.cross_maxM, g.M);
+              w.plan.cross_maxN = std::max(w.plan.cross_maxN, g.N);
+              tiles += helfem::exl_tiles128(g.M, g.N);
             }
         }
       n1 = (int)ct.size();
-      // split K or not: the rule of the single build, on this density's own column count
-      const bool split = tuning().exl_splitk && tiles < 2048 && (size_t)NLM * r >= 512;
-      std::vector<GemmTask> &dst = split ? w.h_csplit : w.h_cplain;
+      for (const GemmTask &q : ct) w.plan.cross_task(q.K);
+      if (grouped) w.plan.cross_skipped = (int)(a.runs.size() * a.runs.size()) - n1 / (E * (E - 1) / 2);
+      // split K or not, and how: the single build's rule (host/exl_plan.h) on this density's own column count
+      const ExlCross cross = helfem::exl_cross((long)NLM * r, tiles, grouped, sw);
+      if (cross.split) split_how = cross;  // (tile and launcher follow from the switches: the same for every split member)
+      w.plan.cross_split[b] = (!ct.empty() && cross.split) ? 1 : 0;
+      std::vector<GemmTask> &dst = cross.split ? w.h_csplit : w.h_cplain;
       dst.insert(dst.end(), ct.begin(), ct.end());
     }
     if (grouped || !w.h_csplit.empty()) HFG_HIP_CHECK(hipMemsetAsync(w.G.p, 0, sizeof(double) * nG * nB, s));
@@ -1605,9 +1663,13 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
     w.h_ctasks.insert(w.h_ctasks.end(), w.h_cplain.begin(), w.h_cplain.end());
     w.ctasks.upload(w.h_ctasks, s);
     const int nsplit = (int)w.h_csplit.size(), nplain = (int)w.h_cplain.size();
+    w.plan.n_cross_split = nsplit;
+    w.plan.n_cross_plain = nplain;
     if (nsplit) {
-      const GemmTile tile = (tuning().exl_crect && grouped) ? GemmTile::T128x64 : GemmTile::T128;
-      if (tile == GemmTile::T128x64 && tuning().exl_wl) {
+      const GemmTile tile = exl_gemm_tile(split_how.tile);
+      w.plan.cross_split_tile = split_how.tile;
+      w.plan.cross_worklist = split_how.worklist;
+      if (split_how.worklist) {
         gemm_worklist(w.h_csplit, tile, true, w.h_cwl);
         w.cwl.upload(w.h_cwl, s);
         gemm_worklist_dev(ctx, w.ctasks.p, w.cwl.p, (int)w.h_cwl.size(), tile, true);
@@ -1618,6 +1680,7 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
       // the tiles the single build's launch of n1 tasks takes
       const long t128 = (long)((maxMN + 127) / 128) * ((maxMN + 127) / 128);
       const GemmTile tile = (n1 <= 65535 && !gemm_prefers_128(ctx, (long)n1 * t128)) ? GemmTile::T64 : GemmTile::T128;
+      w.plan.cross_plain_tile = tile == GemmTile::T64 ? ExlTile::T64 : ExlTile::T128;  // (the single build records Auto: the launcher resolves it)
       gemm_tasklist_dev(ctx, w.ctasks.p + nsplit, nplain, maxMN, maxMN, {tile});
     }
   }
@@ -1695,8 +1758,12 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
     }
     // tiles: the single build's rule on the pair lists of ONE density, so that every column is summed by the kernel its
     // single build uses
-    const int rect_env = tuning().exl_rect;
-    const bool rect_tiles = rect_env >= 0 ? rect_env != 0 : (pairs1 < 1500.0 * (double)w.h_tasks.size());
+    const ExlElem elem = helfem::exl_elem(pairs1, w.h_tasks.size(), sw);
+    w.plan.elem_tile = elem.tile;
+    w.plan.elem_worklist = elem.worklist;
+    w.plan.n_elem = (int)w.h_tasks.size();
+    w.plan.max_pairs = maxN1;
+    w.plan.elem_over = w.h_tasks[0].over != 0;
     ProfScope pgemm(ctx, "exl_batch_element_gemm");
     if (ctx->profiling) {  // useful work in GFLOP, as "exl_element_gemm_gflop" of the single build
       double gf = 0.0;
@@ -1704,17 +1771,17 @@ static void exchange_batch_chunk(hfg_ctx *ctx, hfg_dev_tables *t, ExLRAux &a, Ex
       ctx->prof["exl_batch_element_gemm_gflop"].ms += gf;
       ctx->prof["exl_batch_element_gemm_gflop"].launches += 1;
     }
-    if (tuning().exl_wl) {
-      const int tile_mode = rect_env >= 0 ? rect_env : (rect_tiles ? 2 : 0);
-      const GemmTile tile = tile_mode == 2 ? GemmTile::T64 : tile_mode == 1 ? GemmTile::T128x64 : GemmTile::T128;
+    if (elem.worklist) {
+      const GemmTile tile = exl_gemm_tile(elem.tile);
       gemm_worklist(w.h_tasks, tile, false, w.h_gwl);
       w.gwl.upload(w.h_gwl, s);
       gemm_worklist_dev(ctx, w.tasks.p, w.gwl.p, (int)w.h_gwl.size(), tile);
     } else {
       const int nt = (int)w.h_tasks.size();
       const long t128 = (long)((pp + 127) / 128) * ((maxN1 + 127) / 128);
-      const GemmTile tile = rect_tiles ? GemmTile::T128x64
-                                       : (nt <= 65535 && !gemm_prefers_128(ctx, (long)nt * t128)) ? GemmTile::T64 : GemmTile::T128;
+      // Auto: what the launcher picks for the single build's grid, not for this wider one
+      const GemmTile tile = elem.tile != ExlTile::Auto ? exl_gemm_tile(elem.tile)
+                                                       : (nt <= 65535 && !gemm_prefers_128(ctx, (long)nt * t128)) ? GemmTile::T64 : GemmTile::T128;
       gemm_tasklist_dev(ctx, w.tasks.p, nt, pp, maxN1 * nB, {tile});
     }
   }
@@ -1755,6 +1822,7 @@ void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double
     return;
   }
   ExLBatchAux &w = t->work.get<ExLBatchAux>(WS_EXLR_BATCH);
+  w.plan.chunks = 0;
   hipStream_t s = ctx->stream;
 
   // ---- factorise and verify every density that comes without factors: k_exl_factor and k_exl_resid as in the single
@@ -1811,6 +1879,15 @@ void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double
     if (rk.size() == 1) single(first);  // the single build's code path (and its residual groups, its general kernels)
     else exchange_batch_chunk(ctx, t, *a, w, (int)rk.size(), rk.data(), Lp.data(), sp.data(), Kp.data());
   }
+}
+
+/// hfg_exl_last_plan: {"single": record or null, "batch": record or null} of a table set, what its last builds took
+std::string exl_last_plan_json(hfg_basis *basis, ExTables which) {
+  const hfg_dev_tables *t = which == ExTables::mix ? basis->dev_mix : which == ExTables::screened ? basis->dev_rs : basis->dev;
+  const ExLRAux *a = t ? t->work.find<ExLRAux>(WS_EXLR) : nullptr;
+  const ExLBatchAux *w = t ? t->work.find<ExLBatchAux>(WS_EXLR_BATCH) : nullptr;
+  return "{\"single\": " + (a ? helfem::exl_plan_json(a->plan) : std::string("null")) + ", \"batch\": " +
+         (w ? helfem::exl_plan_json(w->plan) : std::string("null")) + "}";
 }
 
 }  // namespace hfg

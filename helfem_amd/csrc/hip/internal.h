@@ -78,6 +78,9 @@ bool exchange_lowrank_dev(hfg_ctx *ctx, hfg_dev_tables *t, const double *dP, dou
 // nP sets of occupied columns as exchange_dev's Lknown, or null
 void exchange_batch_dev(hfg_ctx *ctx, hfg_basis *basis, int64_t nP, const double *dP, double *dK, ExTables which = ExTables::coulomb,
                         const double *dC = nullptr, const int64_t *nocc = nullptr, int64_t ldc = 0);  // exchange_lr.hip
+// what the last single and batched low-rank builds on a table set took (host/exl_plan.h), as JSON; a set that is not there
+// or has not built yet gives null records
+std::string exl_last_plan_json(hfg_basis *basis, ExTables which);  // exchange_lr.hip
 
 // exchange_mix.hip
 constexpr double EXL_PAIR_MAX_BYTES = 32e9;  // largest pair table the low-rank path takes (exchange_lowrank_dev) and the mixed set builds

@@ -647,6 +647,15 @@ int hfg_profile_names(hfg_ctx *ctx, char *buf, size_t cap);
  * current value in this process, "once" (read when the process first uses a switch) or "live" (read at every use),
  * meaning.  Needs no device. */
 int hfg_tuning_table(char *buf, size_t cap);
+/* What the last low-rank exchange builds on a table set of the basis took ("coulomb": the set of hfg_exchange, "screened":
+ * of hfg_rs_exchange, "mix": of hfg_mix_exchange), as JSON text: {"single": record, "batch": record}, the record of
+ * hfg_exchange and its kin and of the last chunk of the batched entries; null for a build that has not run.  A record
+ * holds NLM, A, Ntab, E, p, the shells per run of equal m, the ranks of the factor groups (or of the chunk's members), per
+ * group or member whether its cross-element products were split over K, the kernels ("alpha", "rb"), whether the cross
+ * products go by blocks of equal m, the tiles and launchers of the cross products and of the element GEMM, the task
+ * counts, the largest M and N of a cross task, the longest pair list, and "declined" when the build handed the density to
+ * the general kernels.  The host fills it while it builds its task lists; nothing is read from the device.  Tests only. */
+int hfg_exl_last_plan(hfg_basis *basis, const char *which, char *buf, size_t cap);
 
 /* Atomic SCF, restricted closed shell or unrestricted (driver loop of src/atomic/main.cpp:760-1005); out as for hfg_scf_diatomic */
 int hfg_scf_atomic(hfg_ctx *ctx, int Z, int Q, int lmax, int mmax, int nelem, int nnodes, int nquad, double Rmax,
