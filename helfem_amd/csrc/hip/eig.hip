@@ -653,7 +653,6 @@ __global__ __launch_bounds__(64) void k_bt_T(EigBatch b, double *const *__restri
 }
 
 struct EigWork : Workspace {
-  GemmHow full_how;  // how this batch's full products are launched (split2: two half-K workgroups per tile)
   std::vector<int64_t> asm_rows;  // eig_assemble_dev: the index list whose device copy is asm_rows_dev
   DevBuf<long long> asm_rows_dev;
   bool folded = false;      // the last batch formed Y = (X Q)^T beside the divide-and-conquer stage (bt_wy_fold_x)
@@ -721,16 +720,20 @@ __global__ void k_copy_slices(CopySlices c) {
   const int q = blockIdx.y;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < c.n[q]; i += gridDim.x * blockDim.x) c.dst[q][i] = c.src[q][i];
 }
-static void copy_slices(hipStream_t s, const std::vector<const double *> &src, const std::vector<double *> &dst, const std::vector<int> &n) {
-  for (size_t q0 = 0; q0 < src.size(); q0 += 16) {
+/// The eigenvalues of `count` blocks to where they are read next: src(q), dst(q) and n(q) give block q's vector, its place
+/// and its length.  The one builder of the copy lists: the direct path, the block slots and eig_assemble_dev differ in
+/// their rules only.
+template <class Src, class Dst, class Len>
+static void publish_values(hipStream_t s, int count, Src src, Dst dst, Len n) {
+  for (int q0 = 0; q0 < count; q0 += 16) {
     CopySlices c{};
-    const int m = (int)std::min<size_t>(16, src.size() - q0);
+    const int m = std::min(16, count - q0);
     int nmax = 0;
     for (int q = 0; q < m; q++) {
-      c.src[q] = src[q0 + q];
-      c.dst[q] = dst[q0 + q];
-      c.n[q] = n[q0 + q];
-      nmax = std::max(nmax, n[q0 + q]);
+      c.src[q] = src(q0 + q);
+      c.dst[q] = dst(q0 + q);
+      c.n[q] = n(q0 + q);
+      nmax = std::max(nmax, c.n[q]);
     }
     if (nmax > 0) hipLaunchKernelGGL(k_copy_slices, dim3((nmax + 255) / 256, m), dim3(256), 0, s, c);
   }
@@ -1264,49 +1267,90 @@ void eig_gsym_dev(hfg_ctx *ctx, int N, int n, const double *dF, const double *dS
 // offset nmax*nmax]; slots of blocks owned by other ranks are zeroed so that a sum all-reduce over ranks
 // completes the buffer.
 size_t eig_block_buf_size(int nblk, const int64_t *blk_ptr) {
-  size_t nmax = 0;
-  for (int ib = 0; ib < nblk; ib++) nmax = std::max<size_t>(nmax, blk_ptr[ib + 1] - blk_ptr[ib]);
+  const size_t nmax = helfem::eig_block_nmax(nblk, blk_ptr);
   return (size_t)nblk * (nmax * nmax + nmax);
 }
+int64_t eig_sel_count(int nblk, const int64_t *blk_ptr, int64_t nev) { return helfem::eig_sel_count(nblk, blk_ptr, nev); }
 
-// nF Fock matrices at once (the two spins of an unrestricted iteration): their blocks join ONE batch -- the
-// tridiagonalisation is a chain of dependent launches whose length does not depend on the number of blocks in it, so two
-// spins cost about what one costs
-static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
-                                 const int64_t *blk_idx, double *const *dBlockBufs, int nev = 0, double *const *dEs = nullptr,
-                                 double *const *dCs = nullptr);
-static int eig_num_cus(hfg_ctx *ctx) {
-  static const int ncu = [&] {  // once per process, under the guard of the static's initialisation
-    hipDeviceProp_t prop;
-    return (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }();
-  return ncu;
+/// the switches of the product rules (host/eig_plan.h): this file reads them here and nowhere else
+static helfem::EigSwitches eig_switches() {
+  return {tuning().gemm_tile, tuning().gemm_splitk, tuning().gemm_rect, tuning().mfma_4x4x4};
 }
-void eig_blocks_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
-                    const int64_t *blk_idx, double *dBlockBuf) {
-  eig_blocks_multi_dev(ctx, N, 1, &dF, dS, nblk, blk_ptr, blk_idx, &dBlockBuf);
-}
-/// nev > 0: the lowest min(nev, n_b) eigenpairs of every block only; slot ib then holds that many columns (ld n_b) and values
-/// dEs, dCs (the one-call entries on one device, nF * nblk <= MAXB; dBlockBufs is not used): no block slots.  The K =
-/// eig_sel_count eigenvalues of matrix f are ranked as soon as they are final and go to dEs[f]; the last product stores
-/// element (i, j) of block ib at row blk_idx[blk_ptr[ib] + i], column rank[koff[ib] + j] of dCs[f] (N x K, zeroed here),
-/// with the tiles and the k order of the slot path, so that E and C are bit for bit those of eig_assemble_dev.
-static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
-                                 const int64_t *blk_idx, double *const *dBlockBufs, int nev, double *const *dEs, double *const *dCs) {
-  EigWork &w = work_for(ctx);
+
+// ---- the blocked driver, stage by stage (eig_blocks_multi_dev below calls them in this order) -------------------------------
+/// Column supports of the symmetry blocks of a block-structured Sinvh (scf_helpers.cpp:150-157): cols[blk_ptr[ib] ...] = the
+/// columns with support on block ib's rows, ascending.  Uploads blk_idx to drows (N values on the device) on the way; the
+/// stream is drained on return.
+static void block_supports(hfg_ctx *ctx, int N, const double *dS, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
+                           int64_t *drows, DevBuf<int> &flag, std::vector<int64_t> &cols) {
   hipStream_t s = ctx->stream;
-  const bool direct = dEs != nullptr;
-  if (direct && (ctx->shard_n != 1 || nF * nblk > MAXB)) throw std::logic_error("eig_blocks_multi_dev: direct path needs one rank and one batch\n");
-  if (blk_ptr[nblk] != N) throw std::logic_error("Symmetry mismatch in eig_gsym_sub\n");
-  // block row indices on the device
-  DevBuf<double> &idxbuf = w.idx;  // raw storage for int64 rows + cols
-  idxbuf.resize(2 * (size_t)N + 16);
-  int64_t *drows = (int64_t *)idxbuf.p;
-  int64_t *dcols = drows + N;
-  for (int ib = 0; ib < nblk; ib++)
-    if (blk_ptr[ib + 1] == blk_ptr[ib]) throw std::logic_error("eig_gsym_sub: empty symmetry block\n");
-  // column support of every block (scf_helpers.cpp:150-157).  It depends on Sinvh and the blocks only: when the caller
-  // has declared Sinvh fixed (hfg_ctx_fix_sinvh) the lists of the previous call are still on the device
+  HFG_HIP_CHECK(hipMemcpyAsync(drows, blk_idx, sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
+  flag.resize((size_t)N * nblk + 8);
+  for (int ib = 0; ib < nblk; ib++) {
+    int n = (int)(blk_ptr[ib + 1] - blk_ptr[ib]);
+    hipLaunchKernelGGL(k_col_support, dim3(N), dim3(256), 0, s, dS, N, drows + blk_ptr[ib], n, flag.p + (size_t)ib * N);
+  }
+  std::vector<int> hflag((size_t)N * nblk);
+  HFG_HIP_CHECK(hipMemcpyAsync(hflag.data(), flag.p, sizeof(int) * hflag.size(), hipMemcpyDeviceToHost, s));
+  HFG_HIP_CHECK(hipStreamSynchronize(s));
+  cols.clear();
+  for (int ib = 0; ib < nblk; ib++) {
+    int cnt = 0;
+    for (int c = 0; c < N; c++)
+      if (hflag[(size_t)ib * N + c]) {
+        cols.push_back(c);
+        cnt++;
+      }
+    if (cnt != (int)(blk_ptr[ib + 1] - blk_ptr[ib]))
+      throw std::logic_error("eig_gsym_sub: Sinvh is not block structured (columns with support != block size)\n");
+  }
+}
+
+/// The declared pattern of F applied to these blocks (EigWork::band_*, eig_band_plan.h), and the lists' device copies
+static void band_lists(hfg_ctx *ctx, EigWork &w, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx) {
+  hipStream_t s = ctx->stream;
+  w.band_rows.resize(N);
+  w.band_pos.resize(N);
+  std::vector<int> nd, ks, toff;
+  int64_t nbig = 0;
+  for (int ib = 0; ib < nblk; ib++) {
+    const int64_t o = blk_ptr[ib], n = blk_ptr[ib + 1] - o;
+    nbig = std::max(nbig, n);
+    nd.resize(n);
+    for (int64_t i = 0; i < n; i++) {
+      if (blk_idx[o + i] < 0 || blk_idx[o + i] >= N) throw std::logic_error("eig_gsym_sub: block index out of range\n");
+      nd[i] = ctx->band_node[blk_idx[o + i]];
+    }
+    helfem::eig_band_order(n, nd.data(), w.band_pos.data() + o);
+    for (int64_t i = 0; i < n; i++) w.band_rows[o + i] = blk_idx[o + w.band_pos[o + i]];
+    if (helfem::eig_band_plan(n, nd.data(), w.band_pos.data() + o, ctx->band_pm, ctx->band_E, ks, toff)) w.band_any = true;
+    for (size_t t = 0; t + 1 < toff.size(); t++) w.band_koff.push_back((int)w.band_ks.size() + toff[t + 1]);
+    w.band_ks.insert(w.band_ks.end(), ks.begin(), ks.end());
+    w.band_toff.push_back((int)w.band_koff.size() - 1);
+  }
+  std::vector<int> iota(nbig);
+  for (int64_t i = 0; i < nbig; i++) iota[i] = (int)i;
+  w.band_rows_dev.resize(N);
+  w.band_pos_dev.resize(N);
+  w.band_ks_dev.resize(w.band_ks.size() + 1);
+  w.band_iota_dev.resize(nbig);
+  HFG_HIP_CHECK(hipMemcpyAsync(w.band_rows_dev.p, w.band_rows.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
+  HFG_HIP_CHECK(hipMemcpyAsync(w.band_pos_dev.p, w.band_pos.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
+  HFG_HIP_CHECK(hipMemcpyAsync(w.band_ks_dev.p, w.band_ks.data(), sizeof(int) * w.band_ks.size(), hipMemcpyHostToDevice, s));
+  HFG_HIP_CHECK(hipMemcpyAsync(w.band_iota_dev.p, iota.data(), sizeof(int) * nbig, hipMemcpyHostToDevice, s));
+  HFG_HIP_CHECK(hipStreamSynchronize(s));  // iota lives on this stack frame
+}
+
+/// The blocks' row and column index lists on the device (w.idx): drows = blk_idx, dcols = the column support of every block.
+/// The supports depend on Sinvh and the blocks only: when the caller has declared Sinvh fixed (hfg_ctx_fix_sinvh) the lists
+/// of the previous call, the band lists derived with them and the X cache are still good.
+struct BlockLists {
+  const int64_t *drows, *dcols;
+};
+static BlockLists block_lists(hfg_ctx *ctx, EigWork &w, int N, const double *dS, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx) {
+  hipStream_t s = ctx->stream;
+  w.idx.resize(2 * (size_t)N + 16);
+  int64_t *drows = (int64_t *)w.idx.p, *dcols = drows + N;
   // the declared pattern of F: valid beside the declared Sinvh only, ignored under HELFEM_EIG_BAND=0 (read at every call)
   const bool want_band = ctx->fixed_sinvh && ctx->fixed_sinvh == dS && ctx->band_state == 1 && ctx->band_node.size() == (size_t)N &&
                          helfem::tuning_live().eig_band;
@@ -1314,338 +1358,336 @@ static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *cons
                       w.sup_N == N && want_band == !w.band_rows.empty() &&
                       w.sup_ptr.size() == (size_t)nblk + 1 && std::equal(w.sup_ptr.begin(), w.sup_ptr.end(), blk_ptr) &&
                       w.sup_idx.size() == (size_t)N && std::equal(w.sup_idx.begin(), w.sup_idx.end(), blk_idx);
-  if (!cached) {
-    w.sup_S = nullptr;
-    w.xc_have.clear();  // the gathered X blocks belong to the lists that go
-    HFG_HIP_CHECK(hipStreamSynchronize(s));  // the band lists may still be the source of an earlier copy
-    w.band_rows.clear();
-    w.band_pos.clear();
-    w.band_ks.clear();
-    w.band_koff.assign(1, 0);
-    w.band_toff.assign(1, 0);
-    w.band_any = false;
-    if (want_band) {
-      w.band_rows.resize(N);
-      w.band_pos.resize(N);
-      std::vector<int> nd, ks, toff;
-      int64_t nbig = 0;
-      for (int ib = 0; ib < nblk; ib++) {
-        const int64_t o = blk_ptr[ib], n = blk_ptr[ib + 1] - o;
-        nbig = std::max(nbig, n);
-        nd.resize(n);
-        for (int64_t i = 0; i < n; i++) {
-          if (blk_idx[o + i] < 0 || blk_idx[o + i] >= N) throw std::logic_error("eig_gsym_sub: block index out of range\n");
-          nd[i] = ctx->band_node[blk_idx[o + i]];
-        }
-        helfem::eig_band_order(n, nd.data(), w.band_pos.data() + o);
-        for (int64_t i = 0; i < n; i++) w.band_rows[o + i] = blk_idx[o + w.band_pos[o + i]];
-        if (helfem::eig_band_plan(n, nd.data(), w.band_pos.data() + o, ctx->band_pm, ctx->band_E, ks, toff)) w.band_any = true;
-        for (size_t t = 0; t + 1 < toff.size(); t++) w.band_koff.push_back((int)w.band_ks.size() + toff[t + 1]);
-        w.band_ks.insert(w.band_ks.end(), ks.begin(), ks.end());
-        w.band_toff.push_back((int)w.band_koff.size() - 1);
-      }
-      std::vector<int> iota(nbig);
-      for (int64_t i = 0; i < nbig; i++) iota[i] = (int)i;
-      w.band_rows_dev.resize(N);
-      w.band_pos_dev.resize(N);
-      w.band_ks_dev.resize(w.band_ks.size() + 1);
-      w.band_iota_dev.resize(nbig);
-      HFG_HIP_CHECK(hipMemcpyAsync(w.band_rows_dev.p, w.band_rows.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
-      HFG_HIP_CHECK(hipMemcpyAsync(w.band_pos_dev.p, w.band_pos.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
-      HFG_HIP_CHECK(hipMemcpyAsync(w.band_ks_dev.p, w.band_ks.data(), sizeof(int) * w.band_ks.size(), hipMemcpyHostToDevice, s));
-      HFG_HIP_CHECK(hipMemcpyAsync(w.band_iota_dev.p, iota.data(), sizeof(int) * nbig, hipMemcpyHostToDevice, s));
-      HFG_HIP_CHECK(hipStreamSynchronize(s));  // iota lives on this stack frame
-    }
-    HFG_HIP_CHECK(hipMemcpyAsync(drows, blk_idx, sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
-    DevBuf<int> &flag = w.ibuf2;
-    flag.resize((size_t)N * nblk + 8);
-    for (int ib = 0; ib < nblk; ib++) {
-      int n = (int)(blk_ptr[ib + 1] - blk_ptr[ib]);
-      hipLaunchKernelGGL(k_col_support, dim3(N), dim3(256), 0, s, dS, N, drows + blk_ptr[ib], n, flag.p + (size_t)ib * N);
-    }
-    std::vector<int> hflag((size_t)N * nblk);
-    HFG_HIP_CHECK(hipMemcpyAsync(hflag.data(), flag.p, sizeof(int) * hflag.size(), hipMemcpyDeviceToHost, s));
-    HFG_HIP_CHECK(hipStreamSynchronize(s));
-    std::vector<int64_t> allcols;
-    for (int ib = 0; ib < nblk; ib++) {
-      int cnt = 0;
-      for (int c = 0; c < N; c++)
-        if (hflag[(size_t)ib * N + c]) {
-          allcols.push_back(c);
-          cnt++;
-        }
-      if (cnt != (int)(blk_ptr[ib + 1] - blk_ptr[ib]))
-        throw std::logic_error("eig_gsym_sub: Sinvh is not block structured (columns with support != block size)\n");
-    }
-    HFG_HIP_CHECK(hipMemcpyAsync(dcols, allcols.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
-    HFG_HIP_CHECK(hipStreamSynchronize(s));  // allcols lives on this stack frame
-    if (ctx->fixed_sinvh == dS) {
-      w.sup_S = dS;
-      w.sup_gen = ctx->fixed_gen;
-      w.sup_N = N;
-      w.sup_ptr.assign(blk_ptr, blk_ptr + nblk + 1);
-      w.sup_idx.assign(blk_idx, blk_idx + N);
+  if (cached) return {drows, dcols};
+  w.sup_S = nullptr;
+  w.xc_have.clear();  // the gathered X blocks belong to the lists that go
+  HFG_HIP_CHECK(hipStreamSynchronize(s));  // the band lists may still be the source of an earlier copy
+  w.band_rows.clear();
+  w.band_pos.clear();
+  w.band_ks.clear();
+  w.band_koff.assign(1, 0);
+  w.band_toff.assign(1, 0);
+  w.band_any = false;
+  if (want_band) band_lists(ctx, w, N, nblk, blk_ptr, blk_idx);
+  std::vector<int64_t> allcols;
+  block_supports(ctx, N, dS, nblk, blk_ptr, blk_idx, drows, w.ibuf2, allcols);
+  HFG_HIP_CHECK(hipMemcpyAsync(dcols, allcols.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
+  HFG_HIP_CHECK(hipStreamSynchronize(s));  // allcols lives on this stack frame
+  if (ctx->fixed_sinvh == dS) {
+    w.sup_S = dS;
+    w.sup_gen = ctx->fixed_gen;
+    w.sup_N = N;
+    w.sup_ptr.assign(blk_ptr, blk_ptr + nblk + 1);
+    w.sup_idx.assign(blk_idx, blk_idx + N);
+  }
+  return {drows, dcols};
+}
+
+/// One call of the driver: its arguments and what is derived from them once
+struct BlocksCall {
+  hfg_ctx *ctx;
+  EigWork &w;
+  int N, nF, nblk;
+  const int64_t *blk_ptr;
+  const double *const *dFs;
+  const double *dS;
+  double *const *dBlockBufs;  // the slot path's buffers, one per matrix
+  int nev;
+  double *const *dEs, *const *dCs;  // the direct path's outputs, one per matrix
+  bool direct;
+  BlockLists lists;
+  size_t nmax, slot;    // order of the largest block, doubles of a block slot
+  bool keep_x;          // X of every block stays in w.Xc, block ib at xoff[ib]
+  const size_t *xoff;
+  const int64_t *koff;  // block ib's values start at koff[ib] among the K of a matrix (eig_value_offsets)
+  int K;
+  int order(int ib) const { return (int)(blk_ptr[ib + 1] - blk_ptr[ib]); }
+  // batch member k: its gathered F, its F X, its X when that is not cached
+  double *Fk(int k) const { return ctx->ws[5].p + (size_t)k * nmax * nmax; }
+  double *Tk(int k) const { return ctx->ws[0].p + (size_t)k * nmax * nmax; }
+  double *Xk(int k) const { return ctx->ws[4].p + (size_t)k * nmax * nmax; }
+  // direct: ranks and eigenvalues of matrix f
+  int *rank(int f) const { return w.ibuf1.p + (size_t)f * (N + 8); }
+  double *Etmp(int f) const { return ctx->ws[3].p + (size_t)f * N; }
+};
+
+/// One batch: at most MAXB (matrix, block) pairs, whose products and decompositions share their launches
+struct EigChunk {
+  int nb = 0, nm = 0;         // pairs, largest order among them
+  int ib[MAXB], f[MAXB];      // block and matrix of pair k
+  int ns[MAXB], nevs[MAXB];   // order, eigenpairs wanted
+  const double *Xptr[MAXB];   // X = Sinvh(rows, cols) of the block
+  helfem::EigProductPlan plan;
+  helfem::EigLastProduct last;
+  double *slot(const BlocksCall &c, int k) const { return c.dBlockBufs[f[k]] + (size_t)ib[k] * c.slot; }
+  const double *values(const BlocksCall &c, int k) const { return c.nev > 0 ? c.w.Ws[k].p : c.w.d[k].p; }  // final behind the solve
+};
+/// items: nb entries matrix * nblk + block.  Sizes the batch's matrices in the workspace as well.
+static EigChunk fill_chunk(const BlocksCall &c, const int *items, int nb) {
+  EigWork &w = c.w;
+  EigChunk b;
+  b.nb = nb;
+  for (int k = 0; k < nb; k++) {
+    const int ib = items[k] % c.nblk, n = c.order(ib);
+    b.ib[k] = ib;
+    b.f[k] = items[k] / c.nblk;
+    b.ns[k] = n;
+    b.nevs[k] = c.nev > 0 ? std::min(c.nev, n) : n;
+    b.nm = std::max(b.nm, n);
+    w.A[k].resize((size_t)n * n + 2);  // + 2: the sweep's 16-byte row pairs may straddle the last element
+    if (c.nev > 0) w.Zs[k].resize((size_t)n * b.nevs[k]);
+    else w.Z[k].resize((size_t)n * n);
+    w.Y[k].resize((size_t)n * n);
+    b.Xptr[k] = c.keep_x ? w.Xc.p + c.xoff[ib] : c.Xk(k);
+  }
+  return b;
+}
+
+/// The three products of every block (F X, X^T (F X), X Z) go through one task-list launch each, so that the blocks fill
+/// the chip together.  [k]: F X, [nb + k]: X^T (F X), [2 nb + k]: X Z, [3 nb + k]: the last product when X Q was folded
+/// (eig_sym_batch): (X Q) Z = Y^T Z
+static std::vector<GemmTask> build_tasks(const BlocksCall &c, const EigChunk &b) {
+  EigWork &w = c.w;
+  const int nb = b.nb;
+  std::vector<GemmTask> gt(4 * (size_t)nb);
+  for (int k = 0; k < nb; k++) {
+    const int ib = b.ib[k], n = b.ns[k];
+    double *Xb = const_cast<double *>(b.Xptr[k]);
+    GemmTask g;
+    g.M = g.N = g.K = n;
+    g.lda = g.ldb = g.ldc = n;
+    g.A = c.Fk(k);
+    g.B = Xb;
+    g.C = c.Tk(k);
+    gt[k] = g;
+    g.A = Xb;
+    g.tA = 1;
+    g.B = c.Tk(k);
+    g.C = w.A[k].p;
+    g.sym = 1;  // X^T (F X): the lower tiles are computed, the upper ones mirrored
+    gt[nb + k] = g;
+    g.sym = 0;
+    g.tA = 0;
+    g.A = Xb;
+    g.B = c.nev > 0 ? w.Zs[k].p : w.Z[k].p;
+    g.N = b.nevs[k];
+    if (c.direct) {
+      g.C = c.dCs[b.f[k]];
+      g.ldc = c.N;
+      g.rmap = c.lists.drows + c.blk_ptr[ib];
+      g.cmap = c.rank(b.f[k]) + c.koff[ib];
+    } else
+      g.C = b.slot(c, k);
+    gt[2 * nb + k] = g;
+    g.A = w.Y[k].p;
+    g.tA = 1;
+    gt[3 * nb + k] = g;
+  }
+  return gt;
+}
+
+/// F X under the declared pattern: one task per 64 rows of F in radial-major ROW order (the gather of reduce_stage), its k
+/// loop over the tile's step list alone, the rows stored at their places in the caller's order (rmap).  Columns of F, X and T
+/// are in the caller's order, so T is bit for bit the dense product.  Once one block of the batch takes row tasks every
+/// block does (a dense one with all steps), and the grid stays that of a 64-row product.  Longest lists first: the launch
+/// hands out the tasks in order, the short ones fill the tail.  Empty: no pattern in force.
+static std::vector<GemmTask> build_row_tasks(const BlocksCall &c, const EigChunk &b, const std::vector<GemmTask> &gt) {
+  const EigWork &w = c.w;
+  std::vector<GemmTask> fx;
+  if (!(w.band_any && !w.band_rows.empty())) return fx;
+  for (int k = 0; k < b.nb; k++) {
+    const int ib = b.ib[k];
+    const int n = b.ns[k], nt = w.band_toff[ib + 1] - w.band_toff[ib];
+    for (int t = 0; t < nt; t++) {
+      const int i0 = t * helfem::EIG_BAND_TILE, q = w.band_toff[ib] + t;
+      GemmTask g = gt[k];
+      g.A = gt[k].A + i0;
+      g.M = std::min(helfem::EIG_BAND_TILE, n - i0);
+      g.rmap = (const int64_t *)w.band_pos_dev.p + c.blk_ptr[ib] + i0;
+      g.cmap = w.band_iota_dev.p;
+      g.kstart = w.band_ks_dev.p + w.band_koff[q];
+      g.nk = w.band_koff[q + 1] - w.band_koff[q];
+      fx.push_back(g);
     }
   }
+  std::stable_sort(fx.begin(), fx.end(), [](const GemmTask &a, const GemmTask &b) { return a.nk > b.nk; });
+  return fx;
+}
 
-  size_t nmax = 0;
-  for (int ib = 0; ib < nblk; ib++) nmax = std::max<size_t>(nmax, blk_ptr[ib + 1] - blk_ptr[ib]);
-  const size_t slot = nmax * nmax + nmax;
+/// Forth = X^T (F X) of every pair of the batch into w.A: the gathers, the zeroing that the plan asks for, the two task-list
+/// launches and the mirror.  nfx: row tasks in w.fxtasks.
+static void reduce_stage(const BlocksCall &c, const EigChunk &b, int nfx) {
+  hfg_ctx *ctx = c.ctx;
+  EigWork &w = c.w;
+  hipStream_t s = ctx->stream;
+  const helfem::EigProductPlan &p = b.plan;
+  const int nb = b.nb, nm = b.nm;
+  const int64_t *drows = c.lists.drows, *dcols = c.lists.dcols;
+  ProfScope ps(ctx, "eig_reduce");
+  for (int k = 0; k < nb; k++) {
+    const int ib = b.ib[k], n = b.ns[k];
+    const double *dF = c.dFs[b.f[k]];
+    double *Fk = c.Fk(k);
+    if (!(c.keep_x && w.xc_have[ib]))
+      hipLaunchKernelGGL(k_gather_block, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, c.dS, c.N, drows + c.blk_ptr[ib],
+                         dcols + c.blk_ptr[ib], n, Fk, const_cast<double *>(b.Xptr[k]));
+    else if (!p.band_fx)
+      hipLaunchKernelGGL(k_gather_f, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, c.N, drows + c.blk_ptr[ib], n, Fk);
+    if (p.band_fx)  // the rows of F radial-major, its columns in the caller's order
+      hipLaunchKernelGGL(k_gather_f2, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, c.N, (const int64_t *)w.band_rows_dev.p + c.blk_ptr[ib],
+                         drows + c.blk_ptr[ib], n, Fk);
+    if (c.keep_x) w.xc_have[ib] = 1;
+  }
+  ProfScope pp3(ctx, "eig_products");  // the N^3 products alone (bench.py: MFMA fraction of the tile engine)
+  if (p.zero_fx)
+    for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(c.Tk(k), 0, sizeof(double) * (size_t)b.ns[k] * b.ns[k], s));
+  if (p.band_fx) {
+    GemmHow how;
+    how.tile = GemmTile::T64;
+    how.scatter = how.klist = true;
+    gemm_tasklist_dev(ctx, w.fxtasks.p, nfx, helfem::EIG_BAND_TILE, nm, how);
+  } else
+    gemm_tasklist_dev(ctx, w.gtasks.p, nb, nm, nm, p.full);
+  if (p.zero_low)
+    for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(w.A[k].p, 0, sizeof(double) * (size_t)b.ns[k] * b.ns[k], s));
+  gemm_tasklist_dev(ctx, w.gtasks.p + nb, nb, nm, nm, p.low);
+  gemm_mirror_lower_dev(ctx, w.gtasks.p + nb, nb, nm);  // the tridiagonalisation sweeps the full square
+}
+
+/// Direct path, the after_solve hook of eig_sym_batch: everything that needs the eigenvalues alone, on the main stream
+/// between the divide-and-conquer stage and the wait for X Q (the side stream ends after that stage: the main stream would
+/// idle there).  The values go to Etmp, are ranked and placed in dEs; C is zeroed ahead of the product that stores into it.
+static void publish_direct(const BlocksCall &c, const EigChunk &b) {
+  hfg_ctx *ctx = c.ctx;
+  EigWork &w = c.w;
+  hipStream_t s = ctx->stream;
+  if (w.used_dc) {  // the status word goes home now; the host waits for this point only
+    if (!w.h_status) HFG_HIP_CHECK(hipHostMalloc((void **)&w.h_status, sizeof(int), hipHostMallocDefault));
+    if (!w.status_ev) HFG_HIP_CHECK(hipEventCreateWithFlags(&w.status_ev, hipEventDisableTiming));
+    HFG_HIP_CHECK(hipMemcpyAsync(w.h_status, dc_status_word(ctx), sizeof(int), hipMemcpyDeviceToHost, s));
+    HFG_HIP_CHECK(hipEventRecord(w.status_ev, s));
+  }
+  ProfScope ps(ctx, "scatter");
+  publish_values(
+      s, b.nb, [&](int k) { return b.values(c, k); }, [&](int k) { return c.Etmp(b.f[k]) + c.koff[b.ib[k]]; },
+      [&](int k) { return b.nevs[k]; });
+  for (int f = 0; f < c.nF; f++) {
+    launch_rank(ctx, c.Etmp(f), c.K, c.rank(f));
+    hipLaunchKernelGGL(k_place_values, dim3((c.K + 255) / 256), dim3(256), 0, s, c.Etmp(f), c.K, c.rank(f), c.dEs[f]);
+    if (b.last.zero_out)  // (stream order: ahead of the product, split K adds into it)
+      HFG_HIP_CHECK(hipMemsetAsync(c.dCs[f], 0, sizeof(double) * (size_t)c.N * c.K, s));
+  }
+}
+
+/// Slot path: the eigenvalues are final, their copy into the slots goes ahead of the last product, not behind it
+static void publish_slots(const BlocksCall &c, const EigChunk &b) {
+  hipStream_t s = c.ctx->stream;
+  if (b.last.zero_out && c.ctx->shard_n == 1)  // (more ranks: the whole buffer was zeroed at the start of the call)
+    for (int k = 0; k < b.nb; k++) HFG_HIP_CHECK(hipMemsetAsync(b.slot(c, k), 0, sizeof(double) * (size_t)b.ns[k] * b.ns[k], s));
+  publish_values(
+      s, b.nb, [&](int k) { return b.values(c, k); }, [&](int k) { return b.slot(c, k) + c.nmax * c.nmax; },
+      [&](int k) { return b.nevs[k]; });
+}
+
+/// C = X Z, or Y^T Z when X Q was folded: into the slots, or through the maps straight into C
+static void last_product(const BlocksCall &c, const EigChunk &b) {
+  ProfScope pp3(c.ctx, "eig_products");
+  const GemmTask *last = c.w.gtasks.p + (c.w.folded ? 3 : 2) * (size_t)b.nb;
+  gemm_tasklist_dev(c.ctx, last, b.nb, b.nm, c.nev > 0 ? *std::max_element(b.nevs, b.nevs + b.nb) : b.nm, b.last.how);
+}
+
+static void wait_status(const BlocksCall &c, int nb) {
+  EigWork &w = c.w;
+  if (c.direct && w.used_dc) {
+    // everything is queued: the one host wait, for the status word behind the divide-and-conquer stage (the persistent
+    // tridiagonalisation's words, written before it, are home by then too)
+    HFG_HIP_CHECK(hipEventSynchronize(w.status_ev));
+    if (*w.h_status != 0) throw std::logic_error("Eigendecomposition failed!\n");
+    trdp_check_status(c.ctx);
+  } else
+    check_status(c.ctx, w, nb);
+}
+
+// nF Fock matrices at once (the two spins of an unrestricted iteration): their blocks join ONE batch -- the
+// tridiagonalisation is a chain of dependent launches whose length does not depend on the number of blocks in it, so two
+// spins cost about what one costs
+/// nev > 0: the lowest min(nev, n_b) eigenpairs of every block only; slot ib then holds that many columns (ld n_b) and values
+/// dEs, dCs (the one-call entries on one device, nF * nblk <= MAXB; dBlockBufs is not used): no block slots.  The K =
+/// eig_sel_count eigenvalues of matrix f are ranked as soon as they are final and go to dEs[f]; the last product stores
+/// element (i, j) of block ib at row blk_idx[blk_ptr[ib] + i], column rank[koff[ib] + j] of dCs[f] (N x K, zeroed here),
+/// with the tiles and the k order of the slot path, so that E and C are bit for bit those of eig_assemble_dev.
+static void eig_blocks_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
+                                 const int64_t *blk_idx, double *const *dBlockBufs, int nev = 0, double *const *dEs = nullptr,
+                                 double *const *dCs = nullptr) {
+  EigWork &w = work_for(ctx);
+  hipStream_t s = ctx->stream;
+  const bool direct = dEs != nullptr;
+  if (direct && (ctx->shard_n != 1 || nF * nblk > MAXB)) throw std::logic_error("eig_blocks_multi_dev: direct path needs one rank and one batch\n");
+  if (blk_ptr[nblk] != N) throw std::logic_error("Symmetry mismatch in eig_gsym_sub\n");
+  for (int ib = 0; ib < nblk; ib++)
+    if (blk_ptr[ib + 1] == blk_ptr[ib]) throw std::logic_error("eig_gsym_sub: empty symmetry block\n");
+  const BlockLists lists = block_lists(ctx, w, N, dS, nblk, blk_ptr, blk_idx);
+
+  const size_t nmax = helfem::eig_block_nmax(nblk, blk_ptr), slot = nmax * nmax + nmax;
   // the slots of the other ranks' blocks are zero so that a sum over the ranks completes the buffer.  One rank writes every
   // word that is read afterwards (eig_assemble_dev: n x nev columns and nev values per slot; the collectives of
   // helfem_amd.parallel move whole buffers or whole slots and read nothing themselves), so nothing is zeroed for it --
-  // except the products' own outputs where two half-K workgroups add into them (below).
+  // except the products' own outputs where two half-K workgroups add into them (eig_product_plan, eig_last_product).
   if (!direct && ctx->shard_n > 1)
     for (int f = 0; f < nF; f++) HFG_HIP_CHECK(hipMemsetAsync(dBlockBufs[f], 0, sizeof(double) * slot * nblk, s));
   // X = Sinvh(rows, cols) of every block, kept across calls while the lists above are (hfg_ctx_fix_sinvh): w.Xc
   const bool keep_x = w.sup_S == dS && w.sup_S != nullptr;
   std::vector<size_t> xoff(nblk + 1, 0);
   for (int ib = 0; ib < nblk; ib++) xoff[ib + 1] = xoff[ib] + (size_t)(blk_ptr[ib + 1] - blk_ptr[ib]) * (size_t)(blk_ptr[ib + 1] - blk_ptr[ib]);
-  if (keep_x) {
-    if (w.xc_have.size() != (size_t)nblk || w.Xc.n < xoff[nblk]) {
-      w.Xc.resize(xoff[nblk]);
-      w.xc_have.assign(nblk, 0);
-    }
+  if (keep_x && (w.xc_have.size() != (size_t)nblk || w.Xc.n < xoff[nblk])) {
+    w.Xc.resize(xoff[nblk]);
+    w.xc_have.assign(nblk, 0);
   }
-  // direct: ranks and eigenvalues of matrix f at rank.p + f (N + 8), Etmp.p + f N; block ib's values start at koff[ib]
-  std::vector<int64_t> koff(nblk + 1, 0);
-  for (int ib = 0; ib < nblk; ib++) {
-    const int64_t n = blk_ptr[ib + 1] - blk_ptr[ib];
-    koff[ib + 1] = koff[ib] + (nev > 0 ? std::min<int64_t>(nev, n) : n);
-  }
-  const int K = (int)koff[nblk];
-  DevBuf<int> &rank = w.ibuf1;
-  DevBuf<double> &Etmp = ctx->ws[3];
+  // direct: ranks and eigenvalues of matrix f at ibuf1 + f (N + 8), ws[3] + f N; block ib's values start at koff[ib]
+  std::vector<int64_t> koff(nblk + 1);
+  const int K = (int)helfem::eig_value_offsets(nblk, blk_ptr, nev, koff.data());
   if (direct) {
-    rank.resize((size_t)nF * (N + 8));
-    Etmp.resize((size_t)nF * N);
+    w.ibuf1.resize((size_t)nF * (N + 8));
+    ctx->ws[3].resize((size_t)nF * N);
   }
-
   // work items: (matrix, block) pairs; `mine` holds matrix * nblk + block
   std::vector<int> mine;
   for (int f = 0; f < nF; f++)
     for (int ib = 0; ib < nblk; ib++)
       if (ib % ctx->shard_n == ctx->shard_rank) mine.push_back(f * nblk + ib);
-  DevBuf<double> &Fb = ctx->ws[5];
-  DevBuf<double> &T1 = ctx->ws[0];
-  DevBuf<double> &Xall = ctx->ws[4];
-  Fb.resize(nmax * nmax * MAXB);
-  T1.resize(nmax * nmax * MAXB);
-  Xall.resize(nmax * nmax * MAXB);
+  ctx->ws[5].resize(nmax * nmax * MAXB);
+  ctx->ws[0].resize(nmax * nmax * MAXB);
+  ctx->ws[4].resize(nmax * nmax * MAXB);
+  const BlocksCall c{ctx, w, N, nF, nblk, blk_ptr, dFs, dS, dBlockBufs, nev, dEs, dCs, direct, lists, nmax, slot, keep_x, xoff.data(), koff.data(), K};
+  const helfem::EigSwitches sw = eig_switches();
   for (size_t c0 = 0; c0 < mine.size(); c0 += MAXB) {
-    int nb = (int)std::min<size_t>(MAXB, mine.size() - c0);
-    std::vector<int> ns(nb), nevs(nb);
-    // the three products of every block (F X, X^T (F X), X Z) go through one task-list launch each, so that the
-    // blocks fill the chip together with 128 x 128 tiles
-    std::vector<GemmTask> gt(4 * (size_t)nb);  // [3 nb + k]: the last product when X Q was folded (eig_sym_batch): (X Q) Z = Y^T Z
-    const double *Xptr[MAXB];
-    int nm = 0;
-    for (int k = 0; k < nb; k++) {
-      const int ib = mine[c0 + k] % nblk;
-      double *dBlockBuf = direct ? nullptr : dBlockBufs[mine[c0 + k] / nblk];
-      int n = (int)(blk_ptr[ib + 1] - blk_ptr[ib]);
-      ns[k] = n;
-      nevs[k] = nev > 0 ? std::min(nev, n) : n;
-      nm = std::max(nm, n);
-      w.A[k].resize((size_t)n * n + 2);  // + 2: the sweep's 16-byte row pairs may straddle the last element
-      if (nev > 0) w.Zs[k].resize((size_t)n * nevs[k]);
-      else w.Z[k].resize((size_t)n * n);
-      w.Y[k].resize((size_t)n * n);
-      double *Xb = keep_x ? w.Xc.p + xoff[ib] : Xall.p + (size_t)k * nmax * nmax;
-      double *Fk = Fb.p + (size_t)k * nmax * nmax, *Tk = T1.p + (size_t)k * nmax * nmax;
-      Xptr[k] = Xb;
-      GemmTask g;
-      g.M = g.N = g.K = n;
-      g.lda = g.ldb = g.ldc = n;
-      g.A = Fk;
-      g.B = Xb;
-      g.C = Tk;
-      gt[k] = g;
-      g.A = Xb;
-      g.tA = 1;
-      g.B = Tk;
-      g.C = w.A[k].p;
-      g.sym = 1;  // X^T (F X): the lower tiles are computed, the upper ones mirrored
-      gt[nb + k] = g;
-      g.sym = 0;
-      g.tA = 0;
-      g.A = Xb;
-      g.B = nev > 0 ? w.Zs[k].p : w.Z[k].p;
-      g.N = nevs[k];
-      if (direct) {
-        const int f = mine[c0 + k] / nblk;
-        g.C = dCs[f];
-        g.ldc = N;
-        g.rmap = drows + blk_ptr[ib];
-        g.cmap = rank.p + (size_t)f * (N + 8) + koff[ib];
-      } else
-        g.C = dBlockBuf + (size_t)ib * slot;
-      gt[2 * nb + k] = g;
-      g.A = w.Y[k].p;
-      g.tA = 1;
-      gt[3 * nb + k] = g;
-    }
+    EigChunk b = fill_chunk(c, mine.data() + c0, (int)std::min<size_t>(MAXB, mine.size() - c0));
+    const std::vector<GemmTask> gt = build_tasks(c, b);
     upload_cached(w.gtasks, w.h_gtasks, gt, s);
-    // F X under the declared pattern: one task per 64 rows of F in radial-major ROW order (the gather below), its k loop
-    // over the tile's step list alone, the rows stored at their places in the caller's order (rmap).  Columns of F, X and T
-    // are in the caller's order, so T is bit for bit the dense product.  Once one block of the batch takes row tasks every
-    // block does (a dense one with all steps), and the grid stays that of a 64-row product.  Longest lists first: the launch
-    // hands out the tasks in order, the short ones fill the tail.
-    std::vector<GemmTask> fx;
-    if (w.band_any && !w.band_rows.empty()) {
-      for (int k = 0; k < nb; k++) {
-        const int ib = mine[c0 + k] % nblk;
-        const int n = ns[k], nt = w.band_toff[ib + 1] - w.band_toff[ib];
-        for (int t = 0; t < nt; t++) {
-          const int i0 = t * helfem::EIG_BAND_TILE, q = w.band_toff[ib] + t;
-          GemmTask g = gt[k];
-          g.A = gt[k].A + i0;
-          g.M = std::min(helfem::EIG_BAND_TILE, n - i0);
-          g.rmap = (const int64_t *)w.band_pos_dev.p + blk_ptr[ib] + i0;
-          g.cmap = w.band_iota_dev.p;
-          g.kstart = w.band_ks_dev.p + w.band_koff[q];
-          g.nk = w.band_koff[q + 1] - w.band_koff[q];
-          fx.push_back(g);
-        }
-      }
-      std::stable_sort(fx.begin(), fx.end(), [](const GemmTask &a, const GemmTask &b) { return a.nk > b.nk; });
-      upload_cached(w.fxtasks, w.h_fxtasks, fx, s);
-    }
-    {
-      ProfScope ps(ctx, "eig_reduce");
-      // two workgroups per tile (split K) when the batch's tiles would not fill the chip evenly: more than half, fewer
-      // than all of the 2 x CU slots; HELFEM_GEMM_SPLITK = 0 / 1 forces it off / on
-      const int force_split = tuning().gemm_splitk;
-      long full_tiles = 0, low_tiles = 0;
-      for (int k = 0; k < nb; k++) {
-        const long t1 = (ns[k] + 127) / 128;
-        full_tiles += t1 * t1;
-        low_tiles += t1 * (t1 + 1) / 2;
-      }
-      // the row tasks of the banded F X are 64 x 64 work with the 16x16x4 instruction: forced large tiles, split K or
-      // HELFEM_MFMA keep the dense tasks
-      const bool band_fx = !fx.empty() && force_split < 0 && !gemm_prefers_128(ctx, full_tiles) && !tuning().mfma_4x4x4;
-      for (int k = 0; k < nb; k++) {
-        const int ib = mine[c0 + k] % nblk;
-        const double *dF = dFs[mine[c0 + k] / nblk];
-        int n = ns[k];
-        double *Fk = Fb.p + (size_t)k * nmax * nmax;
-        if (!(keep_x && w.xc_have[ib]))
-          hipLaunchKernelGGL(k_gather_block, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, dS, N, drows + blk_ptr[ib],
-                             dcols + blk_ptr[ib], n, Fk, const_cast<double *>(Xptr[k]));
-        else if (!band_fx)
-          hipLaunchKernelGGL(k_gather_f, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, N, drows + blk_ptr[ib], n, Fk);
-        if (band_fx)  // the rows of F radial-major, its columns in the caller's order
-          hipLaunchKernelGGL(k_gather_f2, dim3((n + 255) / 256, n), dim3(256), 0, s, dF, N, (const int64_t *)w.band_rows_dev.p + blk_ptr[ib],
-                             drows + blk_ptr[ib], n, Fk);
-        if (keep_x) w.xc_have[ib] = 1;
-      }
-      const int slots = 2 * eig_num_cus(ctx);
-      const bool split_full = force_split >= 0 ? force_split != 0 : (full_tiles < slots && nm >= 256);
-      const bool split_low = force_split >= 0 ? force_split != 0 : (low_tiles < slots && nm >= 256);
-      ProfScope pp3(ctx, "eig_products");  // the N^3 products alone (bench.py: MFMA fraction of the tile engine)
-      // 64 x 64 tiles unless the batch's 128 x 128 tiles would fill whole rounds of the chip (gemm_prefers_128): 386 large
-      // tiles on 512 slots ran at 34 TFLOP/s as two half-K workgroups each, 1452 small ones at 37 and without zeroing C.
-      // HELFEM_GEMM_SPLITK=1 / HELFEM_GEMM_TILE=128 bring the large tiles back (checkers).
-      const bool tile64 = force_split < 0 && !gemm_prefers_128(ctx, full_tiles);
-      GemmHow full, low;  // the full products F X and X Z; X^T (F X), of which only the lower tiles are formed (GemmTask::sym)
-      if (tile64) full.tile = low.tile = GemmTile::T64;
-      else {
-        if (split_full) full.tile = GemmTile::T128, full.split2 = true;
-        else if (tuning().gemm_rect) full.tile = GemmTile::T128x64;
-        if (split_low) low.tile = GemmTile::T128, low.split2 = true;
-      }
-      w.full_how = full;
-      if (full.split2)
-        for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(T1.p + (size_t)k * nmax * nmax, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
-      if (band_fx) {
-        GemmHow how;
-        how.tile = GemmTile::T64;
-        how.scatter = how.klist = true;
-        gemm_tasklist_dev(ctx, w.fxtasks.p, (int)fx.size(), helfem::EIG_BAND_TILE, nm, how);
-      } else
-        gemm_tasklist_dev(ctx, w.gtasks.p, nb, nm, nm, full);
-      if (low.split2)
-        for (int k = 0; k < nb; k++) HFG_HIP_CHECK(hipMemsetAsync(w.A[k].p, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
-      gemm_tasklist_dev(ctx, w.gtasks.p + nb, nb, nm, nm, low);
-      gemm_mirror_lower_dev(ctx, w.gtasks.p + nb, nb, nm);  // the tridiagonalisation sweeps the full square
-    }
-    // direct: everything that needs the eigenvalues alone, on the main stream between the divide-and-conquer stage and the
-    // wait for X Q (the side stream ends after that stage: the main stream would idle there)
-    std::function<void()> after_solve;
+    const std::vector<GemmTask> fx = build_row_tasks(c, b, gt);
+    if (!fx.empty()) upload_cached(w.fxtasks, w.h_fxtasks, fx, s);
+    b.plan = helfem::eig_product_plan(b.nb, b.ns, gemm_tile_slots(ctx), !fx.empty(), sw);
+    b.last = helfem::eig_last_product(b.plan.full, nev > 0, direct);
+    reduce_stage(c, b, (int)fx.size());
     if (direct)
-      after_solve = [&] {
-        if (w.used_dc) {  // the status word goes home now; the host waits for this point only
-          if (!w.h_status) HFG_HIP_CHECK(hipHostMalloc((void **)&w.h_status, sizeof(int), hipHostMallocDefault));
-          if (!w.status_ev) HFG_HIP_CHECK(hipEventCreateWithFlags(&w.status_ev, hipEventDisableTiming));
-          HFG_HIP_CHECK(hipMemcpyAsync(w.h_status, dc_status_word(ctx), sizeof(int), hipMemcpyDeviceToHost, s));
-          HFG_HIP_CHECK(hipEventRecord(w.status_ev, s));
-        }
-        ProfScope ps(ctx, "scatter");
-        std::vector<const double *> csrc;
-        std::vector<double *> cdst;
-        std::vector<int> cn;
-        for (int k = 0; k < nb; k++) {
-          const int ib = mine[c0 + k] % nblk, f = mine[c0 + k] / nblk;
-          csrc.push_back(nev > 0 ? w.Ws[k].p : w.d[k].p);
-          cdst.push_back(Etmp.p + (size_t)f * N + koff[ib]);
-          cn.push_back(nevs[k]);
-        }
-        copy_slices(s, csrc, cdst, cn);
-        for (int f = 0; f < nF; f++) {
-          int *rk = rank.p + (size_t)f * (N + 8);
-          launch_rank(ctx, Etmp.p + (size_t)f * N, K, rk);
-          hipLaunchKernelGGL(k_place_values, dim3((K + 255) / 256), dim3(256), 0, s, Etmp.p + (size_t)f * N, K, rk, dEs[f]);
-          HFG_HIP_CHECK(hipMemsetAsync(dCs[f], 0, sizeof(double) * (size_t)N * K, s));  // (stream order: ahead of the product, split K adds into it)
-        }
-      };
-    eig_sym_batch(ctx, w, nb, ns.data(), Xptr, nev > 0 ? nevs.data() : nullptr, after_solve);
+      eig_sym_batch(ctx, w, b.nb, b.ns, b.Xptr, nev > 0 ? b.nevs : nullptr, [&] { publish_direct(c, b); });
+    else
+      eig_sym_batch(ctx, w, b.nb, b.ns, b.Xptr, nev > 0 ? b.nevs : nullptr);
     {
       ProfScope ps(ctx, "eig_backtransform");
-      if (!direct) {
-        // the eigenvalues are final: their copy into the slots goes ahead of the last product, not behind it
-        std::vector<const double *> csrc;
-        std::vector<double *> cdst;
-        std::vector<int> cn;
-        for (int k = 0; k < nb; k++) {
-          const int ib = mine[c0 + k] % nblk;
-          double *slotp = dBlockBufs[mine[c0 + k] / nblk] + (size_t)ib * slot;
-          csrc.push_back(nev > 0 ? w.Ws[k].p : w.d[k].p);
-          cdst.push_back(slotp + nmax * nmax);
-          cn.push_back(nevs[k]);
-          if (nev <= 0 && w.full_how.split2 && ctx->shard_n == 1)  // (more ranks: the whole buffer was zeroed above)
-            HFG_HIP_CHECK(hipMemsetAsync(slotp, 0, sizeof(double) * (size_t)ns[k] * ns[k], s));
-        }
-        copy_slices(s, csrc, cdst, cn);
-      }
-      {
-        ProfScope pp3(ctx, "eig_products");
-        const GemmTask *last = w.gtasks.p + (w.folded ? 3 : 2) * (size_t)nb;
-        GemmHow how = nev > 0 ? GemmHow{GemmTile::T64} : w.full_how;  // (n x nev products: small tiles, no split)
-        how.scatter = direct;  // split2: the block slots, or all of C, were zeroed above
-        gemm_tasklist_dev(ctx, last, nb, nm, nev > 0 ? *std::max_element(nevs.begin(), nevs.end()) : nm, how);
-      }
+      if (!direct) publish_slots(c, b);
+      last_product(c, b);
     }
-    if (direct && w.used_dc) {
-      // everything is queued: the one host wait, for the status word behind the divide-and-conquer stage (the persistent
-      // tridiagonalisation's words, written before it, are home by then too)
-      HFG_HIP_CHECK(hipEventSynchronize(w.status_ev));
-      if (*w.h_status != 0) throw std::logic_error("Eigendecomposition failed!\n");
-      trdp_check_status(ctx);
-    } else
-    check_status(ctx, w, nb);
+    wait_status(c, b.nb);
   }
   HFG_HIP_CHECK(hipGetLastError());
 }
+void eig_blocks_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
+                    const int64_t *blk_idx, double *dBlockBuf) {
+  eig_blocks_multi_dev(ctx, N, 1, &dF, dS, nblk, blk_ptr, blk_idx, &dBlockBuf);
+}
 
 // phase 2: global sort of all eigenvalues and scatter of the block eigenvectors into C (N x N)
-static void eig_assemble_sel_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx, const double *dBlockBuf,
-                                 double *dE, double *dC, int nev);
-void eig_assemble_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
-                      const double *dBlockBuf, double *dE, double *dC) {
-  eig_assemble_sel_dev(ctx, N, nblk, blk_ptr, blk_idx, dBlockBuf, dE, dC, 0);
-}
-int64_t eig_sel_count(int nblk, const int64_t *blk_ptr, int64_t nev) { return helfem::eig_sel_count(nblk, blk_ptr, nev); }
 /// nev > 0: slot ib holds the lowest min(nev, n_b) pairs of its block; the ranking runs over their K = eig_sel_count values
 /// (ties by position in block order, as over all N values), C is N x K
 static void eig_assemble_sel_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx, const double *dBlockBuf,
@@ -1661,28 +1703,14 @@ static void eig_assemble_sel_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *b
     HFG_HIP_CHECK(hipMemcpyAsync(w.asm_rows_dev.p, w.asm_rows.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
   }
   int64_t *drows = (int64_t *)w.asm_rows_dev.p;
-  size_t nmax = 0;
-  for (int ib = 0; ib < nblk; ib++) nmax = std::max<size_t>(nmax, blk_ptr[ib + 1] - blk_ptr[ib]);
-  const size_t slot = nmax * nmax + nmax;
+  const size_t nmax = helfem::eig_block_nmax(nblk, blk_ptr), slot = nmax * nmax + nmax;
   DevBuf<double> &Etmp = ctx->ws[3];
   Etmp.resize(N);
-  std::vector<int64_t> koff(nblk + 1, 0);  // first of block ib's values among the K wanted ones (all of them: blk_ptr)
-  for (int ib = 0; ib < nblk; ib++) {
-    const int64_t n = blk_ptr[ib + 1] - blk_ptr[ib];
-    koff[ib + 1] = koff[ib] + (nev > 0 ? std::min<int64_t>(nev, n) : n);
-  }
-  const int K = (int)koff[nblk];
-  {
-    std::vector<const double *> csrc;
-    std::vector<double *> cdst;
-    std::vector<int> cn;
-    for (int ib = 0; ib < nblk; ib++) {
-      csrc.push_back(dBlockBuf + (size_t)ib * slot + nmax * nmax);
-      cdst.push_back(Etmp.p + koff[ib]);
-      cn.push_back((int)(koff[ib + 1] - koff[ib]));
-    }
-    copy_slices(s, csrc, cdst, cn);
-  }
+  std::vector<int64_t> koff(nblk + 1);  // first of block ib's values among the K wanted ones (all of them: blk_ptr)
+  const int K = (int)helfem::eig_value_offsets(nblk, blk_ptr, nev, koff.data());
+  publish_values(
+      s, nblk, [&](int ib) { return dBlockBuf + (size_t)ib * slot + nmax * nmax; }, [&](int ib) { return Etmp.p + koff[ib]; },
+      [&](int ib) { return (int)(koff[ib + 1] - koff[ib]); });
   DevBuf<int> &rank = w.ibuf1;
   rank.resize(N + 8);
   HFG_HIP_CHECK(hipMemsetAsync(dC, 0, sizeof(double) * (size_t)N * K, s));
@@ -1694,6 +1722,19 @@ static void eig_assemble_sel_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *b
   }
   HFG_HIP_CHECK(hipGetLastError());
 }
+void eig_assemble_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
+                      const double *dBlockBuf, double *dE, double *dC) {
+  eig_assemble_sel_dev(ctx, N, nblk, blk_ptr, blk_idx, dBlockBuf, dE, dC, 0);
+}
+
+/// the context as one rank for the lifetime of the guard; its shard comes back on every way out
+struct OneRankGuard {
+  hfg_ctx *ctx;
+  const int rank, n;
+  explicit OneRankGuard(hfg_ctx *c) : ctx(c), rank(c->shard_rank), n(c->shard_n) { ctx->shard_rank = 0, ctx->shard_n = 1; }
+  ~OneRankGuard() { ctx->shard_rank = rank, ctx->shard_n = n; }
+  OneRankGuard(const OneRankGuard &) = delete;
+};
 
 // The one-call entries: scf::eig_gsym_sub on one device, whatever the context's shard.  nF matrices with the same Sinvh and
 // blocks; nev > 0: the lowest min(nev, n_b) pairs of every block.  By default nothing goes through block slots
@@ -1701,29 +1742,19 @@ static void eig_assemble_sel_dev(hfg_ctx *ctx, int N, int nblk, const int64_t *b
 // phases through ws[6] -- the checker: same E, same C, bit for bit.
 static void eig_gsym_sub_multi_dev(hfg_ctx *ctx, int N, int nF, const double *const *dFs, const double *dS, int nblk, const int64_t *blk_ptr,
                                    const int64_t *blk_idx, int nev, double *const *dEs, double *const *dCs) {
-  int save_rank = ctx->shard_rank, save_n = ctx->shard_n;
-  ctx->shard_rank = 0;
-  ctx->shard_n = 1;
-  try {
-    if (helfem::tuning_live().eig_direct && nF * nblk <= MAXB) {  // (read at every call)
-      eig_blocks_multi_dev(ctx, N, nF, dFs, dS, nblk, blk_ptr, blk_idx, nullptr, nev, dEs, dCs);
-    } else {
-      const size_t sz = eig_block_buf_size(nblk, blk_ptr);
-      DevBuf<double> &buf = ctx->ws[6];
-      buf.resize(nF * sz);
-      double *bufs[MAXB];
-      if (nF > MAXB) throw std::logic_error("eig_gsym_sub: too many matrices in one call\n");
-      for (int f = 0; f < nF; f++) bufs[f] = buf.p + f * sz;
-      eig_blocks_multi_dev(ctx, N, nF, dFs, dS, nblk, blk_ptr, blk_idx, bufs, nev);
-      for (int f = 0; f < nF; f++) eig_assemble_sel_dev(ctx, N, nblk, blk_ptr, blk_idx, bufs[f], dEs[f], dCs[f], nev);
-    }
-  } catch (...) {
-    ctx->shard_rank = save_rank;
-    ctx->shard_n = save_n;
-    throw;
+  const OneRankGuard one_rank(ctx);
+  if (helfem::tuning_live().eig_direct && nF * nblk <= MAXB) {  // (read at every call)
+    eig_blocks_multi_dev(ctx, N, nF, dFs, dS, nblk, blk_ptr, blk_idx, nullptr, nev, dEs, dCs);
+    return;
   }
-  ctx->shard_rank = save_rank;
-  ctx->shard_n = save_n;
+  const size_t sz = eig_block_buf_size(nblk, blk_ptr);
+  DevBuf<double> &buf = ctx->ws[6];
+  buf.resize(nF * sz);
+  double *bufs[MAXB];
+  if (nF > MAXB) throw std::logic_error("eig_gsym_sub: too many matrices in one call\n");
+  for (int f = 0; f < nF; f++) bufs[f] = buf.p + f * sz;
+  eig_blocks_multi_dev(ctx, N, nF, dFs, dS, nblk, blk_ptr, blk_idx, bufs, nev);
+  for (int f = 0; f < nF; f++) eig_assemble_sel_dev(ctx, N, nblk, blk_ptr, blk_idx, bufs[f], dEs[f], dCs[f], nev);
 }
 
 void eig_gsym_sub_dev(hfg_ctx *ctx, int N, const double *dF, const double *dS, int nblk, const int64_t *blk_ptr,
@@ -1742,30 +1773,10 @@ void eig_gsym_sub_sel_dev(hfg_ctx *ctx, int N, const double *dF, const double *d
 /// the columns with support on block ib's rows, ascending; throws like eig_blocks_dev when Sinvh is not block structured
 void eig_block_supports(hfg_ctx *ctx, int N, const double *dS, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
                         std::vector<int64_t> &cols) {
-  hipStream_t s = ctx->stream;
   DevBuf<int64_t> drows;
   DevBuf<int> flag;
   drows.resize(N);
-  flag.resize((size_t)N * nblk + 8);
-  HFG_HIP_CHECK(hipMemcpyAsync(drows.p, blk_idx, sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
-  for (int ib = 0; ib < nblk; ib++) {
-    const int n = (int)(blk_ptr[ib + 1] - blk_ptr[ib]);
-    hipLaunchKernelGGL(k_col_support, dim3(N), dim3(256), 0, s, dS, N, drows.p + blk_ptr[ib], n, flag.p + (size_t)ib * N);
-  }
-  std::vector<int> hflag((size_t)N * nblk);
-  HFG_HIP_CHECK(hipMemcpyAsync(hflag.data(), flag.p, sizeof(int) * hflag.size(), hipMemcpyDeviceToHost, s));
-  HFG_HIP_CHECK(hipStreamSynchronize(s));
-  cols.clear();
-  for (int ib = 0; ib < nblk; ib++) {
-    int cnt = 0;
-    for (int c = 0; c < N; c++)
-      if (hflag[(size_t)ib * N + c]) {
-        cols.push_back(c);
-        cnt++;
-      }
-    if (cnt != (int)(blk_ptr[ib + 1] - blk_ptr[ib]))
-      throw std::logic_error("eig_gsym_sub: Sinvh is not block structured (columns with support != block size)\n");
-  }
+  block_supports(ctx, N, dS, nblk, blk_ptr, blk_idx, drows.p, flag, cols);
 }
 
 // flag = 1 when H (N x N) has a non-zero entry, inside a symmetry block (blockid null: anywhere), whose two radial

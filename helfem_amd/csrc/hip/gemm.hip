@@ -608,7 +608,7 @@ TaskKernel tasklist_kernel(GemmTile tile, const GemmHow &how) {
 }
 }  // namespace
 
-/// Launches the task list: grid (tiles of a maxM x maxN product, tasks).  GemmHow (internal.h) says which tiles and which
+/// Launches the task list: grid (tiles of a maxM x maxN product, tasks).  GemmHow (host/eig_plan.h) says which tiles and which
 /// variant of the engine: acc -- streaming epilogue, beta != 0 in every active task; split2 -- two workgroups per tile, each
 /// half of K, beta == 0 tasks whose outputs the caller has ZEROED; map -- GemmTask::amap and cmap set in every active task;
 /// scatter -- GemmTask::rmap and cmap set in every active task, beta == 0 (with split2: the mapped elements zeroed)
@@ -653,20 +653,18 @@ void gemm_worklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, in
   HFG_HIP_CHECK(hipGetLastError());
 }
 
-/// 128 x 128 tiles (two workgroups per CU, 59-63 TFLOP/s when they fill the chip) or 64 x 64 tiles (three per CU, 52-56)?
-/// The large tiles only when their count fills whole rounds of the 2 x CU slots to 85 %: 484 tiles (n = 2816) 59.1
-/// against 56.1 TFLOP/s, 2304 (n = 6102) 55.8 against 54.1, 4096 (n = 8192) 63.5 against 58.5 -- but 1156 (n = 4230, 2.26
-/// rounds) 47.7 against 52.1, and the 386 tiles of the eigensolve's three blocks 34 against 37 (profiles/r03_gemm_bench.txt).
-/// HELFEM_GEMM_TILE = 64 / 128 forces one.
-bool gemm_prefers_128(hfg_ctx *ctx, long tiles128) {
-  if (tuning().gemm_tile) return tuning().gemm_tile == 128;
+/// Workgroup slots of the large tiles: two per CU of the first context's device
+int gemm_tile_slots(hfg_ctx *ctx) {
   static const int slots = [&] {  // once per process, under the guard of the static's initialisation
     int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) ncu = 256;
     return 2 * ncu;
   }();
-  const long rounds = (tiles128 + slots - 1) / slots;
-  return tiles128 >= slots / 2 && (double)tiles128 >= 0.85 * (double)(rounds * slots);
+  return slots;
+}
+/// 128 x 128 tiles or 64 x 64 tiles?  The rule and its measurements: host/eig_plan.h.  HELFEM_GEMM_TILE = 64 / 128 forces one.
+bool gemm_prefers_128(hfg_ctx *ctx, long tiles128) {
+  return helfem::gemm_prefers_128(tiles128, gemm_tile_slots(ctx), tuning().gemm_tile);
 }
 
 void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda,

@@ -7,15 +7,12 @@
 #include "common.h"
 #include "tables.h"
 #include "../host/scf.h"
+#include "../host/eig_plan.h"
 
 namespace hfg {
 
-// gemm.hip: the FP64 tile engine.  One launcher for task lists, one for task lists with a work list.
-enum class GemmTile { Auto, T64, T128, T128x64 };  // Auto: gemm_prefers_128() picks T64 or T128 (T64 only up to 65535 tasks)
-struct GemmHow {
-  GemmTile tile = GemmTile::Auto;
-  bool acc = false, split2 = false, map = false, scatter = false, klist = false;
-};
+// gemm.hip: the FP64 tile engine.  One launcher for task lists, one for task lists with a work list.  GemmTile and GemmHow
+// are plain data and live in host/eig_plan.h, beside the rules that choose them for the blocked eigensolve.
 // kernel by (tile, variant); HELFEM_MFMA=4x4x4 reaches the plain, acc and map lists and gemm_dev:
 //   {} / {T64} / {T128}           k_dgemm_tasklist<64, 64> or <128, 128>
 //   {T128x64}                     k_dgemm_tasklist<128, 64>
@@ -32,7 +29,8 @@ void gemm_worklist_dev(hfg_ctx *ctx, const GemmTask *dtasks, const int2 *dwl, in
 // host: (task, tile) or, split2, (task, 2 tile + half) for every tile of every non-empty task, in task order
 void gemm_worklist(const std::vector<GemmTask> &tasks, GemmTile tile, bool split2, std::vector<int2> &out);  // gemm.hip
 void gemm_mirror_lower_dev(hfg_ctx *ctx, const GemmTask *dtasks, int ntasks, int maxN);  // gemm.hip
-bool gemm_prefers_128(hfg_ctx *ctx, long tiles128);  // gemm.hip
+int gemm_tile_slots(hfg_ctx *ctx);  // gemm.hip; workgroup slots of the large tiles: 2 x CUs, taken once per process
+bool gemm_prefers_128(hfg_ctx *ctx, long tiles128);  // gemm.hip; helfem::gemm_prefers_128 on this chip and HELFEM_GEMM_TILE
 void gemm_dev(hfg_ctx *ctx, bool tA, bool tB, int M, int N, int K, double alpha, const double *A, int lda, const double *B, int ldb,
               double beta, double *C, int ldc);  // gemm.hip
 
