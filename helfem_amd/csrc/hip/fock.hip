@@ -22,6 +22,7 @@
 #include "xc_device.h"
 #include "../host/dftfuncs.h"
 #include "../host/fock_need.h"
+#include "../host/fock_plan.h"
 #include <algorithm>
 #include <cstring>
 
@@ -913,6 +914,104 @@ __global__ void k_xc_density_theta(const double *__restrict__ D0, const double *
   }
 }
 
+// Pieces that the two grid kernels below share, each in the operation order the kernels had them in.
+// Scale factors of the radial-like, polar-like and azimuthal coordinates: prolate spheroidal (diatomic dftgrid.cpp:693-707),
+// spherical (atomic dftgrid.cpp:724-743; shm holds r)
+__device__ __forceinline__ void xc_scale_factors(int geom, double Rh, double shm, double sth, double &hmu, double &hnu, double &hphi) {
+  if (geom == 0) {
+    hmu = hnu = Rh * sqrt(shm * shm + sth * sth);
+    hphi = Rh * shm * sth;
+  } else {
+    hmu = 1.0;
+    hnu = shm;
+    hphi = shm * sth;
+  }
+}
+// ... and the volume weight w of theta point i (th_w) at a radial point of weight wr, dphi per point of the phi grid
+__device__ __forceinline__ void xc_scale_factors_weight(int geom, double Rh, double shm, double sth, const double *__restrict__ th_w, int i,
+                                                        double dphi, double wr, double &hmu, double &hnu, double &hphi, double &w) {
+  if (geom == 0) {
+    double h2 = shm * shm + sth * sth;
+    hmu = hnu = Rh * sqrt(h2);
+    hphi = Rh * shm * sth;
+    w = th_w[i] * dphi * wr * Rh * Rh * Rh * shm * h2;
+  } else {
+    hmu = 1.0;
+    hnu = shm;
+    hphi = shm * sth;
+    w = th_w[i] * dphi * wr * shm * shm;
+  }
+}
+// Block reduction of the three scalars of a radial point into partial[3][NQ]; red: 3 * nwave doubles of LDS.  Fixed order
+// (shuffle down 32 ... 1, then the wave sums in wave order) -> deterministic
+__device__ __forceinline__ void xc_reduce_partials(double nel, double exc_sum, double kin_sum, double *red, size_t Q, size_t NQ,
+                                                   double *__restrict__ partial) {
+  int nwave = blockDim.x / 64, wave = threadIdx.x / 64, lane = threadIdx.x & 63;
+  for (int o = 32; o > 0; o >>= 1) {
+    nel += __shfl_down(nel, o, 64);
+    exc_sum += __shfl_down(exc_sum, o, 64);
+    kin_sum += __shfl_down(kin_sum, o, 64);
+  }
+  if (lane == 0) {
+    red[wave] = nel;
+    red[nwave + wave] = exc_sum;
+    red[2 * nwave + wave] = kin_sum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, b = 0.0, c2 = 0.0;
+    for (int w = 0; w < nwave; w++) {
+      a += red[w];
+      b += red[nwave + w];
+      c2 += red[2 * nwave + w];
+    }
+    partial[Q] = a;
+    partial[NQ + Q] = b;
+    partial[2 * NQ + Q] = c2;
+  }
+}
+// Phi transform of one output (ga, gb, theta row i) of one spin: pot holds that spin's potential planes in LDS with stride
+// ng, il is the row's place in them, Fs the spin's planes of Fo
+__device__ __forceinline__ void xc_phi_transform(const double *pot, int ng, int il, int i, int ga, int gb, size_t Q, int G, int nth, int nphi,
+                                                 const int *__restrict__ grp_m, const double *__restrict__ cosd,
+                                                 const double *__restrict__ sind, int Dmax, const double *__restrict__ th_s, int geom,
+                                                 double Rh, double shm, int do_grad, int do_tau, int do_lapl, size_t stride,
+                                                 double *__restrict__ Fs) {
+  int D = grp_m[ga] - grp_m[gb];
+  const double *cd = cosd + (size_t)(D + Dmax) * nphi;
+  const double *sd = sind + (size_t)(D + Dmax) * nphi;
+  const double *p0 = pot, *p1 = p0 + ng, *p2 = p0 + 2 * ng, *p3 = p0 + 3 * ng, *p4 = p0 + 4 * ng, *p5 = p0 + 5 * ng;
+  double fa = 0.0, fs = 0.0, fb = 0.0, ft = 0.0, fl = 0.0;
+  double mga = grp_m[ga];
+  for (int j = 0; j < nphi; j++) {
+    int pt = il * nphi + j;
+    fa += 0.5 * p0[pt] * cd[j];
+    if (do_grad) {
+      fa -= mga * p3[pt] * sd[j];
+      fs += p2[pt] * cd[j];
+      fb += p1[pt] * cd[j];
+    }
+    if (do_tau) ft += p4[pt] * cd[j];
+    if (do_lapl) fl += p5[pt] * cd[j];
+  }
+  size_t o = ((Q * G + ga) * G + gb) * nth + i;
+  if (do_lapl) Fs[5 * stride + o] = fl;
+  if (do_tau) {
+    // the three tau terms of eval_Fxc (dftgrid.cpp:533-540) share the phi sum; the scale factors depend on
+    // theta only.  Halves as for the LDA term: the radial stage adds the (x,y) and (y,x) blocks.
+    double hmu, hnu, hphi;
+    xc_scale_factors(geom, Rh, shm, th_s[i], hmu, hnu, hphi);
+    fa += 0.5 * mga * (double)grp_m[gb] * ft / (hphi * hphi);
+    Fs[3 * stride + o] = 0.5 * ft / (hmu * hmu);
+    Fs[4 * stride + o] = 0.5 * ft / (hnu * hnu);
+  }
+  Fs[o] = fa;
+  if (do_grad) {
+    Fs[stride + o] = fs;
+    Fs[2 * stride + o] = fb;
+  }
+}
+
 // X3 grid evaluation at one radial point: density & gradient on the (theta,phi) grid, functional,
 //    energy/electron partial sums, and the phi-transformed potentials
 //       Fo[0][Q][ga][gb][i] = sum_j (1/2 w vrho cos(D phi_j) - m_ga gr_phi sin(D phi_j))
@@ -951,21 +1050,8 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
   double nel = 0.0, exc_sum = 0.0, kin_sum = 0.0;
   for (int pt = threadIdx.x; pt < ng; pt += blockDim.x) {
     int i = pt / nphi, j = pt % nphi;
-    double sth = th_s[i];
-    // scale factors of the radial-like, polar-like and azimuthal coordinates and the volume weight:
-    // prolate spheroidal (diatomic dftgrid.cpp:693-707), spherical (atomic dftgrid.cpp:724-743; shm holds r)
     double hmu, hnu, hphi, w;
-    if (geom == 0) {
-      double h2 = shm * shm + sth * sth;
-      hmu = hnu = Rh * sqrt(h2);
-      hphi = Rh * shm * sth;
-      w = th_w[i] * dphi * wr * Rh * Rh * Rh * shm * h2;
-    } else {
-      hmu = 1.0;
-      hnu = shm;
-      hphi = shm * sth;
-      w = th_w[i] * dphi * wr * shm * shm;
-    }
+    xc_scale_factors_weight(geom, Rh, shm, th_s[i], th_w, i, dphi, wr, hmu, hnu, hphi, w);
     double rho = 0.0, gmu = 0.0, gnu = 0.0, gphi = 0.0, tau = 0.0, lap = 0.0;
     for (int ga = 0; ga < G; ga++)
       for (int gb = 0; gb < G; gb++) {
@@ -1013,75 +1099,15 @@ __global__ void k_xc_grid(const double *__restrict__ V, const double *__restrict
       p3[pt] = f * gphi / hphi;
     }
   }
-  // block reduction of the two scalars (fixed order -> deterministic)
-  int nwave = blockDim.x / 64, wave = threadIdx.x / 64, lane = threadIdx.x & 63;
-  for (int o = 32; o > 0; o >>= 1) {
-    nel += __shfl_down(nel, o, 64);
-    exc_sum += __shfl_down(exc_sum, o, 64);
-    kin_sum += __shfl_down(kin_sum, o, 64);
-  }
-  if (lane == 0) {
-    red[wave] = nel;
-    red[nwave + wave] = exc_sum;
-    red[2 * nwave + wave] = kin_sum;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0, b = 0.0, c2 = 0.0;
-    for (int w = 0; w < nwave; w++) {
-      a += red[w];
-      b += red[nwave + w];
-      c2 += red[2 * nwave + w];
-    }
-    partial[Q] = a;
-    partial[NQ + Q] = b;
-    partial[2 * NQ + Q] = c2;
-  }
+  xc_reduce_partials(nel, exc_sum, kin_sum, red, Q, NQ, partial);
   // phi transforms
   int nout = G * G * nth;
   for (int t = threadIdx.x; t < nout; t += blockDim.x) {
     int i = t % nth;
     int gab = t / nth;
     int ga = gab / G, gb = gab % G;
-    int D = grp_m[ga] - grp_m[gb];
-    const double *cd = cosd + (size_t)(D + Dmax) * nphi;
-    const double *sd = sind + (size_t)(D + Dmax) * nphi;
-    double fa = 0.0, fs = 0.0, fb = 0.0, ft = 0.0, fl = 0.0;
-    double mga = grp_m[ga];
-    for (int j = 0; j < nphi; j++) {
-      int pt = i * nphi + j;
-      fa += 0.5 * p0[pt] * cd[j];
-      if (do_grad) {
-        fa -= mga * p3[pt] * sd[j];
-        fs += p2[pt] * cd[j];
-        fb += p1[pt] * cd[j];
-      }
-      if (do_tau) ft += p4[pt] * cd[j];
-      if (do_lapl) fl += p5[pt] * cd[j];
-    }
-    size_t o = ((Q * G + ga) * G + gb) * nth + i;
-    if (do_lapl) Fo[5 * stride + o] = fl;
-    if (do_tau) {
-      // the three tau terms of eval_Fxc (dftgrid.cpp:533-540) share the phi sum; the scale factors depend on
-      // theta only.  Halves as for the LDA term: the radial stage adds the (x,y) and (y,x) blocks.
-      double sth = th_s[i], hmu, hnu, hphi;
-      if (geom == 0) {
-        hmu = hnu = Rh * sqrt(shm * shm + sth * sth);
-        hphi = Rh * shm * sth;
-      } else {
-        hmu = 1.0;
-        hnu = shm;
-        hphi = shm * sth;
-      }
-      fa += 0.5 * mga * (double)grp_m[gb] * ft / (hphi * hphi);
-      Fo[3 * stride + o] = 0.5 * ft / (hmu * hmu);
-      Fo[4 * stride + o] = 0.5 * ft / (hnu * hnu);
-    }
-    Fo[o] = fa;
-    if (do_grad) {
-      Fo[stride + o] = fs;
-      Fo[2 * stride + o] = fb;
-    }
+    xc_phi_transform(sh, ng, i, i, ga, gb, Q, G, nth, nphi, grp_m, cosd, sind, Dmax, th_s, geom, Rh, shm, do_grad, do_tau, do_lapl,
+                     stride, Fo);
   }
 }
 
@@ -1123,19 +1149,8 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
   if (i0) __syncthreads();  // the previous chunk's planes have been transformed
   for (int pt = threadIdx.x; pt < rows * nphi; pt += blockDim.x) {
     int i = i0 + pt / nphi, j = pt % nphi;
-    double sth = th_s[i];
     double hmu, hnu, hphi, w;
-    if (geom == 0) {
-      double h2 = shm * shm + sth * sth;
-      hmu = hnu = Rh * sqrt(h2);
-      hphi = Rh * shm * sth;
-      w = th_w[i] * dphi * wr * Rh * Rh * Rh * shm * h2;
-    } else {
-      hmu = 1.0;
-      hnu = shm;
-      hphi = shm * sth;
-      w = th_w[i] * dphi * wr * shm * shm;
-    }
+    xc_scale_factors_weight(geom, Rh, shm, th_s[i], th_w, i, dphi, wr, hmu, hnu, hphi, w);
     double rho[2] = {0.0, 0.0}, gmu[2] = {0.0, 0.0}, gnu[2] = {0.0, 0.0}, gphi[2] = {0.0, 0.0}, tau[2] = {0.0, 0.0};
     double lap[2] = {0.0, 0.0};
     for (int ga = 0; ga < G; ga++)
@@ -1217,71 +1232,11 @@ __global__ void k_xc_grid_pol(const double *__restrict__ V, const double *__rest
     int i = i0 + il;
     int gab = tt / rows;
     int ga = gab / G, gb = gab % G;
-    int D = grp_m[ga] - grp_m[gb];
-    const double *cd = cosd + (size_t)(D + Dmax) * nphi;
-    const double *sd = sind + (size_t)(D + Dmax) * nphi;
-    const double *p0 = sh + (size_t)(npot * sp) * ng, *p1 = p0 + ng, *p2 = p0 + 2 * ng, *p3 = p0 + 3 * ng, *p4 = p0 + 4 * ng;
-    const double *p5 = p0 + 5 * ng;
-    double fa = 0.0, fs = 0.0, fb = 0.0, ft = 0.0, fl = 0.0;
-    double mga = grp_m[ga];
-    for (int j = 0; j < nphi; j++) {
-      int pt = il * nphi + j;
-      fa += 0.5 * p0[pt] * cd[j];
-      if (do_grad) {
-        fa -= mga * p3[pt] * sd[j];
-        fs += p2[pt] * cd[j];
-        fb += p1[pt] * cd[j];
-      }
-      if (do_tau) ft += p4[pt] * cd[j];
-      if (do_lapl) fl += p5[pt] * cd[j];
-    }
-    size_t o = ((Q * G + ga) * G + gb) * nth + i;
-    double *Fs = Fo + (size_t)sp * npl * stride;
-    if (do_lapl) Fs[5 * stride + o] = fl;
-    if (do_tau) {  // the three tau terms of eval_Fxc, as in k_xc_grid
-      double sth = th_s[i], hmu, hnu, hphi;
-      if (geom == 0) {
-        hmu = hnu = Rh * sqrt(shm * shm + sth * sth);
-        hphi = Rh * shm * sth;
-      } else {
-        hmu = 1.0;
-        hnu = shm;
-        hphi = shm * sth;
-      }
-      fa += 0.5 * mga * (double)grp_m[gb] * ft / (hphi * hphi);
-      Fs[3 * stride + o] = 0.5 * ft / (hmu * hmu);
-      Fs[4 * stride + o] = 0.5 * ft / (hnu * hnu);
-    }
-    Fs[o] = fa;
-    if (do_grad) {
-      Fs[stride + o] = fs;
-      Fs[2 * stride + o] = fb;
-    }
+    xc_phi_transform(sh + (size_t)(npot * sp) * ng, ng, il, i, ga, gb, Q, G, nth, nphi, grp_m, cosd, sind, Dmax, th_s, geom, Rh, shm, do_grad,
+                     do_tau, do_lapl, stride, Fo + (size_t)sp * npl * stride);
   }
   }  // theta chunks
-  int nwave = blockDim.x / 64, wave = threadIdx.x / 64, lane = threadIdx.x & 63;
-  for (int o = 32; o > 0; o >>= 1) {
-    nel += __shfl_down(nel, o, 64);
-    exc_sum += __shfl_down(exc_sum, o, 64);
-    kin_sum += __shfl_down(kin_sum, o, 64);
-  }
-  if (lane == 0) {
-    red[wave] = nel;
-    red[nwave + wave] = exc_sum;
-    red[2 * nwave + wave] = kin_sum;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0, b = 0.0, c2 = 0.0;
-    for (int w = 0; w < nwave; w++) {
-      a += red[w];
-      b += red[nwave + w];
-      c2 += red[2 * nwave + w];
-    }
-    partial[Q] = a;
-    partial[NQ + Q] = b;
-    partial[2 * NQ + Q] = c2;
-  }
+  xc_reduce_partials(nel, exc_sum, kin_sum, red, Q, NQ, partial);
 }
 
 // X4 of a group pair none of whose shell pairs the caller reads (hfg_ctx_set_fock_blocks): zeros, never stale data
@@ -1372,7 +1327,7 @@ __global__ void k_xc_fock_theta(const double *__restrict__ Fo, const double *__r
 // (at most XC_FT_MAXPP pairs per thread: groups of up to 64 shells)
 // (LAPL: the Laplacian plane Fo5 -> GL as in k_xc_fock_theta; a template parameter, so that the instance without it keeps
 // its register budget)
-constexpr int XC_FT_MAXPP = 16;
+using helfem::XC_FT_MAXPP;
 template <bool LAPL>
 __global__ __launch_bounds__(256) void k_xc_fock_theta_chunked(const double *__restrict__ Fo, const double *__restrict__ Th,
                                                                const double *__restrict__ dTh, int A, int nth, int G,
@@ -1614,59 +1569,23 @@ __global__ void k_mp_fill(const double *__restrict__ rad_w, const double *__rest
 
 // launchers
 // -------------------------------------------------------------------------------------------------
-static int round_up64(int n) { return ((n + 63) / 64) * 64; }
-static size_t xc_fock_radial_lds(int p, int nq, int do_lapl = 0) {
-  const size_t shb = (size_t)(4 * nq + (do_lapl ? 6 : 4) * nq * p) * sizeof(double);
-  if (shb > 150 * 1024) throw std::runtime_error("radial quadrature too large for the XC Fock kernel's LDS tables");
-  if (shb > 64 * 1024)
-    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_radial, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  return shb;
+// Workgroup sizes, bytes of LDS, chunking and what is refused: host/fock_plan.h.  A refusal of the plan is thrown here.
+using helfem::fock_block_threads;
+static void refuse(const char *why) {
+  if (why) throw std::runtime_error(why);
 }
-// LDS of k_xc_fock_theta: five (six with the Laplacian) potential rows and the Theta, dTheta rows of two shell groups
-static size_t xc_fock_theta_lds(int nth, int maxgrp, int do_lapl) {
-  size_t shb = (size_t)((do_lapl ? 6 : 5) * nth + 4 * nth * maxgrp) * sizeof(double);
-  if (shb > 160 * 1024) throw std::runtime_error("angular grid too large for the XC Fock kernel's LDS tables");  // callers use launch_xc_fock_theta
-  if (shb > 64 * 1024)
-    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_theta, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  return shb;
-}
-// X4 launch: the one-pass kernel when its tables fit a CU's LDS, the chunked one otherwise
-static void launch_xc_fock_theta(hfg_ctx *ctx, size_t NQ, int G, int nth, int maxgrp, const double *Fo, const double *Th, const double *dTh,
-                                 int A, const int *grp_off, const int *grp_shell, int do_grad, int do_tau, int rank, int nranks,
-                                 double *GA, double *GB, double *GC, int do_lapl = 0, double *GL = nullptr, const int *gneed = nullptr) {
-  const int nf = do_lapl ? 6 : 5;  // potential rows
-  const size_t need = (size_t)(nf * nth + 4 * nth * maxgrp) * sizeof(double);
-  if (need <= tuning().xc_lds_limit) {
-    hipLaunchKernelGGL(k_xc_fock_theta, dim3((unsigned)NQ, G * G), dim3(256), xc_fock_theta_lds(nth, maxgrp, do_lapl), ctx->stream, Fo, Th, dTh, A,
-                       nth, G, grp_off, grp_shell, do_grad, do_tau, do_lapl, NQ, rank, nranks, GA, GB, GC, GL, gneed);
-    return;
-  }
-  if (maxgrp * maxgrp > XC_FT_MAXPP * 256) throw std::runtime_error("angular basis too large for the XC Fock kernels (more than 64 shells of one m)");
-  int nthc = (int)(tuning().xc_lds_limit / sizeof(double) / (nf + 4 * maxgrp));
-  if (nthc < 4) throw std::runtime_error("angular basis too large for the XC Fock kernels' LDS tables");
-  nthc = std::min(nthc, nth);
-  const size_t shb = (size_t)(nf * nthc + 4 * nthc * maxgrp) * sizeof(double);
-  if (do_lapl) {
-    if (shb > 64 * 1024)
-      HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_theta_chunked<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-    hipLaunchKernelGGL(k_xc_fock_theta_chunked<true>, dim3((unsigned)NQ, G * G), dim3(256), shb, ctx->stream, Fo, Th, dTh, A, nth, G, grp_off,
-                       grp_shell, do_grad, do_tau, NQ, rank, nranks, GA, GB, GC, GL, nthc, gneed);
-    return;
-  }
-  if (shb > 64 * 1024)
-    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_fock_theta_chunked<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  hipLaunchKernelGGL(k_xc_fock_theta_chunked<false>, dim3((unsigned)NQ, G * G), dim3(256), shb, ctx->stream, Fo, Th, dTh, A, nth, G, grp_off,
-                     grp_shell, do_grad, do_tau, NQ, rank, nranks, GA, GB, GC, (double *)nullptr, nthc, gneed);
+static size_t accepted(const helfem::FockLds &lds) {
+  refuse(lds.refused);
+  return lds.bytes;
 }
 
-// LDS of k_xc_density_radial (256 threads): P block, the two transposed tables, the partial sums of the j classes
-static size_t xc_density_radial_lds(int p, int nq, int do_lapl = 0) {
-  const int NJ = (256 / nq > 0) ? std::min(256 / nq, p) : 1;
-  size_t shb = (size_t)(p * p + 2 * p * nq + 3 * NJ * nq + (do_lapl ? NJ * nq + p * nq : 0)) * sizeof(double);
-  if (shb > 150 * 1024) throw std::runtime_error("radial quadrature too large for the XC density kernel's LDS tables");
-  if (shb > 64 * 1024)  // elements of more than ~24 nodes with the default 5 quadrature points per node
-    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_xc_density_radial, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  return shb;
+// Launch with `bytes` of dynamic LDS: beyond what a kernel may have as it is, its attribute is raised first (the XC radial
+// kernels need that for elements of more than ~24 nodes with the default 5 quadrature points per node)
+template <typename K, typename... Args>
+static void launch_lds(K kernel, dim3 grid, dim3 block, size_t bytes, hipStream_t stream, Args... args) {
+  if (helfem::fock_lds_raise(bytes))
+    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  hipLaunchKernelGGL(kernel, grid, block, bytes, stream, args...);
 }
 
 struct FockAux : Workspace {
@@ -1798,7 +1717,7 @@ static void coulomb_compact(hfg_ctx *ctx, hfg_basis *basis, const double *dPc, d
   a.Paux.resize(2 * nb);
   a.Y.resize(4 * nb);
   a.Jaux.resize(2 * nb);
-  int bs = std::min(256, round_up64(pp));
+  const int bs = fock_block_threads(pp);
   const int *chan = sk.on ? sk.chan : nullptr;  // K1 publishes the channel flags only when it has the density flags
   hipLaunchKernelGGL(k_coulomb_ket, dim3(t->NLM, t->E), dim3(bs), 0, ctx->stream, dPc, t->A, t->E, pp, t->lm_off.p,
                      t->lm_x.p, t->lm_y.p, t->lm_c0.p, t->lm_c2.p, t->NLM, t->LM_ilm.p, ctx->shard_rank, ctx->shard_n, a.Paux.p, sk.on,
@@ -1806,9 +1725,7 @@ static void coulomb_compact(hfg_ctx *ctx, hfg_basis *basis, const double *dPc, d
   hipLaunchKernelGGL(k_coulomb_tei, dim3(t->Nlm * t->E, t->ntt), dim3(bs), 2 * pp * sizeof(double), ctx->stream,
                      t->tei.p, a.Paux.p, t->Ntab, t->NLM, t->E, pp, a.lmpos.p, t->lm_tab.p, ctx->shard_rank, ctx->shard_n,
                      a.Y.p, chan);
-  int nwave = bs / 64;
-  size_t shb = (size_t)(4 * t->E * nwave + 4 * t->E + 2 * t->E) * sizeof(double);
-  hipLaunchKernelGGL(k_coulomb_radial, dim3(t->NLM), dim3(bs), shb, ctx->stream, a.Paux.p, a.Y.p, t->disj.p,
+  hipLaunchKernelGGL(k_coulomb_radial, dim3(t->NLM), dim3(bs), helfem::coulomb_radial_lds(t->E, bs), ctx->stream, a.Paux.p, a.Y.p, t->disj.p,
                      t->LM_ilm.p, t->LM_tab.p, t->LM_fac.p, t->Ntab, t->NLM, t->E, t->p, t->ntt == 4 ? 1 : 0,
                      ctx->shard_rank, ctx->shard_n, a.Jaux.p, chan);
   hipLaunchKernelGGL(k_coulomb_bra, dim3(t->A * t->A, t->E), dim3(bs), 0, ctx->stream, a.Jaux.p, t->A, t->E, pp,
@@ -1836,18 +1753,11 @@ struct CoulombBatchAux : Workspace {
 };
 static CoulombBatchAux &batch_aux_for(hfg_basis *basis) { return basis->dev->work.get<CoulombBatchAux>(WS_COULOMB_BATCH); }
 
-constexpr int CB_MAX_NT = 4;  // column tiles of k_coulomb_tei_mfma at most: 16 result registers of 4 doubles per lane
-
-// Densities per pass over the in-element tables.  k_coulomb_tei_mfma keeps the X panel of a pass, round_up4(p^2) rows of 16
-// columns per column tile, in LDS: as many tiles as fit 64 KB (two workgroups per CU), four at most; where not even one
-// fits (p >= 23), as many as fit the 160 KB of a CU.  A tile holds the +M and -M columns of eight densities.
+// Densities per pass over the in-element tables: the LDS rule of host/fock_plan.h under HELFEM_COULOMB_BATCH_CHUNK
 static int coulomb_batch_chunk(const hfg_dev_tables *t) {
-  const size_t tile = (size_t)((t->p * t->p + 3) & ~3) * 16 * sizeof(double);
-  int nt = (int)std::min<size_t>(CB_MAX_NT, (64 * 1024) / tile);
-  if (nt == 0) nt = (int)std::min<size_t>(CB_MAX_NT, (160 * 1024) / tile);
-  if (nt == 0) throw std::runtime_error("elements of more than 35 nodes: the batched Coulomb kernel's LDS panel does not fit\n");
-  const int forced = helfem::tuning_live().coulomb_batch_chunk;
-  return forced > 0 ? std::min(forced, 8 * nt) : 8 * nt;
+  const helfem::CoulombBatchChunk c = helfem::coulomb_batch_chunk(t->p, helfem::tuning_live().coulomb_batch_chunk);
+  refuse(c.refused);
+  return c.chunk;
 }
 
 template <int NC>
@@ -1860,11 +1770,9 @@ static void launch_tei_cols(hfg_ctx *ctx, const hfg_dev_tables *t, const FockAux
 template <int NT>
 static void launch_tei_mfma(hfg_ctx *ctx, const hfg_dev_tables *t, const FockAux &a, CoulombBatchAux &w, int nb, size_t nbk) {
   const int pp = t->p * t->p;
-  const size_t shb = (size_t)((pp + 3) & ~3) * 16 * NT * sizeof(double);
-  if (shb > 64 * 1024)
-    HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k_coulomb_tei_mfma<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  hipLaunchKernelGGL(k_coulomb_tei_mfma<NT>, dim3(t->Nlm * t->E, t->ntt), dim3(256), shb, ctx->stream, t->tei.p, w.Paux.p, 2 * nbk,
-                     nb, t->Ntab, t->NLM, t->E, pp, a.lmpos.p, t->lm_tab.p, ctx->shard_rank, ctx->shard_n, w.Y.p, 4 * nbk);
+  launch_lds(k_coulomb_tei_mfma<NT>, dim3(t->Nlm * t->E, t->ntt), dim3(256), helfem::coulomb_batch_tile_bytes(t->p) * NT, ctx->stream,
+             t->tei.p, w.Paux.p, 2 * nbk, nb, t->Ntab, t->NLM, t->E, pp, a.lmpos.p, t->lm_tab.p, ctx->shard_rank, ctx->shard_n, w.Y.p,
+             4 * nbk);
 }
 
 // J (compact) from P (compact) for the nb <= coulomb_batch_chunk densities of one pass, both with the stride of one
@@ -1879,26 +1787,25 @@ static void coulomb_batch_compact(hfg_ctx *ctx, hfg_basis *basis, int nb, const 
   w.Paux.resize(nb * 2 * nbk);
   w.Y.resize(nb * 4 * nbk);
   w.Jaux.resize(nb * 2 * nbk);
-  const int bs = std::min(256, round_up64(pp));
+  const int bs = fock_block_threads(pp);
   const unsigned zg = (nb + CB_DB - 1) / CB_DB;
   hipLaunchKernelGGL(k_coulomb_ket_batch, dim3(t->NLM, t->E, zg), dim3(bs), 0, ctx->stream, dPc, nc, nb, t->A, t->E, pp, t->lm_off.p,
                      t->lm_x.p, t->lm_y.p, t->lm_c0.p, t->lm_c2.p, t->NLM, t->LM_ilm.p, ctx->shard_rank, ctx->shard_n, w.Paux.p,
                      2 * nbk);
-  // n = 2 nb columns (+M and -M of every density): matrix cores from n = 16 on, register-blocked FMAs below
   {
     ProfScope ps(ctx, "coulomb_batch_tei");  // the pass over the tables alone (tools/coulomb_batch_time.py)
-    if (nb <= 2) launch_tei_cols<4>(ctx, t, a, w, nb, nbk, bs);
-    else if (nb <= 4) launch_tei_cols<8>(ctx, t, a, w, nb, nbk, bs);
-    else if (nb <= 7) launch_tei_cols<14>(ctx, t, a, w, nb, nbk, bs);
-    else if (nb <= 8) launch_tei_mfma<1>(ctx, t, a, w, nb, nbk);
-    else if (nb <= 16) launch_tei_mfma<2>(ctx, t, a, w, nb, nbk);
-    else if (nb <= 24) launch_tei_mfma<3>(ctx, t, a, w, nb, nbk);
-    else if (nb <= 8 * CB_MAX_NT) launch_tei_mfma<4>(ctx, t, a, w, nb, nbk);
-    else throw std::logic_error("coulomb_batch_compact: pass larger than coulomb_batch_chunk\n");
+    const helfem::CoulombBatchTei v = helfem::coulomb_batch_tei(nb);
+    static_assert(helfem::CB_MAX_NT == 4, "one instantiation of k_coulomb_tei_mfma per tile count the rule can return");
+    if (v.n == 0) throw std::logic_error("coulomb_batch_compact: pass larger than coulomb_batch_chunk\n");
+    if (!v.mfma && v.n == 4) launch_tei_cols<4>(ctx, t, a, w, nb, nbk, bs);
+    else if (!v.mfma && v.n == 8) launch_tei_cols<8>(ctx, t, a, w, nb, nbk, bs);
+    else if (!v.mfma) launch_tei_cols<14>(ctx, t, a, w, nb, nbk, bs);
+    else if (v.n == 1) launch_tei_mfma<1>(ctx, t, a, w, nb, nbk);
+    else if (v.n == 2) launch_tei_mfma<2>(ctx, t, a, w, nb, nbk);
+    else if (v.n == 3) launch_tei_mfma<3>(ctx, t, a, w, nb, nbk);
+    else launch_tei_mfma<4>(ctx, t, a, w, nb, nbk);
   }
-  const int nwave = bs / 64;
-  const size_t shb = (size_t)(4 * t->E * nwave + 4 * t->E + 2 * t->E) * sizeof(double);
-  hipLaunchKernelGGL(k_coulomb_radial_batch, dim3(t->NLM, nb), dim3(bs), shb, ctx->stream, w.Paux.p, 2 * nbk, w.Y.p, 4 * nbk, t->disj.p,
+  hipLaunchKernelGGL(k_coulomb_radial_batch, dim3(t->NLM, nb), dim3(bs), helfem::coulomb_radial_lds(t->E, bs), ctx->stream, w.Paux.p, 2 * nbk, w.Y.p, 4 * nbk, t->disj.p,
                      t->LM_ilm.p, t->LM_tab.p, t->LM_fac.p, t->Ntab, t->NLM, t->E, t->p, t->ntt == 4 ? 1 : 0, ctx->shard_rank,
                      ctx->shard_n, w.Jaux.p, 2 * nbk);
   hipLaunchKernelGGL(k_coulomb_bra_batch, dim3(t->A * t->A, t->E, zg), dim3(bs), 0, ctx->stream, w.Jaux.p, 2 * nbk, nb, t->A, t->E, pp,
@@ -1955,8 +1862,15 @@ struct XCPlan {
   double thr;                    // density threshold
   int maxgrp;                    // largest m group of the angular basis
   size_t NQ, AA, nv;             // radial points, angular pairs, entries of one V / Fo plane
+  int rank, nranks;              // the shard of the radial points that this build computes: the context's
 };
-static XCPlan xc_plan(const hfg_dev_tables *t, int x_func, int c_func, double thr) {
+static int max_group(const hfg_dev_tables *t) {
+  int maxgrp = 0;
+  for (int g = 0; g < t->G; g++) maxgrp = std::max(maxgrp, t->h_grp_off[g + 1] - t->h_grp_off[g]);
+  return maxgrp;
+}
+// (no functional at all, ids 0 and 0: the plain plan of the model potential -- no gradient, no tau, no Laplacian)
+static XCPlan xc_plan(const hfg_ctx *ctx, const hfg_dev_tables *t, int x_func, int c_func, double thr) {
   if (!t->have_xc) throw std::runtime_error("XC grid tables were not uploaded (hfg_basis_upload with ldft,mdft > 0)\n");
   auto either = [&](bool (*is)(int)) { return (x_func > 0 && is(x_func)) || (c_func > 0 && is(c_func)); };
   if ((x_func > 0 && !xc::is_supported(x_func)) || (c_func > 0 && !xc::is_supported(c_func)))
@@ -1973,11 +1887,12 @@ static XCPlan xc_plan(const hfg_dev_tables *t, int x_func, int c_func, double th
   // sigma thresholds, --dftthr 0 would switch the density threshold off.  Far-field densities of an SCF density are
   // rounding noise of the eigensolver at that level (tests/test_gpu_fullsize.py::test_fullsize_xc_without_density_threshold).
   pl.thr = pl.do_tau ? std::max(thr, 1e-40) : thr;
-  pl.maxgrp = 0;
-  for (int g = 0; g < t->G; g++) pl.maxgrp = std::max(pl.maxgrp, t->h_grp_off[g + 1] - t->h_grp_off[g]);
+  pl.maxgrp = max_group(t);
   pl.NQ = (size_t)t->E * t->nq;
   pl.AA = (size_t)t->A * t->A;
   pl.nv = pl.NQ * t->G * t->G * t->ntheta;
+  pl.rank = ctx->shard_rank;
+  pl.nranks = ctx->shard_n;
   return pl;
 }
 
@@ -2004,25 +1919,42 @@ static void xc_buffers(FockAux &a, const XCPlan &pl, int planes) {
 static void xc_density_stage(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, const XCPlan &pl, const double *dPc, double *dV,
                              const FockSkip &sk = FockSkip()) {
   const int A = t->A, E = t->E, p = t->p, nq = t->nq, G = t->G, nth = t->ntheta;
-  hipLaunchKernelGGL(k_xc_density_radial, dim3(A * A, E), dim3(256), xc_density_radial_lds(p, nq, pl.do_lapl), ctx->stream, dPc,
-                     t->rad_B.p, t->rad_dB.p, (const double *)t->rad_L.p, A, E, p, nq, pl.do_grad, pl.do_tau, pl.do_lapl,
-                     ctx->shard_rank, ctx->shard_n, a.D0.p, a.D1.p, a.D2.p, a.D3.p, sk.on);
-  hipLaunchKernelGGL(k_xc_density_theta, dim3((unsigned)pl.NQ, G * G), dim3(std::min(256, round_up64(nth))),
-                     (pl.do_lapl ? 4 : 3) * pl.maxgrp * pl.maxgrp * sizeof(double), ctx->stream, a.D0.p, a.D1.p, (const double *)a.D2.p,
+  launch_lds(k_xc_density_radial, dim3(A * A, E), dim3(256), accepted(helfem::xc_density_radial_lds(p, nq, pl.do_lapl)), ctx->stream, dPc,
+             t->rad_B.p, t->rad_dB.p, t->rad_L.p, A, E, p, nq, pl.do_grad, pl.do_tau, pl.do_lapl, pl.rank, pl.nranks, a.D0.p,
+             a.D1.p, a.D2.p, a.D3.p, sk.on);
+  hipLaunchKernelGGL(k_xc_density_theta, dim3((unsigned)pl.NQ, G * G), dim3(fock_block_threads(nth)),
+                     helfem::xc_density_theta_lds(pl.maxgrp, pl.do_lapl), ctx->stream, a.D0.p, a.D1.p, (const double *)a.D2.p,
                      (const double *)a.D3.p, t->Th.p, t->dTh.p, t->shell_l.p, t->rad_sh.p, A, nth, G, t->grp_off.p, t->grp_shell.p,
-                     pl.do_grad, pl.do_tau, pl.do_lapl, pl.NQ, ctx->shard_rank, ctx->shard_n, dV, nq, sk.gon);
+                     pl.do_grad, pl.do_tau, pl.do_lapl, pl.NQ, pl.rank, pl.nranks, dV, nq, sk.gon);
+}
+
+// X4: the one-pass kernel when its tables fit the LDS the plan allows, the chunked one otherwise
+static void launch_xc_fock_theta(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, const XCPlan &pl, const double *dFo, const FockSkip &sk) {
+  const helfem::XcFockThetaPlan th = helfem::xc_fock_theta_plan(t->ntheta, pl.maxgrp, pl.do_lapl, tuning().xc_lds_limit);
+  refuse(th.refused);
+  const dim3 grid((unsigned)pl.NQ, t->G * t->G), block(256);
+  if (!th.chunked)
+    launch_lds(k_xc_fock_theta, grid, block, th.bytes, ctx->stream, dFo, t->Th.p, t->dTh.p, t->A, t->ntheta, t->G, t->grp_off.p,
+               t->grp_shell.p, pl.do_grad, pl.do_tau, pl.do_lapl, pl.NQ, pl.rank, pl.nranks, a.GA.p, a.GB.p, a.GC.p, a.GL.p,
+               sk.gneed);
+  else if (pl.do_lapl)
+    launch_lds(k_xc_fock_theta_chunked<true>, grid, block, th.bytes, ctx->stream, dFo, t->Th.p, t->dTh.p, t->A, t->ntheta, t->G,
+               t->grp_off.p, t->grp_shell.p, pl.do_grad, pl.do_tau, pl.NQ, pl.rank, pl.nranks, a.GA.p, a.GB.p, a.GC.p, a.GL.p,
+               th.nthc, sk.gneed);
+  else
+    launch_lds(k_xc_fock_theta_chunked<false>, grid, block, th.bytes, ctx->stream, dFo, t->Th.p, t->dTh.p, t->A, t->ntheta, t->G,
+               t->grp_off.p, t->grp_shell.p, pl.do_grad, pl.do_tau, pl.NQ, pl.rank, pl.nranks, a.GA.p, a.GB.p, a.GC.p,
+               (double *)nullptr, th.nthc, sk.gneed);
 }
 
 // Fock stage of one spin: the planes of Fo at dFo -> compact matrix
-static void xc_fock_stage(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, const XCPlan &pl, double *dFo, double *dHc,
+static void xc_fock_stage(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, const XCPlan &pl, const double *dFo, double *dHc,
                           const FockSkip &sk = FockSkip()) {
   const int A = t->A, E = t->E, p = t->p, nq = t->nq;
-  launch_xc_fock_theta(ctx, pl.NQ, t->G, t->ntheta, pl.maxgrp, dFo, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, pl.do_grad,
-                       pl.do_tau, ctx->shard_rank, ctx->shard_n, a.GA.p, a.GB.p, a.GC.p, pl.do_lapl, a.GL.p, sk.gneed);
-  hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))), xc_fock_radial_lds(p, nq, pl.do_lapl),
-                     ctx->stream, a.GA.p, a.GB.p, (const double *)a.GC.p, (const double *)a.GL.p, t->rad_B.p, t->rad_dB.p,
-                     (const double *)t->rad_L.p, t->shell_l.p, t->rad_sh.p, A, E, p, nq, pl.do_grad, pl.do_tau, pl.do_lapl, ctx->shard_rank,
-                     ctx->shard_n, dHc, sk.need);
+  launch_xc_fock_theta(ctx, t, a, pl, dFo, sk);
+  launch_lds(k_xc_fock_radial, dim3(A * A, E), dim3(fock_block_threads(p * p)), accepted(helfem::xc_fock_radial_lds(p, nq, pl.do_lapl)),
+             ctx->stream, a.GA.p, a.GB.p, a.GC.p, a.GL.p, t->rad_B.p, t->rad_dB.p, t->rad_L.p, t->shell_l.p, t->rad_sh.p, A, E, p, nq,
+             pl.do_grad, pl.do_tau, pl.do_lapl, pl.rank, pl.nranks, dHc, sk.need);
 }
 
 // the grid kernel of one build: its EXT instantiation if the plan asks for it, shb bytes of dynamic LDS, one workgroup per
@@ -2030,24 +1962,20 @@ static void xc_fock_stage(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, con
 template <typename K, typename... Tail>
 static void launch_xc_grid(hfg_ctx *ctx, const hfg_dev_tables *t, FockAux &a, const XCPlan &pl, K k_ext, K k_plain, size_t shb,
                            int x_func, int c_func, Tail... tail) {
-  K k = pl.ext ? k_ext : k_plain;
-  if (shb > 64 * 1024) HFG_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-  hipLaunchKernelGGL(k, dim3((unsigned)pl.NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p, t->th_s.p, t->th_w.p,
-                     t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, t->G, t->ntheta, t->nphi, t->Rhalf, t->geom, x_func, c_func, pl.do_grad,
-                     pl.do_tau, pl.do_lapl, pl.thr, pl.NQ, ctx->shard_rank, ctx->shard_n, a.Fo.p, a.partial.p, tail...);
+  launch_lds(pl.ext ? k_ext : k_plain, dim3((unsigned)pl.NQ), dim3(256), shb, ctx->stream, a.V.p, t->rad_w.p, t->rad_sh.p, t->th_s.p,
+             t->th_w.p, t->grp_m.p, t->cosd.p, t->sind.p, t->Dmax, t->G, t->ntheta, t->nphi, t->Rhalf, t->geom, x_func, c_func, pl.do_grad,
+             pl.do_tau, pl.do_lapl, pl.thr, pl.NQ, pl.rank, pl.nranks, a.Fo.p, a.partial.p, tail...);
 }
 
 static void xc_compact(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPc, double *dHc, double *dScal,
                        double thr, const FockSkip &sk = FockSkip()) {
   hfg_dev_tables *t = tables_of(ctx, basis);
-  const XCPlan pl = xc_plan(t, x_func, c_func, thr);
+  const XCPlan pl = xc_plan(ctx, t, x_func, c_func, thr);
   FockAux &a = aux_for(ctx, basis);
   const int npl = pl.do_lapl ? 6 : 5;  // planes of V and Fo, and of the kernel's LDS potentials
   xc_buffers(a, pl, npl);
   xc_density_stage(ctx, t, a, pl, dPc, a.V.p, sk);
-  size_t shb = (size_t)(npl * t->ntheta * t->nphi + 3 * 4) * sizeof(double);
-  if (pl.do_lapl && shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the grid kernel's LDS planes");
-  launch_xc_grid(ctx, t, a, pl, k_xc_grid<true>, k_xc_grid<false>, shb, x_func, c_func);
+  launch_xc_grid(ctx, t, a, pl, k_xc_grid<true>, k_xc_grid<false>, accepted(helfem::xc_grid_lds(npl, t->ntheta, t->nphi)), x_func, c_func);
   xc_fock_stage(ctx, t, a, pl, a.Fo.p, dHc, sk);
   hipLaunchKernelGGL(k_xc_sum_partials, dim3(1), dim3(64), 0, ctx->stream, a.partial.p, pl.NQ, dScal);
   HFG_HIP_CHECK(hipGetLastError());
@@ -2179,14 +2107,11 @@ void xc_fock_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const d
   HFG_HIP_CHECK(hipGetLastError());
 }
 
-// dynamic LDS of k_xc_grid_pol and rowc, the theta rows that go through it per pass
-static size_t xc_grid_pol_lds(const hfg_dev_tables *t, const XCPlan &pl, int *rowc) {
-  const int npot2 = pl.do_lapl ? 12 : (pl.do_tau ? 10 : 8);  // LDS potential planes, both spins
-  *rowc = t->ntheta;
-  while ((size_t)(npot2 * *rowc * t->nphi + 3 * 4) * sizeof(double) > tuning().xc_lds_limit && *rowc > 1) *rowc = (*rowc + 1) / 2;
-  const size_t shb = (size_t)(npot2 * *rowc * t->nphi + 3 * 4) * sizeof(double);
-  if (shb > 150 * 1024) throw std::runtime_error("XC angular grid too large for the polarised grid kernel's LDS tile");
-  return shb;
+// dynamic LDS of k_xc_grid_pol and the theta rows that go through it per pass
+static helfem::XcGridPolPlan xc_grid_pol_plan(const hfg_dev_tables *t, const XCPlan &pl) {
+  const helfem::XcGridPolPlan g = helfem::xc_grid_pol_plan(t->ntheta, t->nphi, pl.do_tau, pl.do_lapl, tuning().xc_lds_limit);
+  refuse(g.refused);
+  return g;
 }
 
 // spin-polarised XC: Hc_a, Hc_b (compact) from Pc_a, Pc_b (compact); dScal = (Exc, Nel, 0).  sk: flags that hold for both
@@ -2194,14 +2119,13 @@ static size_t xc_grid_pol_lds(const hfg_dev_tables *t, const XCPlan &pl, int *ro
 static void xc_compact_pol(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dPca, const double *dPcb,
                            double *dHca, double *dHcb, double *dScal, double thr, const FockSkip &sk = FockSkip()) {
   hfg_dev_tables *t = tables_of(ctx, basis);
-  const XCPlan pl = xc_plan(t, x_func, c_func, thr);
+  const XCPlan pl = xc_plan(ctx, t, x_func, c_func, thr);
   FockAux &a = aux_for(ctx, basis);
   const int npl = pl.do_lapl ? 6 : (pl.do_tau ? 5 : 3);  // planes of V and Fo per spin
   xc_buffers(a, pl, 2 * npl);
   for (int sp = 0; sp < 2; sp++) xc_density_stage(ctx, t, a, pl, sp ? dPcb : dPca, a.V.p + (size_t)sp * npl * pl.nv, sk);
-  int rowc;
-  const size_t shb = xc_grid_pol_lds(t, pl, &rowc);
-  launch_xc_grid(ctx, t, a, pl, k_xc_grid_pol<true>, k_xc_grid_pol<false>, shb, x_func, c_func, rowc);
+  const helfem::XcGridPolPlan g = xc_grid_pol_plan(t, pl);
+  launch_xc_grid(ctx, t, a, pl, k_xc_grid_pol<true>, k_xc_grid_pol<false>, g.bytes, x_func, c_func, g.rowc);
   for (int sp = 0; sp < 2; sp++) xc_fock_stage(ctx, t, a, pl, a.Fo.p + (size_t)sp * npl * pl.nv, sp ? dHcb : dHca, sk);
   hipLaunchKernelGGL(k_xc_sum_partials, dim3(1), dim3(64), 0, ctx->stream, a.partial.p, pl.NQ, dScal);
   HFG_HIP_CHECK(hipGetLastError());
@@ -2228,29 +2152,21 @@ void xc_fock_pol_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, con
 void model_potential_dev(hfg_ctx *ctx, hfg_basis *basis, int kind1, int Z1, double d1, double H1, int kind2, int Z2,
                          double d2, double H2, double *dH) {
   hfg_dev_tables *t = tables_of(ctx, basis);
-  if (!t->have_xc) throw std::runtime_error("XC grid tables were not uploaded (hfg_basis_upload with ldft,mdft > 0)\n");
+  XCPlan pl = xc_plan(ctx, t, 0, 0, 0.0);  // the plain plan: the Fock stage reads the one plane that k_mp_fill writes
+  pl.rank = 0, pl.nranks = 1;              // the whole matrix on every rank: the guess is not summed over them
   for (int k : {kind1, kind2})
     if (k != 0 && k != 1 && k != 3) throw std::logic_error("Unsupported guess\n");
   if ((kind1 == 1 && !(d1 > 0.0)) || (kind2 == 1 && !(d2 > 0.0)))
     throw std::logic_error("GSZ guess: the screening length d_Z must be given\n");
   FockAux &a = aux_for(ctx, basis);
-  const int A = t->A, E = t->E, p = t->p, nq = t->nq, G = t->G, nth = t->ntheta, nphi = t->nphi;
-  const size_t NQ = (size_t)E * nq, AA = (size_t)A * A;
-  const size_t nc = (size_t)A * A * E * p * p;
-  a.Jc.resize(nc);
-  a.GA.resize(NQ * AA);
-  a.GB.resize(NQ * AA);
-  a.Fo.resize(5 * NQ * G * G * nth);
-  int maxgrp = 0;
-  for (int g = 0; g < G; g++) maxgrp = std::max(maxgrp, t->h_grp_off[g + 1] - t->h_grp_off[g]);
+  a.Jc.resize(pl.AA * t->E * t->p * t->p);
+  a.GA.resize(pl.NQ * pl.AA);
+  a.GB.resize(pl.NQ * pl.AA);
+  a.Fo.resize(5 * pl.nv);
   DevModelPot p1{kind1, Z1, d1, H1}, p2{kind2, Z2, d2, H2};
-  hipLaunchKernelGGL(k_mp_fill, dim3((unsigned)NQ), dim3(256), 0, ctx->stream, t->rad_w.p, t->rad_sh.p, t->th_c.p, t->th_s.p,
-                     t->th_w.p, G, nth, nphi, t->Rhalf, t->geom, p1, p2, a.Fo.p);
-  launch_xc_fock_theta(ctx, NQ, G, nth, maxgrp, a.Fo.p, t->Th.p, t->dTh.p, A, t->grp_off.p, t->grp_shell.p, 0, 0, 0, 1, a.GA.p, a.GB.p,
-                       (double *)nullptr);
-  hipLaunchKernelGGL(k_xc_fock_radial, dim3(A * A, E), dim3(std::min(256, round_up64(p * p))),
-                     xc_fock_radial_lds(p, nq), ctx->stream, a.GA.p, a.GB.p, (const double *)nullptr, (const double *)nullptr, t->rad_B.p,
-                     t->rad_dB.p, (const double *)nullptr, t->shell_l.p, t->rad_sh.p, A, E, p, nq, 0, 0, 0, 0, 1, a.Jc.p, (const int *)nullptr);
+  hipLaunchKernelGGL(k_mp_fill, dim3((unsigned)pl.NQ), dim3(256), 0, ctx->stream, t->rad_w.p, t->rad_sh.p, t->th_c.p, t->th_s.p,
+                     t->th_w.p, t->G, t->ntheta, t->nphi, t->Rhalf, t->geom, p1, p2, a.Fo.p);
+  xc_fock_stage(ctx, t, a, pl, a.Fo.p, a.Jc.p);
   scatter_dense(ctx, basis, a.Jc.p, dH);
   HFG_HIP_CHECK(hipGetLastError());
 }
@@ -2294,54 +2210,76 @@ void set_fock_blocks(hfg_ctx *ctx, hfg_basis *basis, const int *dBlockId) {
   ctx->fock_need_tables = t;
 }
 
+// J beside XC, for the restricted and the unrestricted compact build.  J and the XC matrices are independent given the
+// compact densities: the Coulomb kernels (one of them streams the 1 GB of primitive integrals: HBM-bound) run on the
+// context's side stream beside the XC kernels (LDS- and latency-bound); HELFEM_FOCK_OVERLAP=0, or a context that has given
+// its side stream up: one after the other on the main stream.  gather() enqueues the compact densities and returns their
+// flags, coulomb(sk) and xc(sk) enqueue on ctx->stream, combine() adds what the two left.
+template <typename Gather, typename Coulomb, typename XC, typename Combine>
+static void fock_j_beside_xc(hfg_ctx *ctx, Gather gather, Coulomb coulomb, XC xc, Combine combine) {
+  if (!(tuning().fock_overlap && !ctx->avoid_side)) {
+    FockSkip sk;
+    {
+      ProfScope ps(ctx, "coulomb");
+      sk = gather();
+      coulomb(sk);
+    }
+    ProfScope ps(ctx, "xc");
+    xc(sk);
+    combine();
+    HFG_HIP_CHECK(hipGetLastError());
+    return;
+  }
+  const hipStream_t main = ctx->stream, q = ctx->side();
+  const FockSkip sk = gather();  // (the flags go under the event that guards the compact densities)
+  HFG_HIP_CHECK(hipEventRecord(ctx->side_ev[0], main));
+  HFG_HIP_CHECK(hipStreamWaitEvent(q, ctx->side_ev[0], 0));
+  {
+    struct OnStream {  // ctx->stream is q in this scope and main again behind it, also when coulomb() throws
+      hfg_ctx *ctx;
+      hipStream_t back;
+      ~OnStream() { ctx->stream = back; }
+    } on_side{ctx, main};
+    ctx->stream = q;
+    ProfScope ps(ctx, "coulomb");  // (its events go to the side stream with the kernels)
+    coulomb(sk);
+  }
+  HFG_HIP_CHECK(hipEventRecord(ctx->side_ev[1], q));
+  ProfScope ps(ctx, "xc");
+  try {
+    xc(sk);
+  } catch (...) {  // J is under way into the caller's buffer: whatever the caller enqueues after the error comes behind it
+    (void)hipStreamWaitEvent(main, ctx->side_ev[1], 0);
+    throw;
+  }
+  HFG_HIP_CHECK(hipStreamWaitEvent(main, ctx->side_ev[1], 0));
+  combine();
+  HFG_HIP_CHECK(hipGetLastError());
+}
+
 // This shard's part of J + XC in the compact layout (to be summed over ranks), dScal = partial (Exc, Nel, 0)
 void fock_compact_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func, const double *dP, double *dFc,
                       double *dScal, double thr) {
-  hfg_dev_tables *t = tables_of(ctx, basis);
+  tables_of(ctx, basis);
   FockAux &a = aux_for(ctx, basis);
   const size_t nc = fock_compact_size(basis);
   a.Pc.resize(nc);
   a.Jc.resize(nc);
-  // J and the XC matrix are independent given the compact density: the Coulomb kernels (one of them streams the 1 GB of
-  // primitive integrals: HBM-bound) run on the context's side stream beside the XC kernels (LDS- and latency-bound)
-  // -- HELFEM_FOCK_OVERLAP=0: one after the other on the main stream
-  if ((x_func > 0 || c_func > 0) && tuning().fock_overlap && !ctx->avoid_side) {
-    hipStream_t main = ctx->stream, q = ctx->side();
-    const FockSkip sk = gather_compact_flagged(ctx, basis, dP, a.Pc.p, true);  // (the flags go under the event that guards Pc)
-    HFG_HIP_CHECK(hipEventRecord(ctx->side_ev[0], main));
-    HFG_HIP_CHECK(hipStreamWaitEvent(q, ctx->side_ev[0], 0));
-    ctx->stream = q;
-    try {
-      ProfScope ps(ctx, "coulomb");  // (its events go to the side stream with the kernels)
+  if (!(x_func > 0 || c_func > 0)) {
+    {
+      ProfScope ps(ctx, "coulomb");
+      const FockSkip sk = gather_compact_flagged(ctx, basis, dP, a.Pc.p, true);
       coulomb_compact(ctx, basis, a.Pc.p, dFc, sk);
-    } catch (...) {
-      ctx->stream = main;
-      throw;
     }
-    ctx->stream = main;
-    HFG_HIP_CHECK(hipEventRecord(ctx->side_ev[1], q));
-    ProfScope ps(ctx, "xc");
-    xc_compact(ctx, basis, x_func, c_func, a.Pc.p, a.Jc.p, dScal, thr, sk);
-    HFG_HIP_CHECK(hipStreamWaitEvent(main, ctx->side_ev[1], 0));
-    hipLaunchKernelGGL(k_add_inplace, dim3(2048), dim3(256), 0, ctx->stream, dFc, a.Jc.p, nc);
+    HFG_HIP_CHECK(hipMemsetAsync(dScal, 0, 3 * sizeof(double), ctx->stream));
     HFG_HIP_CHECK(hipGetLastError());
     return;
   }
-  FockSkip sk;
-  {
-    ProfScope ps(ctx, "coulomb");
-    sk = gather_compact_flagged(ctx, basis, dP, a.Pc.p, true);
-    coulomb_compact(ctx, basis, a.Pc.p, dFc, sk);
-  }
-  if (x_func > 0 || c_func > 0) {
-    ProfScope ps(ctx, "xc");
-    xc_compact(ctx, basis, x_func, c_func, a.Pc.p, a.Jc.p, dScal, thr, sk);
-    hipLaunchKernelGGL(k_add_inplace, dim3(2048), dim3(256), 0, ctx->stream, dFc, a.Jc.p, nc);
-  } else {
-    HFG_HIP_CHECK(hipMemsetAsync(dScal, 0, 3 * sizeof(double), ctx->stream));
-  }
-  (void)t;
-  HFG_HIP_CHECK(hipGetLastError());
+  fock_j_beside_xc(
+      ctx, [&] { return gather_compact_flagged(ctx, basis, dP, a.Pc.p, true); },
+      [&](const FockSkip &sk) { coulomb_compact(ctx, basis, a.Pc.p, dFc, sk); },
+      [&](const FockSkip &sk) { xc_compact(ctx, basis, x_func, c_func, a.Pc.p, a.Jc.p, dScal, thr, sk); },
+      [&] { hipLaunchKernelGGL(k_add_inplace, dim3(2048), dim3(256), 0, ctx->stream, dFc, a.Jc.p, nc); });
 }
 
 // F = enforce_fock_symmetry(H0 + J + XC) from the (rank-summed) compact matrix
@@ -2362,10 +2300,7 @@ void fock_compact_pol_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func
                           double *dFc, double *dScal, double thr) {
   hfg_dev_tables *t = tables_of(ctx, basis);
   const bool with_xc = x_func > 0 || c_func > 0;
-  if (with_xc) {  // what the XC build would refuse is refused before the first launch
-    int rowc;
-    (void)xc_grid_pol_lds(t, xc_plan(t, x_func, c_func, thr), &rowc);
-  }
+  if (with_xc) xc_grid_pol_plan(t, xc_plan(ctx, t, x_func, c_func, thr));  // what the XC build would refuse is refused before the first launch
   FockAux &a = aux_for(ctx, basis);
   const size_t nc = fock_compact_size(basis);
   a.Pc.resize(nc);
@@ -2382,44 +2317,11 @@ void fock_compact_pol_dev(hfg_ctx *ctx, hfg_basis *basis, int x_func, int c_func
   }
   a.Jc.resize(nc);
   a.Jc2.resize(nc);
-  // J beside the XC kernels on the side stream, as in fock_compact_dev
-  if (tuning().fock_overlap && !ctx->avoid_side) {
-    hipStream_t main = ctx->stream, q = ctx->side();
-    const FockSkip sk = gather_compact_pol_flagged(ctx, basis, dPa, dPb, true);
-    HFG_HIP_CHECK(hipEventRecord(ctx->side_ev[0], main));
-    HFG_HIP_CHECK(hipStreamWaitEvent(q, ctx->side_ev[0], 0));
-    ctx->stream = q;
-    try {
-      ProfScope ps(ctx, "coulomb");
-      coulomb_compact(ctx, basis, a.Pc3.p, dJc, sk);
-    } catch (...) {
-      ctx->stream = main;
-      throw;
-    }
-    ctx->stream = main;
-    HFG_HIP_CHECK(hipEventRecord(ctx->side_ev[1], q));
-    ProfScope ps(ctx, "xc");
-    try {
-      xc_compact_pol(ctx, basis, x_func, c_func, a.Pc.p, a.Pc2.p, a.Jc.p, a.Jc2.p, dScal, thr, sk);
-    } catch (...) {  // J is under way into dFc: whatever the caller enqueues after the error comes behind it
-      (void)hipStreamWaitEvent(main, ctx->side_ev[1], 0);
-      throw;
-    }
-    HFG_HIP_CHECK(hipStreamWaitEvent(main, ctx->side_ev[1], 0));
-    hipLaunchKernelGGL(k_fock_combine_pol, dim3(2048), dim3(256), 0, ctx->stream, dFc, a.Jc.p, a.Jc2.p, nc);
-    HFG_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  FockSkip sk;
-  {
-    ProfScope ps(ctx, "coulomb");
-    sk = gather_compact_pol_flagged(ctx, basis, dPa, dPb, true);
-    coulomb_compact(ctx, basis, a.Pc3.p, dJc, sk);
-  }
-  ProfScope ps(ctx, "xc");
-  xc_compact_pol(ctx, basis, x_func, c_func, a.Pc.p, a.Pc2.p, a.Jc.p, a.Jc2.p, dScal, thr, sk);
-  hipLaunchKernelGGL(k_fock_combine_pol, dim3(2048), dim3(256), 0, ctx->stream, dFc, a.Jc.p, a.Jc2.p, nc);
-  HFG_HIP_CHECK(hipGetLastError());
+  fock_j_beside_xc(
+      ctx, [&] { return gather_compact_pol_flagged(ctx, basis, dPa, dPb, true); },
+      [&](const FockSkip &sk) { coulomb_compact(ctx, basis, a.Pc3.p, dJc, sk); },
+      [&](const FockSkip &sk) { xc_compact_pol(ctx, basis, x_func, c_func, a.Pc.p, a.Pc2.p, a.Jc.p, a.Jc2.p, dScal, thr, sk); },
+      [&] { hipLaunchKernelGGL(k_fock_combine_pol, dim3(2048), dim3(256), 0, ctx->stream, dFc, a.Jc.p, a.Jc2.p, nc); });
 }
 
 // fock_finish_dev for the two slabs of fock_compact_pol_dev, one launch

@@ -37,7 +37,8 @@ if __name__ == "__main__":
     lm = basis.lm_map()
     NLM = sum(1 if M == 0 else 2 for _, M in lm)
     table_bytes = 4 * len(lm) * E * pp * pp * 8
-    tile = ((pp + 3) // 4 * 4) * 16 * 8  # coulomb_batch_chunk (hip/fock.hip): LDS column tiles of eight densities
+    # the rule is coulomb_batch_chunk of helfem_amd/csrc/host/fock_plan.h (it owns it; this restates it for the printout)
+    tile = ((pp + 3) // 4 * 4) * 16 * 8  # LDS column tiles of eight densities
     chunk = 8 * (min(4, 65536 // tile) or min(4, 163840 // tile))
     print("%s: Nbf %d, %d elements of %d nodes, %d (L,|M|) channels, tables %.3f GB, %d densities per pass" % (
         a.workload, N, E, w["nnodes"], len(lm), table_bytes / 1e9, chunk))
