@@ -316,6 +316,48 @@ class Context(object):
                       ctypes.c_void_p, ctypes.c_void_p]
         _check(f(self.h, N, S.data_ptr(), Ca.data_ptr(), na, Cb.data_ptr(), nb, Fa.data_ptr(), Fb.data_ptr()))
 
+    def occupy_blocks(self, E, C, blockid, occupations, out=None):
+        """hfg_occupy_blocks_devptr on torch tensors of this context's device: fractional occupations by symmetry block.  E
+        (ncols) and C (N x ncols, column-major, contiguous float64) as the blocked eigensolve leaves them; blockid (N, int32):
+        the block of every row; occupations: one list of values in [0, 1] per block, lowest level first.  Slot
+        sum(len(occupations[:b])) + k receives the k-th lowest column of block b times the square root of its occupation.
+        Returns (Cocc, Eocc, Focc): N x nslots, nslots, nslots; out = (Cocc, Eocc, Focc) writes into tensors at hand.
+        Queued on the context's stream.  The host waits only when something is new: the first call with a blockid tensor
+        reads it back once to count the rows of every block (the refusal of more occupations than a block has rows needs
+        them), and occupation lists that differ from the previous call's drain the stream before they are staged.  The
+        counts are kept per (address, N, number of blocks) of blockid: after writing into a blockid tensor in place, or
+        when a new tensor may have received the address of a freed one, call forget_block_ids() first -- stale counts
+        refuse a valid call or let one pass whose surplus slots then come back as zero columns of energy 0."""
+        import torch
+        N = int(blockid.numel())
+        ncols = int(E.numel())
+        occ_ptr = np.zeros(len(occupations) + 1, dtype=np.int64)
+        occ_ptr[1:] = np.cumsum([len(o) for o in occupations])
+        occ = np.ascontiguousarray(np.concatenate([np.asarray(o, dtype=np.float64).ravel() for o in occupations] + [np.zeros(0)]))
+        nslots = int(occ_ptr[-1])
+        if str(blockid.dtype) != "torch.int32" or not (blockid.is_cuda and blockid.is_contiguous()):
+            raise ValueError("Context.occupy_blocks: blockid must be a contiguous int32 tensor on the device")
+        if out is None:
+            f64 = dict(dtype=torch.float64, device=C.device)
+            out = (torch.zeros(N * max(nslots, 1), **f64), torch.zeros(max(nslots, 1), **f64), torch.zeros(max(nslots, 1), **f64))
+        for t, count, what in ((E, ncols, "E"), (C, N * ncols, "C"), (out[0], N * nslots, "Cocc"), (out[1], nslots, "Eocc"),
+                               (out[2], nslots, "Focc")):
+            if t is None or not (t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float64" and t.numel() >= count):
+                raise ValueError("Context.occupy_blocks: %s must be a contiguous float64 tensor on the device with at least %d elements"
+                                 % (what, count))
+        f = lib().hfg_occupy_blocks_devptr
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                      c_i64_p, c_double_p] + [ctypes.c_void_p] * 3
+        _check(f(self.h, N, ncols, E.data_ptr(), C.data_ptr(), blockid.data_ptr(), len(occupations), occ_ptr.ctypes.data_as(c_i64_p),
+                 _p(occ), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr()))
+        return out
+
+    def forget_block_ids(self):
+        """drop the rows per block counted for the blockid tensor that occupy_blocks saw last (hfg_occupy_forget_blocks)"""
+        f = lib().hfg_occupy_forget_blocks
+        f.argtypes = [ctypes.c_void_p]
+        _check(f(self.h))
+
 
 _default_ctx = None
 
@@ -1950,3 +1992,87 @@ class DeviceROHFStep(DeviceUSCFStep):
             raise RuntimeError("DeviceROHFStep: the constraint needs the orbitals the densities were formed from "
                                "(set_density with Ca and Cb, or start from the core guess)")
         self.ctx.cuhf_update(self.S, self.Ca, self.nela, self.Cb, self.nelb, self.Fa, self.Fb)
+
+
+def spherical_occupations(basis, shells):
+    """Occupations per spin orbital of a spherically averaged atom, one list per (l, m) block of basis.get_sym_idx(2): what
+    DeviceFracSCFStep takes.  shells = {l: [electrons in the 1st, 2nd, ... shell of that l]}, e.g. carbon {0: [2, 2], 1: [2]}:
+    the n electrons of a shell are spread evenly over its 2 (2l + 1) spin orbitals, so every (l, m) block gets the list
+    n / (2 (2l + 1)).  ValueError for an l the basis lacks, an l whose m values in the basis do not hold all of -l .. l, a
+    shell with more than 2 (2l + 1) electrons, and a diatomic basis (whose blocks carry no l)."""
+    if not isinstance(basis, AtomicTwoDBasis):
+        raise ValueError("spherical_occupations: an atomic basis is needed: the blocks of a diatomic basis carry no l")
+    lm = list(zip(basis.lval, basis.mval))
+    for l, electrons in shells.items():
+        l = int(l)
+        if l < 0 or l not in basis.lval:
+            raise ValueError("spherical_occupations: l = %d is beyond the basis (l = 0 .. %d)" % (l, max(basis.lval)))
+        missing = [m for m in range(-l, l + 1) if (l, m) not in lm]
+        if missing:
+            raise ValueError("spherical_occupations: the basis lacks m = %s of l = %d: a shell cannot be spread over all of m = -l .. l"
+                             % (", ".join(str(m) for m in missing), l))
+        for n in electrons:
+            if not 0.0 <= float(n) <= 2 * (2 * l + 1):
+                raise ValueError("spherical_occupations: %g electrons in a shell of l = %d, which holds 0 to %d" % (n, l, 2 * (2 * l + 1)))
+    by_l = {int(l): [float(n) / (2 * (2 * int(l) + 1)) for n in electrons] for l, electrons in shells.items()}
+    return [list(by_l.get(l, [])) for l, _ in lm]
+
+
+class DeviceFracSCFStep(DeviceSCFStep):
+    """DeviceSCFStep with fractional occupations by symmetry block (the occupations of the reference's sadatom program;
+    spherical_occupations gives those of a spherically averaged atom).  occupations: one list of floats in [0, 1] per block
+    of basis.get_sym_idx(symmetry), lowest level first, each the occupation per spin orbital: the total density is
+    P = 2 sum_i f_i c_i c_i^T.  After every eigensolve Context.occupy_blocks puts sqrt(f_i) c_i into the fixed slot of (block,
+    level) of the N x nslots panel Cocc, on the device; P/2 = Cocc Cocc^T, so the panel stands wherever the occupied
+    orbitals stand in the restricted step, and nocc is nslots: the density build, the factors handed to the exact exchange
+    and the rank-nslots DIIS error (which forms X^T (F C C^T S - S C C^T F) X from the columns and nowhere assumes them
+    orthonormal).  More than 64 slots take the dense paths, as more than 64 orbitals do.  The class overrides only those
+    three hand-overs and set_density, whose optional C is the panel (N x nslots, P/2 = C C^T).  occupied() returns the
+    slots' energies and occupations."""
+
+    def __init__(self, basis, x_func, c_func, ldft, mdft, occupations, symmetry=2, **kw):
+        nblk = len(basis.get_sym_idx(symmetry))
+        if len(occupations) != nblk:
+            raise ValueError("DeviceFracSCFStep: %d occupation lists for %d symmetry blocks" % (len(occupations), nblk))
+        self.occupations = [[float(f) for f in o] for o in occupations]
+        if any(not 0.0 <= f <= 1.0 for o in self.occupations for f in o):
+            raise ValueError("DeviceFracSCFStep: occupations per spin orbital lie in [0, 1]")
+        nslots = sum(len(o) for o in self.occupations)
+        if nslots < 1:
+            raise ValueError("DeviceFracSCFStep: no occupation given")
+        super(DeviceFracSCFStep, self).__init__(basis, x_func, c_func, ldft, mdft, nslots, symmetry=symmetry, **kw)
+        f64 = dict(dtype=self.torch.float64, device=self.dev)
+        self.Cocc = self.torch.zeros(self.N * nslots, **f64)
+        self.Eocc = self.torch.zeros(nslots, **f64)
+        self.Focc = self.torch.zeros(nslots, **f64)
+
+    def set_density(self, P, C=None):
+        """total density P = 2 sum_i f_i c_i c_i^T; C (N x nslots, optional): the scaled columns sqrt(f_i) c_i it was formed
+        from, slot by slot, which the exact exchange and the DIIS error take as the factors of P/2"""
+        super(DeviceFracSCFStep, self).set_density(P, None)
+        self.have_C = C is not None
+        if C is not None:
+            self.Cocc.copy_(self.torch.from_numpy(np.asfortranarray(C[:, :self.nocc]).ravel(order="F").copy()))
+
+    def exchange(self):
+        """K[P/2] into self.K, from the factors Cocc"""
+        self.torch.mul(self.P, 0.5, out=self.Pa)
+        self._build_K(self.Pa, self.Cocc, ctypes.c_int64(self.nocc), self.K)
+
+    def density(self):
+        """Cocc from (E, C) by the occupations, then P = Cocc Cocc^T = sum_i f_i c_i c_i^T"""
+        self.ctx.occupy_blocks(self.E, self.C, self.blockid, self.occupations, out=(self.Cocc, self.Eocc, self.Focc))
+        _check(lib().hfg_form_density_dev(self.ctx.h, ctypes.c_int64(self.N), ctypes.c_int64(self.nocc), self._ptr(self.Cocc),
+                                          ctypes.c_int64(self.nocc), self._ptr(self.P)))
+        self.have_density = True
+
+    def _diis_update(self, diis, E):
+        Pa = self.torch.mul(self.P, 0.5, out=self._nn_buffer("Pa"))
+        if self.have_C:
+            return diis.update(E, self.F, Pa, self.Cocc, self.nocc)
+        return diis.update(E, self.F, Pa)
+
+    def occupied(self):
+        """(E, f) of the slots, block after block and lowest level first, as numpy arrays: one read-back"""
+        v = self.torch.stack((self.Eocc, self.Focc)).cpu().numpy()
+        return v[0].copy(), v[1].copy()

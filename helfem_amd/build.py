@@ -20,7 +20,7 @@ OBJDIR = os.path.join(ROOT, "helfem_amd", "build")
 
 HOST_SRCS = ["host/fem.cpp", "host/special.cpp", "host/atomic_basis.cpp", "host/diatomic_basis.cpp", "host/scf.cpp", "host/diis.cpp", "host/checkpoint.cpp", "host/dftfuncs.cpp", "host/tuning.cpp"]
 HIP_SRCS = ["hip/tables.cpp", "hip/capi.cpp", "hip/fock.hip", "hip/exchange.hip", "hip/exchange_lr.hip", "hip/gemm.hip", "hip/eig.hip", "hip/dc.hip", "hip/stsel.hip", "hip/trd.hip", "hip/trdp.hip",
-            "hip/misc.hip", "hip/scf_gpu.cpp", "hip/scf_device.hip", "hip/diis_dev.hip", "hip/cuhf_dev.hip", "hip/tei_dev.hip", "hip/rs_tei_dev.hip", "hip/exchange_mix.hip"]
+            "hip/misc.hip", "hip/scf_gpu.cpp", "hip/scf_device.hip", "hip/diis_dev.hip", "hip/cuhf_dev.hip", "hip/tei_dev.hip", "hip/rs_tei_dev.hip", "hip/exchange_mix.hip", "hip/occupy.hip"]
 
 
 # Kernel arguments preloaded into SGPRs at wave launch (gfx940+): every launch of the eigensolver's dependent chains

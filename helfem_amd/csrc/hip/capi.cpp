@@ -900,6 +900,17 @@ int hfg_form_density_dev(hfg_ctx *ctx, int64_t N, int64_t ncols, const double *d
   HFG_TRY form_density_dev(ctx, (int)N, (int)ncols, dC, (int)nocc, dP);
   HFG_CATCH
 }
+int hfg_occupy_blocks_devptr(hfg_ctx *ctx, int64_t N, int64_t ncols, const double *dE, const double *dC, const int *dBlockId, int nblk,
+                             const int64_t *occ_ptr, const double *occ, double *dCocc, double *dEocc, double *dFocc) {
+  HFG_TRY occupy_blocks_dev(ctx, N, ncols, dE, dC, dBlockId, nblk, occ_ptr, occ, dCocc, dEocc, dFocc);
+  HFG_CATCH
+}
+int hfg_occupy_forget_blocks(hfg_ctx *ctx) {
+  HFG_TRY
+  if (!ctx) throw std::logic_error("hfg_occupy_forget_blocks: null context\n");
+  occupy_forget_blocks(ctx);
+  HFG_CATCH
+}
 int hfg_gemm_dev(hfg_ctx *ctx, int tA, int tB, int64_t m, int64_t n, int64_t k, const double *dA, int64_t lda,
                  const double *dB, int64_t ldb, double *dC, int64_t ldc) {
   HFG_TRY gemm_dev(ctx, tA != 0, tB != 0, (int)m, (int)n, (int)k, 1.0, dA, (int)lda, dB, (int)ldb, 0.0, dC, (int)ldc);

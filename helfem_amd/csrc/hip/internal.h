@@ -175,6 +175,13 @@ void cuhf_lowrank_dev(hfg_ctx *ctx, int N, const double *dS, const double *dCa, 
 void cuhf_dense_dev(hfg_ctx *ctx, int N, int n, const double *dP, const double *dSh, const double *dSinvh, int nocca, int noccb,
                     double *dFa, double *dFb);  // cuhf_dev.hip
 
+// occupy.hip: fractional occupations by symmetry block (hfg_occupy_blocks_devptr)
+void occupy_blocks_dev(hfg_ctx *ctx, int64_t N, int64_t ncols, const double *dE, const double *dC, const int *dBlockId, int nblk,
+                       const int64_t *occ_ptr, const double *occ, double *dCocc, double *dEocc, double *dFocc);  // occupy.hip
+
+// the next call counts the rows per block anew (hfg_occupy_forget_blocks)
+void occupy_forget_blocks(hfg_ctx *ctx);  // occupy.hip
+
 // scf_device.hip
 helfem::scf::Result scf_device_loop(hfg_ctx *ctx, hfg_basis *hb, const helfem::scf::Options &opt, int nel, double Enucr, int symm,
                                     const std::vector<std::vector<size_t> > &dsym, int ldft, int mdft,

@@ -14,7 +14,7 @@ struct Workspace {
 };
 
 // the slots of a context and of a table set; the structs stay in the files named
-enum CtxSlot { WS_EIG, WS_DC, WS_STSEL, WS_TRD, WS_TRDP, WS_CUHF, WS_CTX_SLOTS };  // eig.hip, dc.hip, stsel.hip, trd.hip, trdp.hip, cuhf_dev.hip
+enum CtxSlot { WS_EIG, WS_DC, WS_STSEL, WS_TRD, WS_TRDP, WS_CUHF, WS_OCC, WS_CTX_SLOTS };  // eig.hip, dc.hip, stsel.hip, trd.hip, trdp.hip, cuhf_dev.hip, occupy.hip
 enum TableSlot { WS_FOCK, WS_EX, WS_EXLR, WS_COULOMB_BATCH, WS_EXLR_BATCH, WS_TABLE_SLOTS };  // fock.hip, exchange.hip, exchange_lr.hip, fock.hip, exchange_lr.hip
 
 template <int NSLOTS>

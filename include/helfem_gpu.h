@@ -498,6 +498,32 @@ int hfg_eig_blocks_dev(hfg_ctx *ctx, int64_t N, const double *dF, const double *
 int hfg_eig_assemble_dev(hfg_ctx *ctx, int64_t N, int nblk, const int64_t *blk_ptr, const int64_t *blk_idx,
                          const double *dBlockBuf, double *dE, double *dC);
 int hfg_form_density_dev(hfg_ctx *ctx, int64_t N, int64_t ncols, const double *dC, int64_t nocc, double *dP);
+/* Fractional occupations by symmetry block, on device pointers.  dE (ncols) and dC (N x ncols, leading dimension N) as
+ * hfg_eig_gsym_sub_dev and hfg_eig_assemble_dev leave them: ascending energies, the blocks' columns interleaved, every column
+ * exactly zero outside its block.  dBlockId (device, N ints): the block of every row, as the step objects hold it.  occ_ptr
+ * (host, nblk + 1, occ_ptr[0] = 0) and occ (host, nslots = occ_ptr[nblk] values in [0, 1]): the occupations of block b, lowest
+ * level first, at occ[occ_ptr[b] .. occ_ptr[b + 1]).  Slot occ_ptr[b] + k receives the k-th column of block b in the order of
+ * (E, column index) -- for sorted energies, the order of dC -- times sqrt(occ[occ_ptr[b] + k]) in dCocc (N x nslots), its energy
+ * in dEocc and its occupation in dFocc; an occupation of 0 gives a zero column.  A column belongs to the block of the row of
+ * its entry of largest magnitude (the lowest such row).  dCocc dCocc^T is then the density sum_i f_i c_i c_i^T, and the panel
+ * serves wherever the occupied orbitals do as the factors of a density (hfg_form_density_dev, hfg_exchange_occ_dev, the
+ * low-rank error of hfg_diis_update_devptr, none of which assumes orthonormal columns).
+ * Three launches on the context's stream, ordered behind the caller's work there; every output has one writer at a fixed place
+ * (no atomics: bitwise repeatable); dE and dC are only read.  No argument is read after the return.  The host synchronises
+ * only when something is new: the first call with a block-id array (address, N, nblk) reads it back once to count the rows of
+ * every block -- the array at an address is taken to keep its contents until hfg_occupy_forget_blocks -- and a call whose
+ * occupation lists differ from the previous call's drains the stream before staging them; an SCF run does neither after
+ * its first iteration.  Refused before any launch (status 1, hfg_last_error): nblk < 1, ncols < N, an occupation outside
+ * [0, 1] -- these before the context is touched -- and more occupations for a block than it has rows.
+ * Profile scope: "occupy". */
+int hfg_occupy_blocks_devptr(hfg_ctx *ctx, int64_t N, int64_t ncols, const double *dE, const double *dC,
+                             const int *dBlockId /* device, N */, int nblk, const int64_t *occ_ptr /* host, nblk + 1 */,
+                             const double *occ /* host, nslots */, double *dCocc /* N x nslots */, double *dEocc /* nslots */,
+                             double *dFocc /* nslots */);
+/* The rows per block that hfg_occupy_blocks_devptr counted for the block-id array it saw last are dropped: the next call reads
+ * the array back again.  For a caller that rewrites a block-id array in place, or whose allocator hands a new array the address
+ * of an old one with the same N and nblk. */
+int hfg_occupy_forget_blocks(hfg_ctx *ctx);
 int hfg_gemm_dev(hfg_ctx *ctx, int transA, int transB, int64_t m, int64_t n, int64_t k, const double *dA,
                  int64_t lda, const double *dB, int64_t ldb, double *dC, int64_t ldc);
 
@@ -636,7 +662,7 @@ int hfg_chk_read_diatomic_basis(hfg_chk *chk, int lpad, hfg_basis **basis);
  * names: "coulomb", "coulomb_batch" (the batched build; "coulomb_batch_tei": its pass over the tables), "xc", "exchange" (the full-range build; "exchange_yukawa" / "exchange_erfc": the screened build of
  * hfg_rs_exchange and of the range-separated hybrids; "exchange_mix": the build on the mixed-kernel set, "exchange_mix_tables":
  * its mixing, once), "eig_reduce", "eig_tridiag", "eig_tridiag_solve",
- * "eig_backtransform", "gemm", "density", "scatter". */
+ * "eig_backtransform", "gemm", "density", "scatter", "occupy" (hfg_occupy_blocks_devptr). */
 int hfg_profile_enable(hfg_ctx *ctx, int on);
 int hfg_profile_reset(hfg_ctx *ctx);
 int hfg_profile_get(hfg_ctx *ctx, const char *name, double *ms, int64_t *launches);
